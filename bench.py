@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path on N MI355X (one process per GPU).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K headline steps, writes the last step's result if --dump-outputs is given
+(DIR/msm_result_affine.npy) and prints the line.  Everything else below -- the check against k*G, the extras, the FFT leg,
+the CPU baseline -- runs only under --full.
 
 Metric (BASELINE.json): G1 scalar-muls/sec of a BLS12-381 G1 MSM, inputs resident in HBM.
   value   ONE MSM per step through the PLAIN entry -- ark_hip_msm_sw_device on raw bases, nothing precomputed: what
@@ -175,7 +179,13 @@ def main():
     ap.add_argument("--fft-steps", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-log-n", type=int, default=24)
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip every side measurement")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the MSM side measurements (the FFT leg and the CPU baseline still run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the headline against k*G and run every side measurement: extras, FFT leg, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's MSM result (affine x|y as 32-bit words, float64) "
+                         "to DIR/msm_result_affine.npy")
     args = ap.parse_args()
 
     import torch
@@ -338,9 +348,15 @@ def main():
     bases, scalars_h, scalars = make_inputs(n, first, 0xA11CE + rank)
     result, elapsed, phases = run_timed(lambda sc: A.msm_bigint(cid, bases, sc), scalars, args.warmup, args.steps,
                                         sharded=lambda sc: D.msm_bigint_sharded(cid, bases, sc))
-    want = expected_affine(scalars_h, first)
-    exact = bool(np.array_equal(A.into_affine(cid, result), want)) if rank == 0 else None
-    extras = not args.no_extras
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        words = np.ascontiguousarray(A.into_affine(cid, result), dtype=np.uint64).view(np.uint32)   # exact in float64
+        np.save(os.path.join(args.dump_outputs, "msm_result_affine.npy"), words.astype(np.float64))
+    want = exact = None
+    if args.full:
+        want = expected_affine(scalars_h, first)
+        exact = bool(np.array_equal(A.into_affine(cid, result), want)) if rank == 0 else None
+    extras = args.full and not args.no_extras
     if start_guard is not None:
         start_guard.cancel()
 
@@ -392,7 +408,7 @@ def main():
                        "pairs_per_gpu": n, "sharding": "base-range, %d rank(s), partials all-gathered" % world,
                        "exchange": exchange},
             "bit_exact_vs_kG": exact,
-            "kG_source": _ORACLE[1],
+            "kG_source": _ORACLE[1] if args.full else None,
             "phases_ms": {"digits": phases[0], "partition_hist_scan": phases[1], "partition_sort_order": phases[2],
                           "accumulate": phases[3], "reduce": phases[4], "device_total": phases[5]},
             "roofline": {"bound": "hbm", "kernel": ACC_KERNEL,
@@ -726,7 +742,7 @@ def main():
     # ---- FFT leg (rank 0's GPU; the FFT config is single-GPU) ---------------------------------------
     # the reference's bench shapes (poly/benches/fft.rs:71-152): in-place FFT, IFFT and their coset variants on Vec<Fr>
     fft = None
-    if rank == 0 and args.fft_steps > 0:
+    if rank == 0 and args.full and args.fft_steps > 0:
         kf = args.fft_log_n
         nf = 1 << kf
         dom = A.Radix2EvaluationDomain.new(FIELD, nf)
@@ -941,7 +957,7 @@ def main():
 
     # ---- CPU baseline: the oracle's msm_bigint_wnaf restatement on the host cores, bounded sample ---
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O  # test infrastructure: used here only as the timed CPU baseline
         ns = 1 << min(args.cpu_sample_log_n, log_local)

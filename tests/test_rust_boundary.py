@@ -19,6 +19,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "trait_items.json")
+FACTS = os.path.join(ROOT, "tests", "golden", "reference_facts.json")
 
 
 def _trait_body(src, name):
@@ -71,19 +72,54 @@ def _trait_items():
     return golden
 
 
+def _reference_facts():
+    """the names and the version the checks below take from the reference tree, parsed from it"""
+    ws = open(os.path.join(REF, "Cargo.toml")).read()
+    aff = open(os.path.join(REF, "ec/src/models/short_weierstrass/affine.rs")).read()
+    aff = aff[aff.index("pub struct Affine<P: SWCurveConfig>"):]
+    grp = open(os.path.join(REF, "ec/src/models/short_weierstrass/group.rs")).read()
+    grp = grp[grp.index("pub struct Projective<P: SWCurveConfig>"):]
+    tt = open(os.path.join(REF, "test-templates", "src", "msm.rs")).read()
+    r2 = open(os.path.join(REF, "poly", "src", "domain", "radix2", "mod.rs")).read()
+    return {"workspace_version": re.search(r'\[workspace.package\]\s*version = "([^"]+)"', ws).group(1),
+            "affine_fields": re.findall(r"pub(?:\(super\))? (\w+):", aff[:aff.index("}")]),
+            "projective_fields": re.findall(r"pub (\w+):", grp[:grp.index("}")]),
+            "msm_template_fns": sorted(set(re.findall(r"pub fn (\w+)<G: VariableBaseMSM>\(\)", tt))),
+            "radix2_test_fns": sorted(set(re.findall(r"\bfn (\w+)\(\)", r2)))}
+
+
+def _facts():
+    golden = json.load(open(FACTS))
+    if os.path.isdir(REF):
+        assert _reference_facts() == golden, "tests/golden/reference_facts.json is stale: regenerate with tools/make_golden.py"
+    return golden
+
+
+def _scratch_copy(work, subs):
+    """copy the reference's `subs` and its Cargo.toml under `work`, writable: the tree may be read-only, and its modes
+    travel with the copy (git apply replaces a file by unlinking it from its directory)"""
+    import shutil
+    import stat
+    for sub in subs:
+        shutil.copytree(os.path.join(REF, sub), str(work / sub), symlinks=True)
+    shutil.copy(os.path.join(REF, "Cargo.toml"), str(work / "Cargo.toml"))
+    for root, dirs, files in os.walk(str(work)):
+        for name in dirs + files:
+            path = os.path.join(root, name)
+            if not os.path.islink(path):
+                os.chmod(path, os.stat(path).st_mode | stat.S_IWUSR)
+
+
 def test_patches_apply_to_the_reference_tree(tmp_path):
     """The series applies IN ORDER (0004 / 0005 build on the hooks 0001-0003 add) to a scratch copy of the subtrees it
     touches -- the reference itself is never written."""
     if not os.path.isdir(REF):
         pytest.skip("reference tree not present on this box")
-    import shutil
     patches = sorted(p for p in os.listdir(os.path.join(ROOT, "patches")) if p.endswith(".patch"))
     assert len(patches) >= 5
     work = tmp_path / "ref"
     work.mkdir()
-    for sub in ("ec", "poly", "curves"):
-        shutil.copytree(os.path.join(REF, sub), str(work / sub), symlinks=True)
-    shutil.copy(os.path.join(REF, "Cargo.toml"), str(work / "Cargo.toml"))
+    _scratch_copy(work, ("ec", "poly", "curves"))
     for p in patches:
         r = subprocess.run(["git", "apply", "-p1", os.path.join(ROOT, "patches", p)], cwd=str(work), capture_output=True, text=True)
         assert r.returncode == 0, (p, r.stderr)
@@ -161,9 +197,7 @@ def test_rust_ffi_declarations_match_the_header():
 
 
 def test_crates_target_the_reference_version():
-    if os.path.isdir(REF):
-        ws = open(os.path.join(REF, "Cargo.toml")).read()
-        assert re.search(r'\[workspace.package\]\s*version = "0.6.0"', ws)
+    assert _facts()["workspace_version"] == "0.6.0"
     for crate in ("ark-hip-sys", "ark-hip", "ark-hip-curves"):
         toml = open(os.path.join(ROOT, "rust", crate, "Cargo.toml")).read()
         deps = re.findall(r'^(ark-(?:ff|ec|poly|serialize|std|bls12-381|bls12-377|bn254)) = \{ version = "([^"]+)"', toml, flags=re.M)
@@ -203,15 +237,9 @@ def test_layout_guard_checks_offsets_not_only_sizes():
     assert "use core::mem::{offset_of, size_of, MaybeUninit};" in msm_rs
     toml = open(os.path.join(ROOT, "rust", "ark-hip", "Cargo.toml")).read()
     assert re.search(r'rust-version = "1\.(7[7-9]|[89]\d)"', toml), "offset_of! needs Rust 1.77"
-    if os.path.isdir(REF):
-        aff = open(os.path.join(REF, "ec/src/models/short_weierstrass/affine.rs")).read()
-        body = aff[aff.index("pub struct Affine<P: SWCurveConfig>"):]
-        body = body[:body.index("}")]
-        assert re.findall(r"pub(?:\(super\))? (\w+):", body) == ["x", "y", "infinity"]
-        grp = open(os.path.join(REF, "ec/src/models/short_weierstrass/group.rs")).read()
-        body = grp[grp.index("pub struct Projective<P: SWCurveConfig>"):]
-        body = body[:body.index("}")]
-        assert re.findall(r"pub (\w+):", body) == ["x", "y", "z"]
+    facts = _facts()
+    assert facts["affine_fields"] == ["x", "y", "infinity"]
+    assert facts["projective_fields"] == ["x", "y", "z"]
 
 
 def test_device_vec_closes_the_transform_chain():
@@ -257,9 +285,7 @@ def test_group_coefficients_reach_the_device_from_the_domain_hook():
     assert "curve_field != fid" in body and "coeffs.truncate(len)" in body
     decl = _c_decls()
     assert decl["ark_hip_fft_group_in_place"] == 4 and decl["ark_hip_fft_group_in_place_device"] == 4
-    if os.path.isdir(REF):
-        grp = open(os.path.join(REF, "ec/src/models/short_weierstrass/group.rs")).read()
-        assert "pub struct Projective<P: SWCurveConfig>" in grp
+    assert _facts()["projective_fields"] == ["x", "y", "z"]   # (parsed from `pub struct Projective<P: SWCurveConfig>`)
 
 
 def _strip_comments(src):
@@ -296,12 +322,9 @@ def test_served_marker_trait_replaces_type_name_sniffing(tmp_path):
         assert "+    const CURVE: core::ffi::c_int = ark_hip::%s;" % cid in p2, cid
     assert p2.count("+unsafe impl ark_hip::HipServed for Config {") == 5
     if os.path.isdir(REF):   # on the patched tree every impl sits in the file of the config the id names
-        import shutil
         work = tmp_path / "ref"
         work.mkdir()
-        shutil.copytree(os.path.join(REF, "curves"), str(work / "curves"), symlinks=True)
-        shutil.copytree(os.path.join(REF, "ec"), str(work / "ec"), symlinks=True)
-        shutil.copy(os.path.join(REF, "Cargo.toml"), str(work / "Cargo.toml"))
+        _scratch_copy(work, ("curves", "ec"))
         for p in ("0001-ark-ec-msm_bigint-hook.patch", "0002-curves-hip-feature.patch"):
             r = subprocess.run(["git", "apply", "-p1", os.path.join(ROOT, "patches", p)], cwd=str(work), capture_output=True, text=True)
             assert r.returncode == 0, (p, r.stderr)
@@ -340,13 +363,11 @@ def test_one_command_recipe_and_test_crate_for_a_box_with_cargo():
     for needle in ("HipRadix2EvaluationDomain as Dom", "fn fft_correctness()", "fn degree_aware_fft_correctness()",
                    "fn device_matches_the_cpu_domain()", "fn fft_ifft_identity()"):
         assert needle in dom, needle
-    if os.path.isdir(REF):   # the templates and tests this crate instantiates / restates exist where it says
-        tt = open(os.path.join(REF, "test-templates", "src", "msm.rs")).read()
-        for fn in ("test_var_base_msm", "test_var_base_msm_mixed_scalars", "test_var_base_msm_specialized",
-                   "test_chunked_pippenger", "test_hashmap_pippenger"):
-            assert "pub fn %s<G: VariableBaseMSM>()" % fn in tt, fn
-        r2 = open(os.path.join(REF, "poly", "src", "domain", "radix2", "mod.rs")).read()
-        for fn in ("test_fft_correctness", "degree_aware_fft_correctness", "parallel_fft_consistency", "test_fft_ifft_identity"):
-            assert "fn %s()" % fn in r2, fn
+    facts = _facts()   # the templates and tests this crate instantiates / restates exist where it says
+    for fn in ("test_var_base_msm", "test_var_base_msm_mixed_scalars", "test_var_base_msm_specialized",
+               "test_chunked_pippenger", "test_hashmap_pippenger"):
+        assert fn in facts["msm_template_fns"], fn
+    for fn in ("test_fft_correctness", "degree_aware_fft_correctness", "parallel_fft_consistency", "test_fft_ifft_identity"):
+        assert fn in facts["radix2_test_fns"], fn
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "rust/ci.sh" in integ

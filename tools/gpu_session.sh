@@ -4,7 +4,7 @@
 # Everything lands in gpurun_out/TAG/.  Steps (each under its own timeout so that a hang cannot eat the box):
 #   tests[:K]            pytest -m gpu (optionally -k K)                      -> tests.log
 #   smoke                __graft_entry__.smoke()                              -> smoke.log
-#   bench[:ARGS]         python bench.py ARGS                                 -> bench.json / bench.err
+#   bench[:ARGS]         python bench.py ARGS (--full for the side legs)      -> bench.json / bench.err
 #   kt                   rocprofv3 --kernel-trace of a short bench            -> kernel_stats.txt
 #   pmc                  FETCH_SIZE / WRITE_SIZE passes + gather calibration  -> pmc_traffic.json, pmc_*.txt
 #                        (needs csrc/ubench/ubench.bin: hipcc --offload-arch=gfx950 -O3 -o ubench.bin ubench.hip)
@@ -30,7 +30,7 @@ O=$PWD/gpurun_out/$tag
 R=$PWD
 export TMPDIR=/tmp
 db() { find $O/$1 -name "*results.db" | head -1; }
-SHORT="python $R/bench.py --steps 3 --warmup 0 --no-cpu-baseline --no-extras --fft-steps 3"
+SHORT="python $R/bench.py --full --steps 3 --warmup 0 --no-cpu-baseline --no-extras --fft-steps 3"
 for step in "$@"; do
   IFS=':' read -r -a a <<< "$step"
   case ${a[0]} in
@@ -41,7 +41,7 @@ for step in "$@"; do
     bench) (timeout 900 python bench.py ${a[@]:1} > $O/bench.json) 2> $O/bench.err ;;
     kt)
       cd /tmp
-      timeout 600 rocprofv3 --kernel-trace -d $O/p_kt -o kt -- python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $O/kt.out 2> $O/kt.err
+      timeout 600 rocprofv3 --kernel-trace -d $O/p_kt -o kt -- python $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $O/kt.out 2> $O/kt.err
       cd $R
       python tools/rocpd_stats.py $(db p_kt) --min-us 100 > $O/kernel_stats.txt 2>> $O/post.err
       rm -rf $O/p_kt ;;
@@ -76,7 +76,7 @@ for step in "$@"; do
       python tools/rocpd_stats.py $(db p_sq) --pmc --min-us 50 > $O/pmc_sq$suffix.txt 2>> $O/post.err
       rm -rf $O/p_sq ;;
     n2gloo)
-      (ARK_BENCH_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus 2 --steps 3 --warmup 1 --log-n 21 --log-total 22 --fft-log-n 20 --fft-steps 4 > $O/bench_n2_gloo.json) 2> $O/bench_n2_gloo.err ;;
+      (ARK_BENCH_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 bench.py --full --gpus 2 --steps 3 --warmup 1 --log-n 21 --log-total 22 --fft-log-n 20 --fft-steps 4 > $O/bench_n2_gloo.json) 2> $O/bench_n2_gloo.err ;;
     soak) (timeout 1200 python tools/soak.py ${a[1]:-200} 2>&1 | tail -4) > $O/soak.log ;;
     skewsoak) (timeout 1500 python tools/skew_soak.py ${a[1]:-100} ${a[2]:-2024} ${a[3]} ${a[4]} 2>&1 | grep -v "^it " | tail -8) >> $O/skew_soak.log ;;
     mulbench)

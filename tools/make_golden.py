@@ -87,6 +87,9 @@ def main():
     with open(T.GOLDEN, "w") as f:
         json.dump(T._reference_items(), f, indent=1)
     print("trait item lists written to %s" % T.GOLDEN)
+    with open(T.FACTS, "w") as f:
+        json.dump(T._reference_facts(), f, indent=1)
+    print("reference names / version written to %s" % T.FACTS)
 
 
 if __name__ == "__main__":
