@@ -225,3 +225,88 @@ def dft(field, coeffs, log_n, offset=1, inverse=False):
             acc = (acc + c[k] * pow(gi, j * k, p)) % p
         out.append(acc * ni % p * pow(oi, j, p) % p)
     return out
+
+
+# ---- closed-form transforms of a geometric input, and the FFT pass planner (tests/test_gpu_fft_plans.py) ----
+def geometric_fft(field, log_n, a, b, js, offset=1, inverse=False, num_coeffs=None):
+    """Outputs at the indices `js` of the transform of x_i = a b^i (ints, canonical), in closed form.
+
+    forward (coset offset h, first `num_coeffs` = c inputs nonzero, the rest zero -- the degree-aware case):
+        X_j = sum_{i<c} a (b h w^j)^i = a (1 - (b h w^j)^c) / (1 - b h w^j)
+    inverse (evaluations y_j = a b^j over the whole domain; coset offset h):
+        x_i = n^-1 h^-i sum_{j<n} a b^j w^-ij = n^-1 h^-i a (1 - b^n) / (1 - b w^-i)      (w^-in = 1)
+    Exact for every index and O(log n) per index: no O(n) work, so it serves any size up to the two-adicity."""
+    p = MODULI[field][0]
+    n = 1 << log_n
+    w = root_of_unity(field, log_n)
+    out = []
+    if not inverse:
+        c = n if num_coeffs is None else num_coeffs
+        bh = b * offset % p
+        for j in js:
+            z = bh * pow(w, int(j), p) % p
+            den = (1 - z) % p
+            assert den, "b h w^j = 1: pick another ratio"
+            out.append(a * (1 - pow(z, c, p)) * pow(den, -1, p) % p)
+        return out
+    assert num_coeffs is None or num_coeffs == n
+    wi, hi = pow(w, -1, p), pow(offset, -1, p)
+    s = pow(n, -1, p) * a * (1 - pow(b, n, p)) % p
+    for i in js:
+        den = (1 - b * pow(wi, int(i), p)) % p
+        assert den, "b w^-i = 1: pick another ratio"
+        out.append(s * pow(hi, int(i), p) * pow(den, -1, p) % p)
+    return out
+
+
+def sample_indices(log_n, extra=300, seed=0):
+    """Where index arithmetic goes wrong: 0, 1, n/2 +- 1, n - 1, every 2^m and 2^m - 1, plus `extra` random indices."""
+    n = 1 << log_n
+    s = {0, n - 1, n >> 1, (n >> 1) + 1, max((n >> 1) - 1, 0), 1 % n}
+    for m in range(log_n):
+        s.update((1 << m, (1 << m) - 1))
+    rng = np.random.default_rng(seed)
+    s.update(int(v) for v in rng.integers(0, n, size=extra))
+    return np.array(sorted(j for j in s if j < n), dtype=np.int64)
+
+
+def fft_plan(k, zlog=0, kp=None, tile_log=None, plan=None, balanced=False, ascending=True, carry_free=False):
+    """Stage counts per pass that csrc/fft.cuh (fft_run_device) executes for a size-2^k transform whose first `zlog`
+    stages are skipped (degree-aware).  kp / tile_log / plan / balanced stand for ARK_HIP_FFT_KP, _TILE_LOG, _PLAN (a
+    list) and _BALANCED, ascending=False for ARK_HIP_FFT_ASCENDING=0, carry_free for the 9 x 29-bit pass kernel."""
+    if k <= 10:   # FFT_SINGLE_MAX: one workgroup runs it whole, a degree-aware input is zero-filled first
+        return [k]
+    kx = k - zlog
+    tl = 10
+    if not carry_free and tile_log is not None and 10 <= tile_log <= 12:
+        tl = tile_log
+    maxkp = kp if kp is not None and 5 <= kp <= 8 else 8
+    if tl > 10:
+        maxkp = tl - 1
+    P = (kx + maxkp - 1) // maxkp
+    kps = [kx // P + (1 if i < kx % P else 0) for i in range(P)]
+    if not balanced:   # pairs of odd passes trade one stage
+        for i in range(P):
+            for j in range(P - 1, i, -1):
+                if kps[i] & 1 and kps[j] & 1 and kps[i] < maxkp and kps[j] > 2:
+                    kps[i] += 1
+                    kps[j] -= 1
+                    break
+    if ascending and P <= 3:
+        kps.sort()
+    if plan is not None:   # honoured only when every count is in 1..tile and they sum to kx (at most 8 are read)
+        q = list(plan)[:8]
+        if q and all(1 <= v <= tl for v in q) and sum(q) == kx:
+            kps = q
+    return kps
+
+
+def degree_aware_zlog(log_n, num_coeffs):
+    """stages a degree-aware forward transform of `num_coeffs` nonzero inputs skips (csrc/capi_hostmath.hpp)"""
+    n = 1 << log_n
+    if num_coeffs == 0 or num_coeffs * 4 > n:
+        return 0
+    d = 2
+    while d < num_coeffs:
+        d <<= 1
+    return log_n - d.bit_length() + 1
