@@ -6,6 +6,7 @@
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "capi_cache.hpp"
+#include "lazytest_api.hpp"
 using namespace arkhip;
 using namespace arkhip::capi;
 
@@ -15,7 +16,49 @@ int msm_sharded_emulated(int curve, int world, const void* const* d_bases, const
                          int scalars_are_montgomery, uint64_t* out_xyz, int* path);   // capi_comm.hip
 }
 }
+namespace arkhip {   // raw-limb hooks: testops_curve.hip (per curve), testops_field.hip (per scalar field)
+#define ARK_DECL_LAZYTEST_RAW(NAME) \
+  int test_lazy_raw_op_##NAME(int op, int k, int h, const void* d_in, void* d_out, size_t n, hipStream_t s);
+#define ARK_DECL_LAZYTEST_ACC(NAME) \
+  int test_lazy_acc_op_##NAME(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s);
+ARK_DECL_LAZYTEST_RAW(BN254_G1) ARK_DECL_LAZYTEST_RAW(BLS12_381_G1) ARK_DECL_LAZYTEST_RAW(BLS12_377_G1)
+ARK_DECL_LAZYTEST_RAW(BLS12_377_G2) ARK_DECL_LAZYTEST_RAW(BLS12_381_G2)
+ARK_DECL_LAZYTEST_RAW(BN254_FR) ARK_DECL_LAZYTEST_RAW(BLS12_381_FR) ARK_DECL_LAZYTEST_RAW(BLS12_377_FR)
+ARK_DECL_LAZYTEST_ACC(BN254_G1) ARK_DECL_LAZYTEST_ACC(BLS12_381_G1) ARK_DECL_LAZYTEST_ACC(BLS12_377_G1)
+ARK_DECL_LAZYTEST_ACC(BLS12_377_G2) ARK_DECL_LAZYTEST_ACC(BLS12_381_G2)
+#undef ARK_DECL_LAZYTEST_RAW
+#undef ARK_DECL_LAZYTEST_ACC
+}  // namespace arkhip
 namespace {
+typedef int (*lazy_raw_fn)(int, int, int, const void*, void*, size_t, hipStream_t);
+// FpL / Fft29 ops: the unit of the field (a base field through the G1 curve over it); Fp2L ops: the G2 unit over the base field
+lazy_raw_fn lazy_raw_fn_of(int field, bool x2) {
+  switch (field) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_FQ: return x2 ? nullptr : test_lazy_raw_op_BN254_G1;
+    case ARK_HIP_BN254_FR: return x2 ? nullptr : test_lazy_raw_op_BN254_FR;
+    case ARK_HIP_BLS12_381_FQ: return x2 ? test_lazy_raw_op_BLS12_381_G2 : test_lazy_raw_op_BLS12_381_G1;
+    case ARK_HIP_BLS12_381_FR: return x2 ? nullptr : test_lazy_raw_op_BLS12_381_FR;
+    case ARK_HIP_BLS12_377_FQ: return x2 ? test_lazy_raw_op_BLS12_377_G2 : test_lazy_raw_op_BLS12_377_G1;
+    case ARK_HIP_BLS12_377_FR: return x2 ? nullptr : test_lazy_raw_op_BLS12_377_FR;
+#endif
+  }
+  return nullptr;
+}
+elementwise_fn lazy_acc_fn_of(int curve) {
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case 0: return test_lazy_acc_op_BN254_G1;
+    case 1: return test_lazy_acc_op_BLS12_381_G1;
+    case 2: return test_lazy_acc_op_BLS12_377_G1;
+    case 3: return test_lazy_acc_op_BLS12_377_G2;
+    case 4: return test_lazy_acc_op_BLS12_381_G2;
+#endif
+  }
+  return nullptr;
+}
+// limbs of the carry-free form of a field (params.hpp LZ_L): 14 x 28 bits for the 384-bit fields, 9 x 29 bits otherwise
+int lazy_limbs(int field) { return (field == ARK_HIP_BLS12_381_FQ || field == ARK_HIP_BLS12_377_FQ) ? 14 : 9; }
 elementwise_fn field_op_fn(int field) {
   switch (field) {
 #ifndef ARK_HIP_DEV
@@ -115,6 +158,43 @@ int ark_hip_test_point_op(int curve, int kind, const uint64_t* acc, const uint64
   return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, point_op_fn(curve), kind, n);
 }
 
+int ark_hip_test_lazy_raw_op(int field, int op, int k, int h, const uint32_t* in, uint32_t* out, size_t n) {
+  using namespace arkhip::lazytest;
+  if (field < 0 || field > 5 || !in || !out) return ARK_HIP_ERR_ARG;
+  const Row* row = row_of(op);
+  if (!row || !params_ok(op, k, h)) return ARK_HIP_ERR_ARG;
+  const bool x2 = op >= X2_FIRST;
+  lazy_raw_fn fn = lazy_raw_fn_of(field, x2);
+  if (!fn || (x2 && (n & 1))) return ARK_HIP_ERR_ARG;
+  const size_t L = (size_t)lazy_limbs(field);
+  const size_t ibytes = n * (size_t)row->arity * L * 4, obytes = n * (L + 1) * 4;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) return 0;
+  if (c->stage_a.ensure(ibytes) || c->stage_c.ensure(obytes)) return ARK_HIP_ERR_NOMEM;
+  ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, ibytes, hipMemcpyHostToDevice, c->stream));
+  const int rc = fn(op, k, h, c->stage_a.p, c->stage_c.p, n, c->stream);
+  if (rc) return rc == -1 ? ARK_HIP_ERR_ARG : rc;   // -1: not an op of this field's unit (Fft29 outside the scalar fields, ..)
+  ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, obytes, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int ark_hip_test_lazy_acc_op(int curve, int kind, const void* acc, const void* other, void* out, size_t n) {
+  using namespace arkhip::lazytest;
+  if (curve < 0 || curve > 4 || !acc || !out || kind < 0 || kind >= ACC_KINDS) return ARK_HIP_ERR_ARG;
+  const size_t fb = (size_t)CURVES[curve].fe_words * 8;
+  const size_t L = curve == 0 ? 9 : 14;
+  const size_t slot = (curve >= 3 ? 8 * L + 1 : 4 * L + 1) * 4;   // LazyK::WORDS words
+  const size_t abytes = n * (kind == ACC_FROM_BUCKET ? 4 * fb : slot);
+  size_t bbytes = 0;
+  if (kind <= ACC_MDBL_NEG) bbytes = n * 2 * fb;
+  else if (kind == ACC_ADD) bbytes = n * 4 * fb;
+  else if (kind == ACC_ADD_ACC) bbytes = n * slot;
+  const size_t rbytes = n * (kind == ACC_TO_BUCKET ? 4 * fb : slot);
+  if (bbytes && !other) return ARK_HIP_ERR_ARG;
+  return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, lazy_acc_fn_of(curve), kind, n);
+}
 
 int ark_hip_test_msm_host_fold(int curve, const uint64_t* parts, int windows, int nbits, int log2_l0, const int* widths,
                                uint64_t* out_xyz) {

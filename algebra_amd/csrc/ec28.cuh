@@ -17,16 +17,17 @@
 // semi-normalised (< 3 2^28).
 //
 // Two limb geometries share these formulas (FpL::W / L from params.hpp).  The bounds in the comments are for 14 x 28
-// bits (Fp384: R' / p > 2048, bases enter below 2^8 p).  For 9 x 29 bits (BN254 Fq: R' / p >= 169, bases enter below
+// bits (Fp384: R' / p >= 2520, bases enter below 2^8 p).  For 9 x 29 bits (BN254 Fq: R' / p >= 169, bases enter below
 // 2^5 p) the same chain gives
-//   x2, y2 < 32;  first point / U2 / S2 < 32 * 1.06 / 169 + 1 < 1.21;  P in (0.9, 7.21), R in (0.8, 3.21) -- both SWEPT to
+//   x2, y2 < 32;  first point < 32 / 169 + 1 < 1.21 (so are zz, zzz right after from_bucket);  U2 / S2 < 32 * 1.21 / 169 + 1 < 1.23;
+//   P in (0.9, 7.23), R in (0.78, 3.23) -- both SWEPT to
 //   normalised limbs (FpL::sub_op: a 29-bit column has no room for two semi-normalised operands, 90 2^58 > 2^64);
-//   PP < 7.21^2 / 169 + 1 < 1.31 (the zero test needs < 2);  PPP < 7.21 * 1.31 / 169 + 1 < 1.06;  Q < 5.07 * 1.31 / 169 + 1
+//   PP < 7.23^2 / 169 + 1 < 1.31 (the zero test needs < 2);  PPP < 7.23 * 1.31 / 169 + 1 < 1.06;  Q < 5.07 * 1.31 / 169 + 1
 //   < 1.04;  R^2 < 1.07;  X3 = R^2 - PPP - 2 Q + 4p in (0.8, 5.07);  t = Q - X3 + 6p < 7.04 (s);
-//   Y3 < (3.21 * 7.04 + 2 * 1.06) / 169 + 1 < 1.15;  ZZ3 < 1.06 * 1.31 / 169 + 1 < 1.01;  ZZZ3 < 1.01
+//   Y3 < (3.23 * 7.04 + 2 * 1.06) / 169 + 1 < 1.15;  ZZ3 < 1.06 * 1.31 / 169 + 1 < 1.01;  ZZZ3 < 1.01
 //   columns: (n x s) 9 x 3 2^58 + (limbs < 2^30) x n 9 x 2 2^58 + reduction 9 x 2^58 = 54 2^58 < 2^64
 //   full addition: U1 = X1 ZZ2 < 5.07 * 32 / 169 + 1 < 1.97 (hence P = U2 - U1 + 3p), S1 < 1.21 * 32 / 169 + 1 < 1.23,
-//   P in (1.03, 4.21), PP < 1.11; leaving: shr_mod<5> output < 5.07 / 32 + 1 < 2.
+//   P in (1.03, 4.23), PP < 1.11; leaving: shr_mod<5> output < 5.07 / 32 + 1 < 2.
 #pragma once
 #include "ec.cuh"
 #include "fp28.cuh"
@@ -35,7 +36,8 @@ namespace arkhip {
 
 template <class P>
 struct XYZZL {
-  FpL<P> x, y, zz, zzz;  // x < 5.01, y < 1.13, zz, zzz < 1.01 (all n)
+  FpL<P> x, y, zz, zzz;  // x < 5.01, y < 1.13, zz, zzz < 1.13 (all n); zz, zzz < 1.01 once an addition has multiplied them --
+                         // 1.13 is what from_bucket and the first full addition leave (one product with the residue 1)
   bool inf;
 };
 
@@ -122,7 +124,7 @@ ARK_HD bool xyzz_madd_lazy(XYZZL<P>& acc, const FpL<P>& x2, const FpL<P>& y2) {
     acc.inf = false;
     return false;
   }
-  const F u2 = F::mul(x2, acc.zz);                                // < 256 * 1.01 / 2048 + 1 < 1.13 (n)
+  const F u2 = F::mul(x2, acc.zz);                                // < 256 * 1.13 / 2520 + 1 < 1.13 (n; R' / p >= 2520)
   const F s2 = F::mul(y2, acc.zzz);                               // < 1.13 (n)
   const F pd = F::template sub_op<6>(u2, acc.x);                  // U2 - X1 + 6p: (0.99, 7.13), s (n on 29-bit limbs)
   const F rd = F::template sub_op<2>(s2, acc.y);                  // S2 - Y1 + 2p: (0.87, 3.13), s (n on 29-bit limbs)
@@ -150,7 +152,7 @@ ARK_HD bool xyzz_madd_lazy(XYZZL<P>& acc, const FpL<P>& x2, const FpL<P>& y2) {
 // repacked (below 256 p: lazy_operands_of) or another accumulator's (small): they enter through products with acc's
 // small coordinates only.  Bounds for the large case:
 //   U1 = X1 ZZ2 < 5.01 * 256 / 2048 + 1 < 1.63, U2 = X2 ZZ1 < 1.13, S1 = Y1 ZZZ2 < 1.15, S2 = Y2 ZZZ1 < 1.13  (n)
-//   P = U2 - U1 + 2p in (0.37, 3.13), R = S2 - S1 + 2p in (0.85, 3.13)  (s);  PP < 1.01, PPP, Q < 1.01  (n)
+//   P = U2 - U1 + 3p in (1.37, 4.13), R = S2 - S1 + 2p in (0.85, 3.13)  (s);  PP < 1.01, PPP, Q < 1.01  (n)
 //   X3 = R^2 - PPP - 2 Q + 4p in (0.99, 5.01) (n);  Y3 < (3.13 * 7.01 + 2 * 1.01) / 2048 + 1 < 1.02;  ZZ3, ZZZ3 < 1.01
 // equal points (P = R = 0 mod p): xyzz_dbl_lazy, in place (rare).
 template <class P>

@@ -17,7 +17,7 @@ namespace arkhip {
 
 template <class FL2>
 struct XYZZL2 {
-  FL2 x, y, zz, zzz;  // x < 7.2 (n), y < 1.11 (n), zz, zzz < 1.02 (n)
+  FL2 x, y, zz, zzz;  // x < 7.2 (n), y < 1.11 (n), zz, zzz < 1.11 (n): what from_bucket leaves; < 1.02 once an addition has multiplied them
   bool inf;
 };
 
@@ -105,12 +105,12 @@ ARK_DEV bool xyzz_madd_lazy2(XYZZL2<FL2>& acc, const FL2& x2, const FL2& y2) {
     acc.inf = false;
     return false;
   }
-  const F u2 = F::template mul<2>(acc.zz, x2);                    // (1.02 * 256 + NB 2 * 256) / R' + 1 < 1.31 (n)
-  const F s2 = F::template mul<2>(acc.zzz, y2);                   // < 1.31 (n)
-  const F pd = F::template sub_sweep<8>(u2, acc.x);               // U2 - X1 + 8p in (0.8, 9.31), n
-  const F rd = F::template sub_sweep<2>(s2, acc.y);               // S2 - Y1 + 2p in (0.89, 3.31), n
+  const F u2 = F::template mul<2>(acc.zz, x2);                    // (1.11 * 256 + NB 2 * 256) / R' + 1 < 1.32 (n)
+  const F s2 = F::template mul<2>(acc.zzz, y2);                   // < 1.32 (n)
+  const F pd = F::template sub_sweep<8>(u2, acc.x);               // U2 - X1 + 8p in (0.8, 9.32), n
+  const F rd = F::template sub_sweep<2>(s2, acc.y);               // S2 - Y1 + 2p in (0.89, 3.32), n
   bool pz;
-  const F pp = F::template sqr<10>(pd, &pz);                      // s < 18.7 * (9.31 + NB 10) / R' + 1 < 1.15, c1 < 1.07; c0 < 3.1 (s)
+  const F pp = F::template sqr<10>(pd, &pz);                      // s < 18.7 * (9.32 + NB 10) / R' + 1 < 1.15, c1 < 1.07; c0 < 3.1 (s)
   if (pz) {                                                       // P = 0: same x -- doubling or infinity (bucket.rs:176-200)
     bool rz;
     (void)F::template sqr<4>(rd, &rz);
@@ -118,12 +118,12 @@ ARK_DEV bool xyzz_madd_lazy2(XYZZL2<FL2>& acc, const FL2& x2, const FL2& y2) {
     acc.inf = true;
     return false;
   }
-  const F ppp = F::template mul<10>(pd, pp);                      // (9.31 * 3.1 + NB 10 * 1.07) / R' + 1 < 1.02 (n)
+  const F ppp = F::template mul<10>(pd, pp);                      // (9.32 * 3.1 + NB 10 * 1.07) / R' + 1 < 1.02 (n)
   const F q = F::template mul<8>(acc.x, pp);                      // (7.2 * 3.1 + NB 8 * 1.07) / R' + 1 < 1.02 (n)
   const F rr = F::template sqr<4>(rd);                            // c0 < 3.1 (s), c1 < 1.01
   const F x3 = F::template sub_b_2c_norm<4>(rr, ppp, q);          // R^2 - PPP - 2 Q + 4p in (0.9, 7.1), n
   const F t = F::template sub_sweep<8>(q, x3);                    // Q - X3 + 8p in (0.9, 9.02), n
-  acc.y = F::template mul_sub<4, 2>(rd, t, acc.y, ppp);           // (3.31 * 9.02 + NB 4 * 9.02 + 2 * 1.02 + NB 1.11 * 1.02) / R' + 1 < 1.04
+  acc.y = F::template mul_sub<4, 2>(rd, t, acc.y, ppp);           // (3.32 * 9.02 + NB 4 * 9.02 + 2 * 1.02 + NB 1.11 * 1.02) / R' + 1 < 1.04
   acc.zz = F::template mul<2>(acc.zz, pp);                        // < 1.01
   acc.zzz = F::template mul<2>(acc.zzz, ppp);                     // < 1.01
   acc.x = x3;
@@ -132,8 +132,8 @@ ARK_DEV bool xyzz_madd_lazy2(XYZZL2<FL2>& acc, const FL2& x2, const FL2& y2) {
 
 // ---- full addition (the reduction and heavy-run kernels) ----
 // acc += b; b's coordinates are a stored bucket's canonical limbs repacked (below 256 p) or another accumulator's.
-//   U1 = X1 ZZ2 < (7.2 * 256 + NB 8 * 256) / R' + 1 < 2.55;  U2, S2 < 1.31;  S1 = Y1 ZZZ2 < (1.11 * 256 + NB 2 * 256) / R' + 1 < 1.32
-//   P = U2 - U1 + 4p in (1.4, 5.31), R = S2 - S1 + 2p in (0.6, 3.31)  (n)
+//   U1 = X1 ZZ2 < (7.2 * 256 + NB 8 * 256) / R' + 1 < 2.55;  U2, S2 < 1.32;  S1 = Y1 ZZZ2 < (1.11 * 256 + NB 2 * 256) / R' + 1 < 1.32
+//   P = U2 - U1 + 4p in (1.45, 5.32), R = S2 - S1 + 2p in (0.68, 3.32)  (n)
 template <class FL2>
 struct XYZZOperands2 { FL2 x, y, zz, zzz; bool inf; };
 template <class FL2>
@@ -182,7 +182,7 @@ ARK_DEV void xyzz_add_lazy2(XYZZL2<FL2>& acc, const FL2& bx, const FL2& by, cons
   const F x3 = F::template sub_b_2c_norm<4>(rr, ppp, q);
   const F t = F::template sub_sweep<8>(q, x3);
   acc.y = F::template mul_sub<4, 2>(rd, t, s1, ppp);
-  acc.zz = F::template mul<2>(F::template mul<2>(acc.zz, bzz), pp);      // inner: (1.02 * 256 + NB 2 * 256) / R' + 1 < 1.31
+  acc.zz = F::template mul<2>(F::template mul<2>(acc.zz, bzz), pp);      // inner: (1.11 * 256 + NB 2 * 256) / R' + 1 < 1.32
   acc.zzz = F::template mul<2>(F::template mul<2>(acc.zzz, bzzz), ppp);
   acc.x = x3;
 }

@@ -372,7 +372,8 @@ struct FpL {
     r.l[L - 1] = (u32)(d[L - 1] + carry);
     return r;
   }
-  // a - b + K p, normalised          (the caller guarantees a - b + K p >= 0; limbs of a, b below 2^30)
+  // a - b + K p, normalised          (the caller guarantees a - b + K p >= 0; limbs of a, b below 3 2^29 -- 3 xx of the
+  // doubling on 29-bit limbs -- so that every signed limb with its carry stays inside 32 bits)
   template <int K>
   ARK_HD static FpL sub(const FpL& a, const FpL& b) {
     int d[L];

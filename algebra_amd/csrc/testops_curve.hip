@@ -2,6 +2,7 @@
 // into libark_hip_test.so only -- the shipped libark_hip.so contains neither these kernels nor their entry points.
 #include "devops.cuh"
 #include "testops.cuh"
+#include "lazytest.cuh"
 #include "internal.hpp"
 #ifndef ARK_TEST_CURVE
 #error "compile with -DARK_TEST_CURVE=BLS12_381_G1 (or another curve of curves.cuh)"
@@ -14,5 +15,14 @@ int ARK_CAT(test_basefield_op_, ARK_TEST_CURVE)(int op, const void* a, const voi
 }
 int ARK_CAT(test_point_op_, ARK_TEST_CURVE)(int kind, const void* acc, const void* other, void* out, size_t n, hipStream_t s) {
   return test_point_op_launch<ARK_TEST_CURVE>(kind, acc, other, out, n, s);
+}
+// raw-limb hooks (lazytest.cuh): a G1 unit serves the FpL ops of its base field, a G2 unit the Fp2L ops over it
+int ARK_CAT(test_lazy_raw_op_, ARK_TEST_CURVE)(int op, int k, int h, const void* in, void* out, size_t n, hipStream_t s) {
+  typedef LazyK<ARK_TEST_CURVE> K;
+  if constexpr (K::LANES == 1) return lazytest::lazy_raw_op_launch<typename K::P, false, void>(op, k, h, in, out, n, s);
+  else return lazytest::lazy_raw_op_launch<typename K::P, false, typename K::FL>(op, k, h, in, out, n, s);
+}
+int ARK_CAT(test_lazy_acc_op_, ARK_TEST_CURVE)(int kind, const void* acc, const void* other, void* out, size_t n, hipStream_t s) {
+  return lazytest::lazy_acc_op_launch<ARK_TEST_CURVE>(kind, acc, other, out, n, s);
 }
 }  // namespace arkhip

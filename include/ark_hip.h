@@ -439,6 +439,17 @@ int ark_hip_test_msm_sharded_emulated(int curve, int world, const void* const* d
 int ark_hip_test_base_hash(const uint64_t* p, size_t words, uint64_t out[2]);
 int ark_hip_test_msm_host_fold(int curve, const uint64_t* parts, int windows, int nbits, int log2_l0, const int* widths,
                                uint64_t* out_xyz);
+/* The carry-free limb arithmetic (csrc/fp28.cuh, fp28x2.cuh, fft.cuh Fft29) ONE OP AT A TIME ON RAW LIMBS: lane t reads `arity`
+ * slots of L words (u32[L]: the W-bit limbs as the test chose them, not canonical words) at in[(t * arity + j) * L] and writes
+ * L + 1 words at out[t * (L + 1)] (word L: the op's boolean result).  The Fp2L ops (op >= 40; field = BLS12-381 / BLS12-377 Fq)
+ * own a lane pair per element: even lane c0, odd lane c1, n even.  op, arity and the (k, h) template parameters served are
+ * THE TABLE of csrc/lazytest_api.hpp -- exactly those of the kernels' call sites; anything else is ARK_HIP_ERR_ARG. */
+int ark_hip_test_lazy_raw_op(int field, int op, int k, int h, const uint32_t* in, uint32_t* out, size_t n);
+/* The bucket additions on carry-free limbs with the accumulator in the PARKED layout of LazyK::park / unpark (4 L + 1 words; G2:
+ * 8 L + 1 per lane pair) on both sides.  kind (csrc/lazytest_api.hpp AccKind): 0 / 1 acc +/- affine base (other: x | y), 2 / 3
+ * acc = +/- 2 base, 4 acc += stored bucket (other: canonical XYZZ), 5 acc += parked accumulator, 6 acc = 2 acc,
+ * 7 from_bucket (acc: canonical XYZZ), 8 to_bucket (out: canonical XYZZ). */
+int ark_hip_test_lazy_acc_op(int curve, int kind, const void* acc, const void* other, void* out, size_t n);
 
 #endif /* ARK_HIP_TEST_HOOKS */
 

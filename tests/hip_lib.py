@@ -64,3 +64,23 @@ def gpu_extend_bases(curve, seed_bases, n, delta_fn):
               "sw_add_affine_device")
         m += cnt
     return buf
+
+
+def lazy_raw_op(field, op, k, h, rows, limbs):
+    """One carry-free limb op on RAW limbs (csrc/lazytest_api.hpp): rows (n lanes, arity * L words) -> (n, L + 1) words,
+    the last one the op's boolean result.  Returns (status, out): parameters outside THE TABLE come back as ARK_HIP_ERR_ARG."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint32)
+    n = rows.shape[0]
+    out = np.zeros((n, limbs + 1), dtype=np.uint32)
+    rc = test_lib().ark_hip_test_lazy_raw_op(field, op, k, h, _p(rows), _p(out), n)
+    return rc, out
+
+
+def lazy_acc_op(curve, kind, acc, other, out_words):
+    """One bucket addition on carry-free limbs with the accumulator in LazyK's parked layout (uint32 words) on both sides."""
+    acc = np.ascontiguousarray(acc, dtype=np.uint32)
+    n = acc.shape[0]
+    o = None if other is None else np.ascontiguousarray(other, dtype=np.uint32)
+    out = np.zeros((n, out_words), dtype=np.uint32)
+    check(test_lib().ark_hip_test_lazy_acc_op(curve, kind, _p(acc), _p(o), _p(out), n), "test_lazy_acc_op")
+    return out

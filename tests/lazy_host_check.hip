@@ -3,7 +3,8 @@
 // products, sums of two products, differences, divisions by powers of two, exact zero tests, and random point sequences
 // through the curve-isomorphism boundary (lazy_from_affine / lazy_from_bucket / lazy_to_bucket) that hit the doubling and
 // infinity branches and the "continue from a stored bucket" path.  The templates are __host__ __device__, so this runs on
-// the CPU.  Built and run by tests/test_lazy_host.py.
+// the CPU.  Built and run by tests/test_lazy_host.py.  (Operands here are random; the same host forms at the LIMITS of their
+// operand classes, limb for limb against an exact model: tests/lazy_raw_host.hip, tests/test_lazy_model_host.py.)
 #include "ec28.cuh"
 #include "curves.cuh"
 #include <stdio.h>
