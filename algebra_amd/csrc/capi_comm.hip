@@ -89,7 +89,7 @@ int sums_reduce(Context* c, int curve, const MsmSumsHeader& mine, const char* d_
     const MsmSumsHeader& o = hh[r];
     err |= o.err != 0;
     same &= o.c == mine.c && o.W == mine.W && o.narrow == mine.narrow && o.shared == mine.shared && o.nbits == mine.nbits &&
-            o.log2L0 == mine.log2L0 && o.Q == mine.Q && o.npairs == mine.npairs;
+            o.L0 == mine.L0 && o.Q == mine.Q && o.npairs == mine.npairs;
   }
   *agree = same;
   if (err) return ARK_HIP_ERR_SCALAR_RANGE;

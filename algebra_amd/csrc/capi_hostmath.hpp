@@ -46,16 +46,16 @@ inline void host_field_ops(int op, const uint64_t* a, const uint64_t* b, uint64_
     z.store(r + i * W);
   }
 }
-// the MSM's host tail on caller-supplied bit sums (ark_hip_test_msm_host_fold)
+// the MSM's host tail on caller-supplied bit sums (ark_hip_test_msm_host_fold, ark_hip_test_msm_host_fold_l0); l0: the level-0 chunk length itself
 template <class C>
-int host_fold(const uint64_t* parts, int windows, int nbits, int log2_l0, const int* widths, uint64_t* out_xyz) {
+int host_fold(const uint64_t* parts, int windows, int nbits, u32 l0, const int* widths, uint64_t* out_xyz) {
   std::vector<int> off((size_t)windows + 1);
   off[0] = 0;
   for (int w = 0; w < windows; w++) {
     if (widths[w] < 1 || widths[w] > 32) return ARK_HIP_ERR_ARG;
     off[w + 1] = off[w] + widths[w];
   }
-  const XYZZ<typename C::F> t = msm_host_fold<C>((const char*)parts, (u32)(nbits + 1), windows, nbits, log2_l0, off.data());
+  const XYZZ<typename C::F> t = msm_host_fold<C>((const char*)parts, (u32)(nbits + 1), windows, nbits, l0, off.data());
   xyzz_to_jac<typename C::F>(t).store(out_xyz);
   return 0;
 }

@@ -196,18 +196,28 @@ int ark_hip_test_lazy_acc_op(int curve, int kind, const void* acc, const void* o
   return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, lazy_acc_fn_of(curve), kind, n);
 }
 
+static int host_fold_dispatch(int curve, const uint64_t* parts, int windows, int nbits, u32 l0, const int* widths, uint64_t* out_xyz) {
+  switch (curve) {
+    case 0: return host_fold<BN254_G1>(parts, windows, nbits, l0, widths, out_xyz);
+    case 1: return host_fold<BLS12_381_G1>(parts, windows, nbits, l0, widths, out_xyz);
+    case 2: return host_fold<BLS12_377_G1>(parts, windows, nbits, l0, widths, out_xyz);
+    case 3: return host_fold<BLS12_377_G2>(parts, windows, nbits, l0, widths, out_xyz);
+    case 4: return host_fold<BLS12_381_G2>(parts, windows, nbits, l0, widths, out_xyz);
+  }
+  return ARK_HIP_ERR_ARG;
+}
 int ark_hip_test_msm_host_fold(int curve, const uint64_t* parts, int windows, int nbits, int log2_l0, const int* widths,
                                uint64_t* out_xyz) {
   if (!parts || !widths || !out_xyz || windows < 1 || windows > 256 || nbits < 0 || nbits > 31 || log2_l0 < 0 || log2_l0 > 16)
     return ARK_HIP_ERR_ARG;
-  switch (curve) {
-    case 0: return host_fold<BN254_G1>(parts, windows, nbits, log2_l0, widths, out_xyz);
-    case 1: return host_fold<BLS12_381_G1>(parts, windows, nbits, log2_l0, widths, out_xyz);
-    case 2: return host_fold<BLS12_377_G1>(parts, windows, nbits, log2_l0, widths, out_xyz);
-    case 3: return host_fold<BLS12_377_G2>(parts, windows, nbits, log2_l0, widths, out_xyz);
-    case 4: return host_fold<BLS12_381_G2>(parts, windows, nbits, log2_l0, widths, out_xyz);
-  }
-  return ARK_HIP_ERR_ARG;
+  return host_fold_dispatch(curve, parts, windows, nbits, 1u << log2_l0, widths, out_xyz);
+}
+// the same tail with the level-0 chunk length given itself (any integer 1 .. 65536, not only a power of two)
+int ark_hip_test_msm_host_fold_l0(int curve, const uint64_t* parts, int windows, int nbits, int l0, const int* widths,
+                                  uint64_t* out_xyz) {
+  if (!parts || !widths || !out_xyz || windows < 1 || windows > 256 || nbits < 0 || nbits > 31 || l0 < 1 || l0 > 65536)
+    return ARK_HIP_ERR_ARG;
+  return host_fold_dispatch(curve, parts, windows, nbits, (u32)l0, widths, out_xyz);
 }
 // Test hook (host only, no device): the verified cache's tag of `words` u64 words -- tests/test_capi_host.py checks that
 // edits the round-4 hash could not see (a two-word edit built from its published constants) change it.

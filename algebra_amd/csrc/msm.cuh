@@ -17,9 +17,10 @@
 //   K4  msm_accumulate    one lane per bucket: gathers its bases (96 B random gathers run at ~3.5 TB/s on this
 //                         chip) and sums them with XYZZ mixed additions on relaxed residues ([0, 2p)).
 //   K4h msm_heavy_*       buckets too long for one lane (skewed scalars): one wave per 2048-entry chunk.
-//   K5a msm_reduce_level  sum_k k*B_k per window, level 0: chunked running sums over <= 32 buckets per lane
-//                         (parallel form of mod.rs:478-484).
-//   K5b msm_reduce_bits   the rest, bit-sliced: log2(m)+1 independent masked sums per window.
+//   K5a msm_reduce_level  sum_k k*B_k per window, level 0: chunked running sums over L0 buckets per lane (any integer,
+//                         chosen to fill whole rounds of the chip; parallel form of mod.rs:478-484).
+//   K5b msm_reduce_bits   the rest, bit-sliced: log2(m)+1 independent masked sums per window -- over all m pairs (few
+//                         pairs), or over their row and column sums (msm_reduce_rowcol + msm_reduce_bits2).
 //   host                  one Horner over the bit positions of all bit sums and window sums: <= 256 serial doublings -- a
 //                         chain with no parallelism, run on the host in the same templated formulas (~0.2 ms).
 #pragma once
@@ -1149,31 +1150,62 @@ __global__ void __launch_bounds__(64) msm_apply_heavy_kernel(const u32* __restri
 // Per window the buckets X[0..mwin) carry weights 1..mwin.  A slot folds the chunk of L consecutive buckets
 // [tL, (t+1)L) with a running sum:  S_t = sum_r X[tL+r],  A_t = sum_r (r+1) X[tL+r], so that
 //   sum_k k B_k = sum_t A_t + L * sum_t t S_t          (parallel form of mod.rs:478-484)
+// L is any integer >= 1: the last chunk of a window is ragged.  A window has its own bucket count -- a narrow window
+// (c - 1 bits: the top `narrow` ones) fills only the lower half of its mwin cells -- and lanes are numbered over the
+// chunks that hold buckets, window after window, so no wave walks an empty upper half.
+struct MsmLevelGeom {
+  u32 L;        // buckets per chunk
+  u32 mwin;     // cells per window in the bucket array
+  u32 m;        // chunks per full window = row stride of the (S, A) outputs
+  u32 mn;       // chunks of a narrow window (<= m)
+  u32 nfull;    // the first nfull windows of this launch are full, the rest narrow
+  u32 total;    // chunks of this launch: nfull * m + (windows - nfull) * mn
+};
+// chunk t of a launch -> its window, its index in the window and its length
+ARK_DEV void msm_level_chunk(const MsmLevelGeom& g, u32 t, u32& w, u32& tt, u32& len) {
+  const u32 nf = g.nfull * g.m;
+  u32 nbw;
+  if (t < nf) {
+    w = t / g.m;
+    tt = t - w * g.m;
+    nbw = g.mwin;
+  } else {
+    const u32 u = t - nf, wn = u / g.mn;
+    w = g.nfull + wn;
+    tt = u - wn * g.mn;
+    nbw = g.mwin >> 1;
+  }
+  const u32 first = tt * g.L;
+  len = nbw - first < g.L ? nbw - first : g.L;
+}
 // (two waves per SIMD for the one-lane-per-point curves; the lane-pair G2 form keeps two accumulators of 112 limbs and an
 // addition's temporaries per lane: one wave per SIMD, its overflow in AGPRs instead of scratch memory)
 template <class C>
-__global__ void __launch_bounds__(128, (C::LAZY_A && C::FA::LANES == 2) ? 1 : 2) msm_reduce_level_kernel(const char* __restrict__ in, u32 L, u32 total_out,
+__global__ void __launch_bounds__(128, (C::LAZY_A && C::FA::LANES == 2) ? 1 : 2) msm_reduce_level_kernel(const char* __restrict__ in, MsmLevelGeom g,
                                                                char* __restrict__ outS, char* __restrict__ outA) {
   typedef AccOps<C> Ops;
   typedef typename Ops::Pt Pt;
   const u32 t = (blockIdx.x * blockDim.x + threadIdx.x) / Ops::LANES;
-  if (t >= total_out) return;
-  const size_t base = (size_t)t * L;
+  if (t >= g.total) return;
+  u32 w, tt, len;
+  msm_level_chunk(g, t, w, tt, len);
+  const size_t base = (size_t)w * g.mwin + (size_t)tt * g.L;
+  const size_t o = (size_t)w * g.m + tt;
   // the weighted sum A lives in LDS between its updates (one 4-coordinate slot per lane, or per lane pair over Fp2): two
   // accumulators + the loaded bucket + an addition's temporaries do not fit 256 registers (they spilled 16 B to scratch)
   __shared__ uint4 park_lds[(128 / Ops::LANES) * Ops::ACC_BYTES / 16];
   char* slot = (char*)park_lds + (size_t)(threadIdx.x / Ops::LANES) * Ops::ACC_BYTES;
   typename Ops::Acc running = Ops::zero();
   Ops::park(running, slot);
-  for (u32 r = L; r-- > 0;) {
+  for (u32 r = len; r-- > 0;) {
     Pt x = Pt::load(in + (base + r) * Pt::BYTES);
     Ops::add(running, x);
     typename Ops::Acc acc = Ops::unpark(slot);
     Ops::add_acc(acc, running);
     Ops::park(acc, slot);
   }
-  Ops::fin(running).store(outS + (size_t)t * Pt::BYTES);
-  Ops::fin(Ops::unpark(slot)).store(outA + (size_t)t * Pt::BYTES);
+  Ops::fin(running).store(outS + o * Pt::BYTES);
+  Ops::fin(Ops::unpark(slot)).store(outA + o * Pt::BYTES);
 }
 
 // K5a with the two chains of a chunk on two WAVES (round 5).  In the kernel above a lane alternates between the running
@@ -1183,7 +1215,7 @@ __global__ void __launch_bounds__(128, (C::LAZY_A && C::FA::LANES == 2) ? 1 : 2)
 // additions, twice the lanes.  Used where the doubled lane count still fits the chip's resident lanes (msm_enqueue).
 template <class C>
 __global__ void __launch_bounds__(128, (C::LAZY_A && C::FA::LANES == 2) ? 1 : 2) msm_reduce_level_split_kernel(
-    const char* __restrict__ in, u32 L, u32 total_out, char* __restrict__ outS, char* __restrict__ outA) {
+    const char* __restrict__ in, MsmLevelGeom g, char* __restrict__ outS, char* __restrict__ outA) {
   typedef AccOps<C> Ops;
   typedef typename Ops::Pt Pt;
   constexpr u32 PTS = 64 / Ops::LANES;   // chunks per workgroup
@@ -1191,24 +1223,26 @@ __global__ void __launch_bounds__(128, (C::LAZY_A && C::FA::LANES == 2) ? 1 : 2)
   const u32 role = threadIdx.x >> 6;     // 0: running sum, 1: weighted sum
   const u32 pslot = (threadIdx.x & 63u) / Ops::LANES;
   const u32 t = blockIdx.x * PTS + pslot;
-  const bool live = t < total_out;
-  const size_t base = (size_t)t * L;
+  const bool live = t < g.total;
+  u32 w = 0, tt = 0, len = 0;
+  if (live) msm_level_chunk(g, t, w, tt, len);
+  const size_t base = (size_t)w * g.mwin + (size_t)tt * g.L;
   char* slot0 = (char*)hand_lds + (size_t)pslot * Ops::ACC_BYTES;
   char* slot1 = slot0 + (size_t)PTS * Ops::ACC_BYTES;
   typename Ops::Acc a = Ops::zero();
-  for (u32 step = 0; step <= L; step++) {
+  for (u32 step = 0; step <= g.L; step++) {   // (len <= L: a ragged chunk idles through its last steps, the barriers stay uniform)
     if (role == 0) {
-      if (step < L && live) {
-        Pt x = Pt::load(in + (base + (L - 1 - step)) * Pt::BYTES);
+      if (step < len) {
+        Pt x = Pt::load(in + (base + (len - 1 - step)) * Pt::BYTES);
         Ops::add(a, x);
         Ops::park(a, (step & 1u) ? slot1 : slot0);
       }
-    } else if (step > 0 && live) {
+    } else if (step > 0 && step <= len) {
       Ops::add_acc(a, Ops::unpark(((step - 1) & 1u) ? slot1 : slot0));
     }
     __syncthreads();   // the running sum of this step is visible; the slot read in this step may be overwritten in the next
   }
-  if (live) Ops::fin(a).store((role == 0 ? outS : outA) + (size_t)t * Pt::BYTES);
+  if (live) Ops::fin(a).store((role == 0 ? outS : outA) + ((size_t)w * g.m + tt) * Pt::BYTES);
 }
 
 // ---- K5b: the rest of the reduction, bit-sliced -------------------------------------------------------
@@ -1218,27 +1252,108 @@ __global__ void __launch_bounds__(128, (C::LAZY_A && C::FA::LANES == 2) ? 1 : 2)
 // masked plain sums plus the plain sum of the A_j -- all independent, each a strided partial sum + LDS tree.
 // grid = (chunks, log2(m) + 1, W): quantity q < nbits -> U_q, q == nbits -> sum A.  The host finishes with
 // a Horner over the bits (a few dozen point operations per window, same templated formulas).
+// (m is the row stride of S and A; window w of the launch holds m pairs if w < nfull, mn otherwise -- a narrow window)
 template <class C>
 __global__ void __launch_bounds__(256) msm_reduce_bits_kernel(const char* __restrict__ S, const char* __restrict__ A,
-                                                              u32 m, int nbits, u32 chunk, char* __restrict__ partial) {
+                                                              u32 m, u32 mn, u32 nfull, int nbits, u32 chunk,
+                                                              char* __restrict__ partial) {
   typedef AccOps<C> Ops;
   typedef typename Ops::Pt Pt;
   extern __shared__ uint4 reduce_lds[];
   char* sh = (char*)reduce_lds;
   const u32 q = blockIdx.y, w = blockIdx.z, ch = blockIdx.x;
   const u32 slot = threadIdx.x / Ops::LANES, nslots = blockDim.x / Ops::LANES;
+  const u32 mw = w < nfull ? m : mn;
   const bool plain = (int)q == nbits;
   const char* src = plain ? A : S;
   typename Ops::Acc acc = Ops::zero();
   for (u32 e = slot; e < chunk; e += nslots) {
     u32 j = ch * chunk + e;
-    if (j < m && (plain || ((j >> q) & 1u))) {
+    if (j < mw && (plain || ((j >> q) & 1u))) {
       Pt x = Pt::load(src + ((size_t)w * m + j) * Pt::BYTES);
       Ops::add(acc, x);
     }
   }
   Ops::tree(acc, sh, slot, nslots);
   if (slot == 0) Ops::fin(acc).store(partial + (((size_t)w * gridDim.y + q) * gridDim.x + ch) * Pt::BYTES);
+}
+
+// ---- K5b in two digits (the larger sizes) ----------------------------------------------------------------
+// The kernel above reads every S_j once per bit and adds it to half of them: (nbits / 2 + 1) m additions per window.  With
+// j = D h + l, D = 2^d, 0 <= l < D:
+//   sum_j j S_j = D sum_h h R_h + sum_l l C_l,    R_h = sum_l S_(D h + l) (row sums),  C_l = sum_h S_(D h + l) (column sums)
+// and bit b of j is bit b of l for b < d, bit b - d of h above: U_b is the masked sum of the C_l for b < d and of the R_h
+// for b >= d -- ~sqrt(m) elements each instead of m.  msm_reduce_rowcol_kernel adds every S_j twice (one row, one column)
+// and every A_j once (row sums of A); msm_reduce_bits2_kernel is the bit-sliced kernel on those short vectors.  The host
+// sees the same [w][q] part sums.  m need not be a power of two or a multiple of D: absent entries count as the identity.
+//
+// Per window the sums are laid out  R_0 .. R_(rows-1) | RA_0 .. RA_(rows-1) | C_0 .. C_(D-1),  rows = ceil(m / D).
+// `lps` lanes (a power of two, at most the slots of a wave) share one sum: each walks every lps-th element, then an LDS tree
+// over the lps partials; a wave holds 64 / LANES / lps sums.  grid = (ceil(sums / sums per wave), windows).
+template <class C>
+__global__ void __launch_bounds__(64) msm_reduce_rowcol_kernel(const char* __restrict__ S, const char* __restrict__ A, u32 m,
+                                                               u32 mn, u32 nfull, u32 d, u32 rows, u32 lps,
+                                                               char* __restrict__ out) {
+  typedef AccOps<C> Ops;
+  typedef typename Ops::Pt Pt;
+  constexpr u32 NS = 64 / Ops::LANES;
+  __shared__ uint4 rowcol_lds[NS * Ops::ACC_BYTES / 16];
+  const u32 w = blockIdx.y, slot = threadIdx.x / Ops::LANES;
+  const u32 mw = w < nfull ? m : mn;
+  const u32 D = 1u << d, nsum = 2 * rows + D;
+  const u32 grp = slot / lps, k0 = slot - grp * lps;
+  const u32 s = blockIdx.x * (NS / lps) + grp;
+  typename Ops::Acc acc = Ops::zero();
+  if (s < nsum) {
+    const char* src = S;
+    u32 first, step, len;
+    if (s < 2 * rows) {   // a row of S or of A: D consecutive pairs
+      const u32 h = s < rows ? s : s - rows;
+      if (s >= rows) src = A;
+      first = h * D;
+      step = 1;
+      len = first >= mw ? 0 : (mw - first < D ? mw - first : D);
+    } else {              // a column of S: every D-th pair
+      first = s - 2 * rows;
+      step = D;
+      len = first >= mw ? 0 : (mw - first + D - 1) >> d;
+    }
+    src += (size_t)w * m * Pt::BYTES;
+    for (u32 k = k0; k < len; k += lps) {
+      Pt x = Pt::load(src + (size_t)(first + k * step) * Pt::BYTES);
+      Ops::add(acc, x);
+    }
+  }
+  Ops::tree(acc, (char*)rowcol_lds + (size_t)grp * lps * Ops::ACC_BYTES, k0, lps);
+  if (s < nsum && k0 == 0) Ops::fin(acc).store(out + ((size_t)w * nsum + s) * Pt::BYTES);
+}
+// grid = (nbits + 1, windows): quantity q < d -> U_q from the column sums, d <= q < nbits -> U_q from the row sums,
+// q == nbits -> sum A from the row sums of A.  One workgroup per quantity: its slots stride over the vector, then an LDS tree.
+template <class C>
+__global__ void __launch_bounds__(256) msm_reduce_bits2_kernel(const char* __restrict__ rc, u32 d, u32 rows, int nbits,
+                                                               char* __restrict__ out) {
+  typedef AccOps<C> Ops;
+  typedef typename Ops::Pt Pt;
+  extern __shared__ uint4 reduce_lds[];
+  char* sh = (char*)reduce_lds;
+  const u32 q = blockIdx.x, w = blockIdx.y;
+  const u32 slot = threadIdx.x / Ops::LANES, nslots = blockDim.x / Ops::LANES;
+  const u32 D = 1u << d, nsum = 2 * rows + D;
+  const bool plain = (int)q == nbits;
+  const u32 first = plain ? rows : (q < d ? 2 * rows : 0);
+  const u32 len = q < d ? D : rows;
+  const u32 bit = q < d ? q : q - d;
+  const char* src = rc + ((size_t)w * nsum + first) * Pt::BYTES;
+  typename Ops::Acc acc = Ops::zero();
+  for (u32 e = slot; e < len; e += nslots)
+    if (plain || ((e >> bit) & 1u)) {
+      Pt x = Pt::load(src + (size_t)e * Pt::BYTES);
+      Ops::add(acc, x);
+    }
+  u32 width = 1;
+  while (width < len && width < nslots) width <<= 1;
+  Ops::tree(acc, sh, slot, width);
+  if (slot == 0) Ops::fin(acc).store(out + ((size_t)w * gridDim.x + q) * Pt::BYTES);
 }
 
 // sums the `nchunks` chunk partials of every (window, quantity) pair: one wave per pair, its slots stride over the
@@ -1551,7 +1666,8 @@ struct MsmJob {
   bool empty = false;     // n == 0: identity, nothing enqueued
   bool no_result = false; // a non-final piece of a streamed MSM (MsmPiece): only the scalar-range flag comes back
   MsmPlan pl{};
-  int nbits = 0, log2L0 = 0;
+  int nbits = 0;
+  u32 L0 = 1;                     // level-0 chunk length: T_w = A_w + L0 V_w
   u32 Q = 0;
   size_t npairs = 0;
   const char* d_sums = nullptr;   // the job's part sums in device memory (npairs XYZZ points): read by the sharded combine
@@ -1768,6 +1884,9 @@ int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const Ms
   const int accum = (piece && !piece->first) ? 1 : 0;
 
   // bucket reduction geometry: level 0 (chunked running sums over L0 buckets per lane), then the bit-sliced sums
+  // a window's own bucket count: the narrow windows (the top pl.narrow ones of a plain job) fill the lower half of their cells
+  const u32 red_narrow = (!pl.shared && mwin >= 2) ? (u32)pl.narrow : 0u;
+  const u32 red_full = (u32)Wr - red_narrow;
   u32 L0 = 32;
   {
     size_t want = (mwin * (size_t)Wr) >> 17;  // keep ~1e5 (S, A) pairs for the bit-sliced stage
@@ -1799,18 +1918,52 @@ int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const Ms
       while (g < cap && (size_t)g * 32768 < nbr) g <<= 1;
       L0 = g;
     }
-    if (const char* e0 = getenv("ARK_HIP_MSM_L0")) {  // tuning knob
-      int v = atoi(e0);
-      if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) L0 = (u32)v;
+    // Large plain jobs on the one-lane-per-point curves (the rules above say 32): the chunks that hold buckets are a
+    // non-integer number of rounds of the chip's resident lanes (2^24, c = 20: 172 032 chunks on 131 072 lanes = 1.31 rounds of a
+    // 64-addition chain, the second at a third of the occupancy).  Keep the number of rounds and shorten the chain until they are
+    // full: the smallest L0 whose chunks still fit k rounds (2^24: k = 2, L0 = 22).  ARK_HIP_MSM_L0_FILL=0: the power of two.
+    static const bool fill_env = [] { const char* e = getenv("ARK_HIP_MSM_L0_FILL"); return !(e && e[0] == '0'); }();
+    if (fill_env && Wr > 1 && C::FA::LANES == 1 && L0 == 32 && nbr > ((size_t)1 << 21)) {
+      static const size_t resident = [] {   // chunks the level-0 kernel keeps resident, from the occupancy it was built with
+        int dev = 0, cus = 0, blocks = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_reduce_level_kernel<C>, 128, 0) != hipSuccess) {
+          (void)hipGetLastError();
+          return (size_t)0;
+        }
+        return (size_t)blocks * (size_t)cus * 128;
+      }();
+      auto chunks = [&](u32 L) { return red_full * ((mwin + L - 1) / L) + red_narrow * ((mwin / 2 + L - 1) / L); };
+      if (resident) {
+        const size_t rounds = (chunks(32) + resident - 1) / resident;
+        while (L0 > 8 && chunks(L0 - 1) <= rounds * resident) L0--;
+      }
     }
-    while (L0 > mwin) L0 >>= 1;
+    if (const char* e0 = getenv("ARK_HIP_MSM_L0")) {  // tuning knob: any chunk length 1 .. 128
+      int v = atoi(e0);
+      if (v >= 1 && v <= 128) L0 = (u32)v;
+    }
+    if (L0 > mwin) L0 = (u32)mwin;
   }
-  const size_t m = mwin / L0;  // pairs per window after level 0
-  int log2L0 = 0;
-  while ((1u << log2L0) < L0) log2L0++;
+  const size_t m = (mwin + L0 - 1) / L0;         // pairs per full window after level 0 (the last chunk may be ragged)
+  const size_t mn = red_narrow ? (mwin / 2 + L0 - 1) / L0 : m;   // ... per narrow window
   int nbits = 0;
   while (((size_t)1 << nbits) < m) nbits++;
   const u32 Q = (u32)nbits + 1;
+  // second stage: the two-digit form (row and column sums, then the bit-sliced sums of those) from 2048 pairs per window
+  // (a lane pair per point: 1024), the one-kernel form below that (ARK_HIP_MSM_STAGE2=0 / 1 forces one).  Measured
+  // (profiles/reduce_geometry_free_l0.txt, reduction in ms, one-kernel form at its best chunk -> two digits): BLS12-381 G1
+  // m = 512 (2^16) 0.27 -> 0.34, m = 2048 (2^18) 0.53 -> 0.50, m = 4096 (2^20 / 2^22) 0.75 -> 0.62 / 1.08 -> 0.85, m = 16 384
+  // (2^24, L0 = 32) 3.58 -> 3.06; BN254 m = 512 0.16 -> 0.20, m = 4096 0.32 -> 0.29; BLS12-377 G2 m = 1024 (2^18) 1.25 -> 1.08,
+  // m = 2048 (2^20) 1.57 -> 1.20, m = 4096 (2^22) 4.39 -> 3.35
+  bool two_digit = m >= (C::FA::LANES == 2 ? 1024u : 2048u);
+  if (const char* e2 = getenv("ARK_HIP_MSM_STAGE2")) {
+    if (e2[0] == '0') two_digit = false;
+    if (e2[0] == '1') two_digit = true;
+  }
+  const u32 d2 = (u32)nbits / 2;                                   // low digit: D = 2^d2 columns
+  const u32 rows2 = (u32)((m + ((size_t)1 << d2) - 1) >> d2);      // high digit: rows of D pairs
+  const size_t nsum2 = 2 * (size_t)rows2 + ((size_t)1 << d2);      // R, RA, C of one window
   // chunk of the bit-sliced stage: a workgroup's 256 lanes stride over it (chunk/256 serial additions each) before the
   // 8-step LDS tree -- both pure latency, so chunks are kept short once there are enough of them to fill the chip
   // (few workgroups, e.g. one window of a prepared set at small n: latency only, 2^16 1.39 -> 1.11 ms; many: throughput)
@@ -1820,13 +1973,14 @@ int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const Ms
     int v = atoi(ec);
     if (v == 256 || v == 512 || v == 1024 || v == 2048 || v == 4096 || v == 8192 || v == 16384) chunk = (u32)v;
   }
-  if (chunk > m) chunk = (u32)m;
+  if (chunk > m || two_digit) chunk = (u32)m;    // (the two-digit form writes the part sums themselves: no chunk partials)
   const u32 nchunks = (u32)((m + chunk - 1) / chunk);
   const size_t npart = (size_t)Wr * Q * nchunks;
   const size_t npairs = (size_t)Wr * Q;
   if (ws.lvlS[0].ensure(m * Wr * Pt::BYTES) || ws.lvlA[0].ensure(m * Wr * Pt::BYTES)) return -3;
   if (ws.lvlS[1].ensure(npart * Pt::BYTES)) return -3;
   if (nchunks > 1 && ws.lvlA[1].ensure(npairs * Pt::BYTES)) return -3;
+  if (two_digit && ws.lvlA[1].ensure((size_t)Wr * nsum2 * Pt::BYTES)) return -3;
   {
     int rc = msm_job_pinned(job, npairs * Pt::BYTES + 64);
     if (rc) return rc;
@@ -2139,21 +2293,37 @@ int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const Ms
     // (split lanes <= 131 072: one round of the chip); 2^23 2.31 -> 2.00 (L0 = 32: 33 steps instead of 64 outweigh the 1.75
     // rounds of 229 376 lanes); 2^21 / 2^22 (L0 = 8, 245 760 lanes) 1.15 -> 1.21 / equal; 2^24, 2^26 equal; the lane-pair
     // curves (G2) lose 2-3 % everywhere: off there
-    const size_t split_lanes = m * wg * 2;
+    const u32 nfull_g = w0 >= red_full ? 0u : (u32)std::min<size_t>(wg, red_full - w0);   // full windows among [w0, w0 + wg)
+    const MsmLevelGeom geom{L0, (u32)mwin, (u32)m, (u32)mn, nfull_g, (u32)(nfull_g * m + (wg - nfull_g) * mn)};
+    const size_t split_lanes = m * wg * 2;   // (the rule was fitted on the windows' nominal lanes)
     const bool split_level = split_env >= 0 ? split_env != 0
                                             : (LNr == 1 && L0 >= 2 && (split_lanes <= 131072 || (L0 >= 16 && split_lanes <= 262144)));
     if (split_level)
-      hipLaunchKernelGGL((msm_reduce_level_split_kernel<C>), dim3((u32)((m * wg * LNr + 63) / 64)), dim3(128), 0, st,
-                         (const char*)d_buckets + w0 * mwin * Pt::BYTES, L0, (u32)(m * wg), (char*)ws.lvlS[0].p + bo,
+      hipLaunchKernelGGL((msm_reduce_level_split_kernel<C>), dim3((u32)(((size_t)geom.total * LNr + 63) / 64)), dim3(128), 0, st,
+                         (const char*)d_buckets + w0 * mwin * Pt::BYTES, geom, (char*)ws.lvlS[0].p + bo,
                          (char*)ws.lvlA[0].p + bo);
     else
-    hipLaunchKernelGGL((msm_reduce_level_kernel<C>), dim3((u32)((m * wg * LNr + 127) / 128)), dim3(128), 0, st,
-                       (const char*)d_buckets + w0 * mwin * Pt::BYTES, L0, (u32)(m * wg), (char*)ws.lvlS[0].p + bo,
+    hipLaunchKernelGGL((msm_reduce_level_kernel<C>), dim3((u32)(((size_t)geom.total * LNr + 127) / 128)), dim3(128), 0, st,
+                       (const char*)d_buckets + w0 * mwin * Pt::BYTES, geom, (char*)ws.lvlS[0].p + bo,
                        (char*)ws.lvlA[0].p + bo);
     constexpr size_t ACCBr = AccOps<C>::ACC_BYTES;
     const u32 rthreads = ACCBr * (256 / LNr) > 49152 ? 128 : 256;  // LDS tree within 48 KiB
+    if (two_digit) {
+      // lanes per row / column sum: the longest is walked in <= 8 steps by each (12 dependent additions with the tree at
+      // 128-element rows), which at 2^24 pairs is 1.2 waves per SIMD
+      constexpr u32 NSr = 64 / LNr;
+      const u32 longest = std::max<u32>(rows2, 1u << d2);
+      u32 lps = 1;
+      while (lps < NSr && lps * 8 < longest) lps <<= 1;
+      char* const rc = (char*)ws.lvlA[1].p + w0 * nsum2 * Pt::BYTES;
+      hipLaunchKernelGGL((msm_reduce_rowcol_kernel<C>), dim3((u32)((nsum2 + NSr / lps - 1) / (NSr / lps)), (u32)wg), dim3(64), 0, st,
+                         (const char*)ws.lvlS[0].p + bo, (const char*)ws.lvlA[0].p + bo, (u32)m, (u32)mn, nfull_g, d2, rows2, lps, rc);
+      hipLaunchKernelGGL((msm_reduce_bits2_kernel<C>), dim3(Q, (u32)wg), dim3(rthreads), (rthreads / LNr) * ACCBr, st,
+                         (const char*)rc, d2, rows2, nbits, (char*)ws.lvlS[1].p + po);
+      return;
+    }
     hipLaunchKernelGGL((msm_reduce_bits_kernel<C>), dim3(nchunks, Q, (u32)wg), dim3(rthreads), (rthreads / LNr) * ACCBr, st,
-                       (const char*)ws.lvlS[0].p + bo, (const char*)ws.lvlA[0].p + bo, (u32)m, nbits, chunk,
+                       (const char*)ws.lvlS[0].p + bo, (const char*)ws.lvlA[0].p + bo, (u32)m, (u32)mn, nfull_g, nbits, chunk,
                        (char*)ws.lvlS[1].p + po);
     if (two_level)
       hipLaunchKernelGGL((msm_sum_chunks_kernel<C>), dim3((u32)(wg * Q)), dim3(64), (64 / LNr) * AccOps<C>::ACC_BYTES, st,
@@ -2210,7 +2380,7 @@ int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const Ms
   ARK_HIP_TRY(hipEventRecord(job.done, stream));
   job.pl = pl;
   job.nbits = nbits;
-  job.log2L0 = log2L0;
+  job.L0 = L0;
   job.short_job = (double)n * (double)W <= 6.0e6;   // (up to ~2^18 full-width pairs)
   job.Q = Q;
   job.npairs = npairs;
@@ -2248,9 +2418,21 @@ static inline hipError_t msm_wait_event(hipEvent_t ev) {
 // off_w + log2 L0 + b, so the chain doubles once per scalar bit (<= 256 doublings) instead of once per bit inside every
 // window and again between windows (~2 c W).  parts: [w][q] XYZZ points, q < nbits: U_(w,q), q == nbits: A_w, row
 // stride Q; off: Wr + 1 bit offsets.  A prepared base set has a single T (Wr = 1).
-// window w's own sum  T_w = A_w + 2^log2L0 sum_b 2^b U_(w,b)
+// h <- k h for a small constant k >= 1, double-and-add from k's top bit (k = 2^e: e doublings)
+template <class F>
+XYZZ<F> msm_host_mul_small(const XYZZ<F>& h, u32 k) {
+  int top = 31;
+  while (!((k >> top) & 1u)) top--;
+  XYZZ<F> r = h;
+  for (int b = top - 1; b >= 0; b--) {
+    r = xyzz_dbl<F>(r);
+    if ((k >> b) & 1u) xyzz_add<F>(r, h);
+  }
+  return r;
+}
+// window w's own sum  T_w = A_w + L0 sum_b 2^b U_(w,b)
 template <class C>
-XYZZ<typename C::F> msm_host_window_sum(const char* parts, u32 Q, int nbits, int log2L0, int w) {
+XYZZ<typename C::F> msm_host_window_sum(const char* parts, u32 Q, int nbits, u32 L0, int w) {
   typedef typename C::F F;
   typedef XYZZ<F> Pt;
   auto part_at = [&](u32 q) { return Pt::load(parts + ((size_t)w * Q + q) * Pt::BYTES); };
@@ -2260,7 +2442,7 @@ XYZZ<typename C::F> msm_host_window_sum(const char* parts, u32 Q, int nbits, int
     Pt ub = part_at((u32)b);
     xyzz_add<F>(h, ub);
   }
-  for (int i = 0; i < log2L0; i++) h = xyzz_dbl<F>(h);
+  h = msm_host_mul_small<F>(h, L0);
   Pt asum = part_at((u32)nbits);
   xyzz_add<F>(h, asum);
   return h;
@@ -2270,11 +2452,12 @@ template <class C>
 struct MsmWindowSums {
   const char* parts;
   u32 Q;
-  int nbits, log2L0;
+  int nbits;
+  u32 L0;
   XYZZ<typename C::F>* T;
   static void task(void* ctx, int w) {
     const MsmWindowSums& s = *(const MsmWindowSums*)ctx;
-    s.T[(size_t)w] = msm_host_window_sum<C>(s.parts, s.Q, s.nbits, s.log2L0, w);
+    s.T[(size_t)w] = msm_host_window_sum<C>(s.parts, s.Q, s.nbits, s.L0, w);
   }
 };
 // total = sum_w 2^(off_w) T_w: the doublings between the windows, the only serial part of the tail
@@ -2289,7 +2472,7 @@ XYZZ<typename C::F> msm_host_combine_windows(const XYZZ<typename C::F>* T, int W
   return total;
 }
 template <class C>
-XYZZ<typename C::F> msm_host_fold(const char* parts, u32 Q, int Wr, int nbits, int log2L0, const int* off) {
+XYZZ<typename C::F> msm_host_fold(const char* parts, u32 Q, int Wr, int nbits, u32 L0, const int* off) {
   typedef typename C::F F;
   typedef XYZZ<F> Pt;
   auto part_at = [&](int w, u32 q) { return Pt::load(parts + ((size_t)w * Q + q) * Pt::BYTES); };
@@ -2300,10 +2483,19 @@ XYZZ<typename C::F> msm_host_fold(const char* parts, u32 Q, int Wr, int nbits, i
   // whole tail is ~0.25 ms); msm_finish splits it for short jobs.
   if (C::FA::LANES == 2 && Wr >= 4 && HostPool::instance().helpers() > 0) {
     std::vector<Pt> T((size_t)Wr);
-    MsmWindowSums<C> ws{parts, Q, nbits, log2L0, T.data()};
+    MsmWindowSums<C> ws{parts, Q, nbits, L0, T.data()};
     HostPool::instance().run_all(&MsmWindowSums<C>::task, &ws, Wr);   // the pool's helpers + this thread; no thread is created here
     return msm_host_combine_windows<C>(T.data(), Wr, off);
   }
+  if (L0 & (L0 - 1)) {
+    // L0 is not a power of two: L0 V_w has no bit position of its own in the merged Horner below.  Every window's own sum first
+    // (its V_w times the small constant L0: <= 6 doublings + <= 6 additions each), then the doublings between the windows.
+    std::vector<Pt> T((size_t)Wr);
+    for (int w = 0; w < Wr; w++) T[(size_t)w] = msm_host_window_sum<C>(parts, Q, nbits, L0, w);
+    return msm_host_combine_windows<C>(T.data(), Wr, off);
+  }
+  int log2L0 = 0;
+  while ((1u << log2L0) < L0) log2L0++;
   int top = 0;
   for (int w = 0; w < Wr; w++) top = std::max(top, off[w] + log2L0 + nbits - 1);
   Pt total = Pt::zero();
@@ -2359,7 +2551,7 @@ int msm_finish(MsmWorkspace& ws, int slot, uint64_t* out_xyz, MsmTimings* tm) {
   // cost nothing but their share.  A job whose GPU work has already finished keeps the single Horner.
   // ARK_HIP_HOST_TAIL_THREADS=0: no pool.
   std::vector<Pt> early_T;
-  MsmWindowSums<C> early_ws{(const char*)job.pinned, Q, nbits, job.log2L0, nullptr};
+  MsmWindowSums<C> early_ws{(const char*)job.pinned, Q, nbits, job.L0, nullptr};
   HostPool::Handle early;
   struct EarlyGuard {   // an error return between here and the fold must not leave the batch open
     HostPool::Handle& h;
@@ -2402,7 +2594,7 @@ int msm_finish(MsmWorkspace& ws, int slot, uint64_t* out_xyz, MsmTimings* tm) {
       early.reset();
       total = msm_host_combine_windows<C>(early_T.data(), Wr, off.data());
     } else {
-      total = msm_host_fold<C>((const char*)job.pinned, Q, Wr, nbits, job.log2L0, off.data());
+      total = msm_host_fold<C>((const char*)job.pinned, Q, Wr, nbits, job.L0, off.data());
     }
     xyzz_to_jac<F>(total).store(out_xyz);
   }
@@ -2429,7 +2621,8 @@ int msm_finish(MsmWorkspace& ws, int slot, uint64_t* out_xyz, MsmTimings* tm) {
 // kernel adds the G copies of every part, and the single host tail runs on the sums of the whole job
 // (variable_base/mod.rs:542-557: the chunk sum, moved in front of the window combine -- elliptic-curve addition commutes).
 struct MsmSumsHeader {   // 64 bytes in front of a rank's part sums; all ranks must agree on every field but `err`
-  int c, W, narrow, shared, nbits, log2L0;
+  int c, W, narrow, shared, nbits;
+  u32 L0;                // level-0 chunk length (any integer >= 1)
   u32 Q, npairs;
   u32 err;               // this rank's scalar-range flag (msm_digits_kernel)
   u32 pad[7];
@@ -2475,7 +2668,7 @@ int msm_fold_sums(const MsmSumsHeader& h, const void* h_sums, uint64_t* out_xyz)
   std::vector<int> off((size_t)Wr + 1);
   off[0] = 0;
   for (int w = 0; w < Wr; w++) off[w + 1] = off[w] + msm_window_width(w, h.c, h.W, h.narrow);
-  const XYZZ<F> total = msm_host_fold<C>((const char*)h_sums, h.Q, Wr, h.nbits, h.log2L0, off.data());
+  const XYZZ<F> total = msm_host_fold<C>((const char*)h_sums, h.Q, Wr, h.nbits, h.L0, off.data());
   xyzz_to_jac<F>(total).store(out_xyz);
   return 0;
 }
@@ -2491,7 +2684,7 @@ static inline int msm_job_sums(MsmWorkspace& ws, int slot, MsmSumsInfo* out) {
   out->h.narrow = job.pl.narrow;
   out->h.shared = job.pl.shared ? 1 : 0;
   out->h.nbits = job.nbits;
-  out->h.log2L0 = job.log2L0;
+  out->h.L0 = job.L0;
   out->h.Q = job.Q;
   out->h.npairs = (u32)job.npairs;
   out->d_sums = job.d_sums;

@@ -439,6 +439,10 @@ int ark_hip_test_msm_sharded_emulated(int curve, int world, const void* const* d
 int ark_hip_test_base_hash(const uint64_t* p, size_t words, uint64_t out[2]);
 int ark_hip_test_msm_host_fold(int curve, const uint64_t* parts, int windows, int nbits, int log2_l0, const int* widths,
                                uint64_t* out_xyz);
+/* The same tail with the level-0 chunk length l0 itself (1 .. 65536, any integer):
+ * out = sum_w 2^(off_w) (A_w + l0 sum_b 2^b U_(w,b)). */
+int ark_hip_test_msm_host_fold_l0(int curve, const uint64_t* parts, int windows, int nbits, int l0, const int* widths,
+                                  uint64_t* out_xyz);
 /* The carry-free limb arithmetic (csrc/fp28.cuh, fp28x2.cuh, fft.cuh Fft29) ONE OP AT A TIME ON RAW LIMBS: lane t reads `arity`
  * slots of L words (u32[L]: the W-bit limbs as the test chose them, not canonical words) at in[(t * arity + j) * L] and writes
  * L + 1 words at out[t * (L + 1)] (word L: the op's boolean result).  The Fp2L ops (op >= 40; field = BLS12-381 / BLS12-377 Fq)
