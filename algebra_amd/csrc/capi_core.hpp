@@ -223,6 +223,7 @@ struct Context {
   FftWorkspace fft;
   DevBuf stage_a, stage_b, stage_c;    // host-pointer entry points: device copies
   DevBuf gfft_work, gfft_scal;         // transform over group elements: XYZZ scratch, per-position scalars
+  DevBuf poly_work;                    // polynomial ops: result slot, tile values / carries of every scan level, partial sums
   DevBuf ring_s[2], ring_b[2];         // double-buffered scalar / base uploads of the streaming entry points
   hipEvent_t ring_free[2] = {nullptr, nullptr}, ring_up[2] = {nullptr, nullptr};
   int ring_next = 0;
@@ -460,6 +461,33 @@ inline size_t gfft_work_bytes_any(int curve, int k) {
 }
 inline int fr_div_dispatch(int field, const void* num, const void* den, void* r, size_t n, hipStream_t st) {
 #define X(NAME) fr_div_##NAME(num, den, r, n, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int poly_tile_value_dispatch(int field, const void* src, size_t n, const PolyPowers& pw, void* vals, hipStream_t st) {
+#define X(NAME) poly_tile_value_##NAME(src, n, pw, vals, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int poly_tile_divide_dispatch(int field, const void* src, size_t n, const PolyPowers& pw, const void* carries, void* dst,
+                                     void* rem, hipStream_t st) {
+#define X(NAME) poly_tile_divide_##NAME(src, n, pw, carries, dst, rem, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int poly_vanishing_dispatch(int field, const void* p, size_t n, size_t m, void* q, void* r, hipStream_t st) {
+#define X(NAME) poly_vanishing_##NAME(p, n, m, q, r, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int poly_lagrange_dispatch(int field, const uint64_t* a4, const uint64_t* c4, const uint64_t* w4, const uint64_t* wstep4,
+                                  int onehot, void* out, size_t n, size_t lanes, hipStream_t st) {
+#define X(NAME) poly_lagrange_##NAME(a4, c4, w4, wstep4, onehot, out, n, lanes, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int fr_inner_product_dispatch(int field, const void* a, const void* b, size_t n, void* partials, void* out, hipStream_t st) {
+#define X(NAME) fr_inner_product_##NAME(a, b, n, partials, out, st)
   ARK_FIELD_SWITCH(field, X);
 #undef X
 }

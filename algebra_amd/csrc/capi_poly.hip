@@ -1,0 +1,222 @@
+// C ABI of libark_hip.so: polynomial operations on device-resident vectors -- evaluation at a point, division by x - z and
+// by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products (see
+// include/ark_hip.h; kernels: polyops.cuh).
+#include "capi_core.hpp"
+#include "capi_hostmath.hpp"
+#include "polyops.cuh"
+using namespace arkhip;
+using namespace arkhip::capi;
+
+namespace {
+
+constexpr int POLY_MAX_LEVELS = 8;   // 2048^6 > 2^64
+
+inline bool field_served(int field) {
+  return field == ARK_HIP_BN254_FR || field == ARK_HIP_BLS12_381_FR || field == ARK_HIP_BLS12_377_FR;
+}
+template <class FP>
+FrConst to_const(const Fp<FP>& x) {
+  FrConst k;
+  for (int j = 0; j < 8; j++) k.l[j] = x.l[j];
+  return k;
+}
+// the powers every scan level needs, by repeated squaring on the host: level l works with z_l = z^(T^l)
+template <class FP>
+void poly_powers(const uint64_t* z4, int levels, PolyPowers* pw) {
+  typedef Fp<FP> F;
+  F z = F::load(z4);
+  for (int l = 0; l < levels; l++) {
+    pw[l].z = to_const(z);
+    F t = z;
+    int lg = 0;
+    for (int e = 1; e < POLY_TILE; e <<= 1, lg++) {   // t = z^e on entry
+      if (e >= POLY_E) pw[l].zs[lg - 3] = to_const(t);
+      t = F::sqr(t);
+    }
+    z = t;   // z^T
+  }
+}
+inline int poly_powers_any(int field, const uint64_t* z4, int levels, PolyPowers* pw) {
+#define X(NAME) (poly_powers<NAME>(z4, levels, pw), 0)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+
+// scratch of one call inside Context::poly_work: [result slot | tile values of level 1 | level 2 | ...]
+struct PolyLevels {
+  int levels = 1;
+  size_t len[POLY_MAX_LEVELS] = {};   // coefficients at level l
+  size_t off[POLY_MAX_LEVELS] = {};   // element offset of level l's vector in the scratch (l >= 1)
+  size_t total = 1;                   // elements of scratch
+};
+inline PolyLevels poly_levels(size_t n) {
+  PolyLevels L;
+  L.len[0] = n;
+  while (L.len[L.levels - 1] > (size_t)POLY_TILE) {
+    L.len[L.levels] = (L.len[L.levels - 1] + POLY_TILE - 1) / POLY_TILE;
+    L.off[L.levels] = L.total;
+    L.total += L.len[L.levels];
+    L.levels++;
+  }
+  return L;
+}
+// grows only with every stream idle: earlier asynchronous calls may still be using the buffer
+inline int poly_scratch(Context* c, size_t elems) {
+  if (c->poly_work.cap >= elems * 32) return 0;
+  if (int rc = sync_compute(c)) return rc;
+  return c->poly_work.ensure(elems * 32) ? ARK_HIP_ERR_NOMEM : 0;
+}
+inline int result_to_host(Context* c, uint64_t* out) {
+  ARK_HIP_TRY(hipMemcpyAsync(out, c->poly_work.p, 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+template <class FP>
+int lagrange_constants(const ark_hip_radix2_domain* dom, const uint64_t* tau4, size_t lanes, uint64_t a4[4], uint64_t c4[4],
+                       uint64_t w4[4], uint64_t wstep4[4], int* onehot) {
+  typedef Fp<FP> F;
+  const F tau = F::load(tau4), h = F::load(dom->offset);
+  uint64_t e[1] = {dom->size};
+  const F zh = F::sub(host_pow<FP>(tau, e, 1), F::load(dom->offset_pow_size));   // Z_H(tau) = tau^m - h^m
+  uint64_t le[1] = {(uint64_t)lanes};
+  if (zh.is_zero()) {   // tau = h g^i for one i: that coefficient is one, the others are zero (domain/mod.rs:175-189)
+    const F g = F::load(dom->group_gen);
+    h.store(a4);
+    tau.store(c4);
+    g.store(w4);
+    host_pow<FP>(g, le, 1).store(wstep4);
+    *onehot = 1;
+    return 0;
+  }
+  // 1 / L_i = l_i r_i with l_i = l_0 g^-i, l_0 = m h^(m-1) / Z_H(tau), r_i = tau - h g^i (:204-215)
+  //         = (l_0 tau) g^-i - l_0 h
+  uint64_t em[1] = {dom->size - 1};
+  const F l0 = F::mul(host_inverse(zh), F::mul(F::load(dom->size_as_field_element), host_pow<FP>(h, em, 1)));
+  const F gi = F::load(dom->group_gen_inv);
+  F::mul(l0, tau).store(a4);
+  F::mul(l0, h).store(c4);
+  gi.store(w4);
+  host_pow<FP>(gi, le, 1).store(wstep4);
+  *onehot = 0;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ark_hip_poly_scan_plan(size_t n, int* tile, int* levels) {
+  if (!tile || !levels) return ARK_HIP_ERR_ARG;
+  *tile = POLY_TILE;
+  *levels = poly_scan_levels(n);
+  return 0;
+}
+
+int ark_hip_poly_evaluate_device(int field, const void* d_coeffs, size_t n, const uint64_t* point, uint64_t* out) {
+  if (!field_served(field) || !point || !out || (n && !d_coeffs)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) {
+    memset(out, 0, 32);
+    return 0;
+  }
+  const PolyLevels L = poly_levels(n);
+  PolyPowers pw[POLY_MAX_LEVELS];
+  if (int rc = poly_powers_any(field, point, L.levels, pw)) return rc;
+  if (int rc = poly_scratch(c, L.total)) return rc;
+  char* w = (char*)c->poly_work.p;
+  const void* cur = d_coeffs;
+  for (int l = 0; l < L.levels; l++) {   // the last level has one tile: its value is p(z), written to the result slot
+    void* vals = l + 1 < L.levels ? w + L.off[l + 1] * 32 : w;
+    if (int rc = poly_tile_value_dispatch(field, cur, L.len[l], pw[l], vals, c->stream)) return rc;
+    cur = vals;
+  }
+  return result_to_host(c, out);
+}
+
+int ark_hip_poly_divide_linear_device(int field, const void* d_coeffs, size_t n, const uint64_t* z, void* d_quot, uint64_t* out_rem) {
+  if (!field_served(field) || !z || (n && !d_coeffs) || (n > 1 && !d_quot)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) {
+    if (out_rem) memset(out_rem, 0, 32);
+    return 0;
+  }
+  const PolyLevels L = poly_levels(n);
+  PolyPowers pw[POLY_MAX_LEVELS];
+  if (int rc = poly_powers_any(field, z, L.levels, pw)) return rc;
+  if (int rc = poly_scratch(c, L.total)) return rc;
+  char* w = (char*)c->poly_work.p;
+  auto vec = [&](int l) -> void* { return l == 0 ? const_cast<void*>(d_coeffs) : (void*)(w + L.off[l] * 32); };
+  // up: tile values of every level that has more than one tile
+  for (int l = 0; l + 1 < L.levels; l++)
+    if (int rc = poly_tile_value_dispatch(field, vec(l), L.len[l], pw[l], vec(l + 1), c->stream)) return rc;
+  // down: the top level is one tile with no carry; every level's quotient is the carries of the level below it, written
+  // over its own tile values (the last one stays: the last tile's carry is zero by definition)
+  for (int l = L.levels - 1; l >= 0; l--) {
+    const void* carries = l + 1 < L.levels ? vec(l + 1) : nullptr;
+    void* dst = l == 0 ? d_quot : vec(l);
+    void* rem = (l == 0 && out_rem) ? (void*)w : nullptr;
+    if (int rc = poly_tile_divide_dispatch(field, vec(l), L.len[l], pw[l], carries, dst, rem, c->stream)) return rc;
+  }
+  if (out_rem) return result_to_host(c, out_rem);
+  return mark_producer(c);
+}
+
+int ark_hip_poly_divide_by_vanishing_device(int field, size_t domain_size, const void* d_coeffs, size_t n, void* d_quot, void* d_rem) {
+  if (!field_served(field) || domain_size == 0 || (n && (!d_coeffs || !d_rem)) || (n > domain_size && !d_quot)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) return 0;
+  if (n < domain_size) {   // the quotient is zero and the whole polynomial is the remainder (dense.rs:171-173)
+    ARK_HIP_TRY(hipMemcpyAsync(d_rem, d_coeffs, n * 32, hipMemcpyDeviceToDevice, c->stream));
+    return mark_producer(c);
+  }
+  if (int rc = poly_vanishing_dispatch(field, d_coeffs, n, domain_size, d_quot, d_rem, c->stream)) return rc;
+  return mark_producer(c);
+}
+
+int ark_hip_domain_lagrange_coefficients_device(int field, const ark_hip_radix2_domain* dom, const uint64_t* tau, void* d_out) {
+  if (!field_served(field) || !dom || !tau || !d_out) return ARK_HIP_ERR_ARG;
+  if (dom->log_size_of_group > 63 || dom->size != ((uint64_t)1 << dom->log_size_of_group)) return ARK_HIP_ERR_ARG;
+  if (!domain_is_of_field(field, dom)) return ARK_HIP_ERR_ARG;
+  const size_t n = (size_t)dom->size;
+  const size_t lanes = poly_lagrange_lanes(n);   // the kernel's partition: the host supplies its step w^lanes
+  uint64_t a4[4], c4[4], w4[4], ws4[4];
+  int onehot = 0;
+  {
+    int rc = ARK_HIP_ERR_ARG;
+    switch (field) {
+#ifndef ARK_HIP_DEV
+      case ARK_HIP_BN254_FR: rc = lagrange_constants<BN254_FR>(dom, tau, lanes, a4, c4, w4, ws4, &onehot); break;
+      case ARK_HIP_BLS12_377_FR: rc = lagrange_constants<BLS12_377_FR>(dom, tau, lanes, a4, c4, w4, ws4, &onehot); break;
+#endif
+      case ARK_HIP_BLS12_381_FR: rc = lagrange_constants<BLS12_381_FR>(dom, tau, lanes, a4, c4, w4, ws4, &onehot); break;
+    }
+    if (rc) return rc;
+  }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (int rc = poly_lagrange_dispatch(field, a4, c4, w4, ws4, onehot, d_out, n, lanes, c->stream)) return rc;
+  // batch_inversion of the inverse coefficients (domain/mod.rs:219), lane-batched in place
+  if (!onehot)
+    if (int rc = fr_div_dispatch(field, nullptr, d_out, d_out, n, c->stream)) return rc;
+  return mark_producer(c);
+}
+
+int ark_hip_fr_inner_product_device(int field, const void* d_a, const void* d_b, size_t n, uint64_t* out) {
+  if (!field_served(field) || !out || (n && (!d_a || !d_b))) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) {
+    memset(out, 0, 32);
+    return 0;
+  }
+  if (int rc = poly_scratch(c, 1 + INNER_BLOCKS)) return rc;
+  char* w = (char*)c->poly_work.p;
+  if (int rc = fr_inner_product_dispatch(field, d_a, d_b, n, w + 32, w, c->stream)) return rc;
+  return result_to_host(c, out);
+}
+
+}  // extern "C"

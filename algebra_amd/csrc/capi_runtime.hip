@@ -47,6 +47,7 @@ void ark_hip_shutdown(void) {
       c->stage_a.release();
       c->stage_b.release();
       c->stage_c.release();
+      c->poly_work.release();
       for (int j = 0; j < 2; j++) {
         c->ring_s[j].release();
         c->ring_b[j].release();

@@ -1,6 +1,7 @@
-// Instantiation of the radix-2 FFT and the pointwise field kernels for BLS12_381_FR.
+// Instantiation of the radix-2 FFT and the pointwise field kernels and the polynomial kernels for BLS12_381_FR.
 #include "fft.cuh"
 #include "devops.cuh"
+#include "polyops.cuh"
 #include "internal.hpp"
 namespace arkhip {
 int fft_run_BLS12_381_FR(FftWorkspace& ws, void* d_data, int k, const uint64_t* root4, const uint64_t* pre4, const uint64_t* post4,
@@ -21,6 +22,22 @@ int fr_div_BLS12_381_FR(const void* num, const void* den, void* r, size_t n, hip
 }
 int fr_scale_BLS12_381_FR(const void* a, const uint64_t* k4, void* r, size_t n, hipStream_t s) {
   return fr_scale_launch<Fp<BLS12_381_FR>>(a, k4, r, n, s);
+}
+int poly_tile_value_BLS12_381_FR(const void* src, size_t n, const PolyPowers& pw, void* vals, hipStream_t s) {
+  return poly_tile_value_launch<Fp<BLS12_381_FR>>(src, n, pw, vals, s);
+}
+int poly_tile_divide_BLS12_381_FR(const void* src, size_t n, const PolyPowers& pw, const void* carries, void* dst, void* rem, hipStream_t s) {
+  return poly_tile_divide_launch<Fp<BLS12_381_FR>>(src, n, pw, carries, dst, rem, s);
+}
+int poly_vanishing_BLS12_381_FR(const void* p, size_t n, size_t m, void* q, void* r, hipStream_t s) {
+  return poly_vanishing_launch<Fp<BLS12_381_FR>>(p, n, m, q, r, s);
+}
+int poly_lagrange_BLS12_381_FR(const uint64_t* a4, const uint64_t* c4, const uint64_t* w4, const uint64_t* wstep4, int onehot, void* out,
+                       size_t n, size_t lanes, hipStream_t s) {
+  return poly_lagrange_launch<Fp<BLS12_381_FR>>(a4, c4, w4, wstep4, onehot, out, n, lanes, s);
+}
+int fr_inner_product_BLS12_381_FR(const void* a, const void* b, size_t n, void* partials, void* out, hipStream_t s) {
+  return fr_inner_product_launch<Fp<BLS12_381_FR>>(a, b, n, partials, out, s);
 }
 int fft_axis_BLS12_381_FR(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4, hipStream_t s) {
   return fft_axis_run<BLS12_381_FR>(ws, d_src, d_dst, G, cols, root4, s);

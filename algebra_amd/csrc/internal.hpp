@@ -13,6 +13,7 @@ struct MsmSumsHeader;
 struct MsmWidths;
 struct FftWorkspace;
 struct FftTimings;
+struct PolyPowers;
 
 // one function per curve / field, defined in msm_<curve>.hip / fft_<field>.hip
 #define ARK_DECL_CURVE(NAME)                                                                                    \
@@ -47,6 +48,13 @@ ARK_DECL_CURVE(BLS12_381_G2)
   int field_op_##NAME(int op, const void* d_a, const void* d_b, void* d_r, size_t n, hipStream_t s);          \
   int fr_scale_##NAME(const void* d_a, const uint64_t* k4, void* d_r, size_t n, hipStream_t s);                     \
   int fr_div_##NAME(const void* d_num, const void* d_den, void* d_r, size_t n, hipStream_t s);                      \
+  int poly_tile_value_##NAME(const void* d_src, size_t n, const PolyPowers& pw, void* d_vals, hipStream_t s);       \
+  int poly_tile_divide_##NAME(const void* d_src, size_t n, const PolyPowers& pw, const void* d_carries, void* d_dst, \
+                              void* d_rem, hipStream_t s);                                                          \
+  int poly_vanishing_##NAME(const void* d_p, size_t n, size_t m, void* d_q, void* d_r, hipStream_t s);              \
+  int poly_lagrange_##NAME(const uint64_t* a4, const uint64_t* c4, const uint64_t* w4, const uint64_t* wstep4,      \
+                           int onehot, void* d_out, size_t n, size_t lanes, hipStream_t s);                         \
+  int fr_inner_product_##NAME(const void* d_a, const void* d_b, size_t n, void* d_partials, void* d_out, hipStream_t s); \
   int fft_roots_##NAME(FftWorkspace& ws, int k, const uint64_t* root4, hipStream_t s, const uint32_t** out);        \
   int fft_scalars_##NAME(FftWorkspace& ws, const uint64_t* base4, const uint64_t* mul4, size_t count, void* d_out,  \
                          hipStream_t s);                                                                            \

@@ -183,6 +183,28 @@ class Radix2EvaluationDomain:
     def ifft_batch_in_place(self, evals):
         return self.fft_batch_in_place(evals, inverse=True)
 
+    def evaluate_vanishing_polynomial(self, tau):
+        """Z_H(tau) = tau^size - offset^size (domain/mod.rs:231-239), host arithmetic."""
+        t = np.ascontiguousarray(tau, dtype=np.uint64).reshape(4)
+        p = np.zeros(4, dtype=np.uint64)
+        check(lib().ark_hip_fr_pow(self.field, t.ctypes.data_as(C.c_void_p), self.size(), p.ctypes.data_as(C.c_void_p)),
+              "ark_hip_fr_pow")
+        r = cv.SCALAR_MODULUS[cv.FIELDS[self.field]]
+        val = lambda a: sum(int(v) << (64 * i) for i, v in enumerate(a))   # noqa: E731 -- Montgomery residues subtract as integers
+        d = (val(p) - val(self.coset_offset_pow_size())) % r
+        return np.array([(d >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+
+    def evaluate_all_lagrange_coefficients(self, tau):
+        """EvaluationDomain::evaluate_all_lagrange_coefficients (domain/mod.rs:157-222) as a DeviceVec of size()
+        elements: L_i(tau) for the points h g^i; with `DeviceVec.inner_product` and the evaluations of P over this
+        domain that is P(tau).  Asynchronous like the other device-vector operations."""
+        from .poly import DeviceVec
+        t = np.ascontiguousarray(tau, dtype=np.uint64).reshape(4)
+        out = DeviceVec(self.field, self.size(), _zero=False)
+        check(lib().ark_hip_domain_lagrange_coefficients_device(self.field, C.byref(self._s), t.ctypes.data_as(C.c_void_p),
+                                                                out.ptr), "ark_hip_domain_lagrange_coefficients_device")
+        return out
+
     def __repr__(self):
         return "Radix-2 multiplicative subgroup of size %d" % self.size()
 

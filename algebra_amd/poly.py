@@ -180,3 +180,45 @@ class DeviceVec:
             raise ValueError("domains are unequal")
         check(lib().ark_hip_ifft_in_place_device(self.field, C.byref(domain._s), self.ptr), "ark_hip_ifft_in_place_device")
         return self
+
+    # ---- the O(n) steps between the transforms and the MSM, without leaving the device ------------------------
+    def evaluate(self, point):
+        """DensePolynomial::evaluate (dense.rs:42-92): p(point) as a numpy uint64[4] (Montgomery); waits for it."""
+        z = np.ascontiguousarray(point, dtype=np.uint64).reshape(4)
+        out = np.zeros(4, dtype=np.uint64)
+        check(lib().ark_hip_poly_evaluate_device(self.field, self.ptr, self.len, z.ctypes.data_as(C.c_void_p),
+                                                 out.ctypes.data_as(C.c_void_p)), "ark_hip_poly_evaluate_device")
+        return out
+
+    def divide_by_linear(self, z, in_place=False):
+        """(quotient, remainder) of the division by x - z (divide_with_q_and_r for a degree-1 divisor, univariate/
+        mod.rs:145-159): the quotient is a DeviceVec of max(len, 1) - 1 coefficients, the remainder p(z) a numpy
+        uint64[4].  in_place: the quotient overwrites this vector, which is returned one element shorter."""
+        z = np.ascontiguousarray(z, dtype=np.uint64).reshape(4)
+        rem = np.zeros(4, dtype=np.uint64)
+        qlen = max(self.len, 1) - 1
+        q = self if in_place else DeviceVec(self.field, qlen, _zero=False)
+        check(lib().ark_hip_poly_divide_linear_device(self.field, self.ptr, self.len, z.ctypes.data_as(C.c_void_p), q.ptr,
+                                                      rem.ctypes.data_as(C.c_void_p)), "ark_hip_poly_divide_linear_device")
+        if in_place:
+            self.len = qlen
+        return q, rem
+
+    def divide_by_vanishing_poly(self, domain):
+        """DensePolynomial::divide_by_vanishing_poly (dense.rs:168-211): (quotient, remainder) as DeviceVecs of
+        max(len - m, 0) and min(len, m) coefficients, m = domain.size().  Only the size of the domain enters (the
+        divisor is x^m - 1 for a coset too, as in the reference)."""
+        m = domain.size()
+        q = DeviceVec(self.field, max(self.len - m, 0), _zero=False)
+        r = DeviceVec(self.field, min(self.len, m), _zero=False)
+        check(lib().ark_hip_poly_divide_by_vanishing_device(self.field, m, self.ptr, self.len, q.ptr, r.ptr),
+              "ark_hip_poly_divide_by_vanishing_device")
+        return q, r
+
+    def inner_product(self, other):
+        """sum_i self[i] * other[i] as a numpy uint64[4]; waits for it."""
+        self._same(other)
+        out = np.zeros(4, dtype=np.uint64)
+        check(lib().ark_hip_fr_inner_product_device(self.field, self.ptr, other.ptr, self.len, out.ctypes.data_as(C.c_void_p)),
+              "ark_hip_fr_inner_product_device")
+        return out

@@ -363,6 +363,43 @@ int ark_hip_fr_pow(int field, const uint64_t* base, uint64_t exp, uint64_t* out)
  * out[j][c] = sum_i root^(i j) in[i][c] */
 int ark_hip_fft_axis_device(int field, void* d_data, unsigned G, size_t cols, const uint64_t* root);
 
+/* ---- polynomial operations on device-resident vectors ------------------------------------------------------------
+ * The O(n) steps that sit between the transforms and the MSM in a prover -- a KZG opening (p(z), the witness polynomial
+ * (p(x) - p(z)) / (x - z)), the quotient by a vanishing polynomial, evaluation-form protocols -- on vectors that stay in
+ * device memory.  `field` as for ark_hip_fr_*_device; elements are 4 x u64 Montgomery residues; d_* are device pointers
+ * and the work runs on the context stream.  The single elements handed over by host pointer (point, z, tau) must be
+ * canonical residues (< p), like every element of the vectors; they are not checked.  ARK_HIP_ERR_ARG for an unknown field or
+ * a null pointer, checked before any device is touched; ARK_HIP_ERR_NO_DEVICE without a GPU. */
+/* DensePolynomial::evaluate (poly/src/polynomial/univariate/dense.rs:42-92): *out = sum_i coeffs[i] point^i.  point and
+ * out are HOST pointers to one element; the call waits for its result.  n = 0 gives 0; trailing zero coefficients are
+ * allowed (a device vector is not truncated). */
+int ark_hip_poly_evaluate_device(int field, const void* d_coeffs, size_t n, const uint64_t* point, uint64_t* out);
+/* Division by x - z: what DenseOrSparsePolynomial::divide_with_q_and_r computes for a degree-1 divisor
+ * (polynomial/univariate/mod.rs:145-159, the naive division).  Writes exactly max(n, 1) - 1 quotient elements
+ * q[i] = sum_{j > i} p[j] z^(j-i-1) to d_quot and the remainder p(z) to the HOST element out_rem, waiting for it.
+ * out_rem may be NULL: the call is then asynchronous like ark_hip_fr_*_device.  d_quot == d_coeffs (the same pointer) is
+ * allowed, element n - 1 of the buffer is then left as it was; any other overlap of the two is undefined. */
+int ark_hip_poly_divide_linear_device(int field, const void* d_coeffs, size_t n, const uint64_t* z, void* d_quot,
+                                      uint64_t* out_rem);
+/* DensePolynomial::divide_by_vanishing_poly (dense.rs:168-211).  As in the reference only the SIZE m of the domain enters:
+ * the divisor is x^m - 1, also when the domain is a coset.  n >= m: d_quot receives n - m elements
+ * q[j] = sum_{i >= 1, j + i m < n} p[j + i m], d_rem receives m elements r[j] = p[j] + q[j] (j < n - m), p[j] otherwise.
+ * n < m: the quotient is empty and d_rem receives the n coefficients.  Asynchronous; no aliasing.  The work is O(n) on m
+ * parallel lanes of n / m serial steps each: made for n a few times m with m large. */
+int ark_hip_poly_divide_by_vanishing_device(int field, size_t domain_size, const void* d_coeffs, size_t n, void* d_quot,
+                                            void* d_rem);
+/* EvaluationDomain::evaluate_all_lagrange_coefficients (poly/src/domain/mod.rs:157-222): d_out[i] = L_i(tau) for the
+ * dom->size points h g^i of the (coset) domain; when tau is one of them, that coefficient is one and the others are zero.
+ * tau: HOST pointer to one element.  Asynchronous. */
+int ark_hip_domain_lagrange_coefficients_device(int field, const ark_hip_radix2_domain* dom, const uint64_t* tau, void* d_out);
+/* *out = sum_i a[i] b[i] (HOST element; the call waits).  With the Lagrange coefficients above: P(tau) from the
+ * evaluations of P over the domain (the use domain/mod.rs:150-156 describes). */
+int ark_hip_fr_inner_product_device(int field, const void* d_a, const void* d_b, size_t n, uint64_t* out);
+/* Host only, no device needed: the tile length and the number of scan levels ark_hip_poly_evaluate_device and
+ * ark_hip_poly_divide_linear_device use for n coefficients (one level while a tile holds them all, one more per factor
+ * `tile`), as ark_hip_msm_plan exposes the MSM's plan. */
+int ark_hip_poly_scan_plan(size_t n, int* tile, int* levels);
+
 /* ---- one process per GPU: RCCL inside the library ---------------------------------------------------------------
  * The reference chunks an MSM by base range and sums the chunk results (variable_base/mod.rs:521-557); an FFT shards by
  * coefficient range with ONE transpose between two rounds of local butterflies (the four-step form of the radix-2

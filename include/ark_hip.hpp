@@ -349,6 +349,8 @@ class Communicator {
 
 // ---- Radix2EvaluationDomain ------------------------------------------------------------------------------------------
 template <int FIELD_ID>
+class DeviceVec;
+template <int FIELD_ID>
 class Radix2EvaluationDomain {
  public:
   // EvaluationDomain::new
@@ -429,6 +431,10 @@ class Radix2EvaluationDomain {
     check(ark_hip_fft_group_in_place(Curve::ID, &s_, reinterpret_cast<uint64_t*>(pts.data()), inverse ? 1 : 0),
           "ark_hip_fft_group_in_place");
   }
+  // evaluate_vanishing_polynomial (poly/src/domain/mod.rs:231-239) is host arithmetic of the caller's field type; what the
+  // device offers is evaluate_all_lagrange_coefficients (domain/mod.rs:157-222): L_i(tau) for the size() points h g^i, as a
+  // device vector -- with DeviceVec::inner_product and the evaluations of P over this domain that is P(tau).  Asynchronous.
+  DeviceVec<FIELD_ID> evaluate_all_lagrange_coefficients(const Fr& tau) const;
   const ark_hip_radix2_domain& raw() const { return s_; }
 
  private:
@@ -513,6 +519,49 @@ class DeviceVec {
   DeviceVec& operator*=(const Fr& k) { here(); check(ark_hip_fr_scale_device(FIELD_ID, p_, k.limbs.data(), p_, len_), "ark_hip_fr_scale_device"); return *this; }
   void negate() { here(); check(ark_hip_fr_neg_device(FIELD_ID, p_, p_, len_), "ark_hip_fr_neg_device"); }
 
+  // ---- the O(n) steps between the transforms and the MSM, without leaving the device ----
+  // len elements of device memory whose content is whatever the allocator left (for results written in full)
+  static DeviceVec uninit(size_t len) { DeviceVec v; v.alloc(len); return v; }
+  // DensePolynomial::evaluate (dense.rs:42-92); waits for its result
+  Fr evaluate(const Fr& point) const {
+    here();
+    Fr out;
+    check(ark_hip_poly_evaluate_device(FIELD_ID, p_, len_, point.limbs.data(), out.limbs.data()), "ark_hip_poly_evaluate_device");
+    return out;
+  }
+  // (quotient, remainder) of the division by x - z (divide_with_q_and_r for a degree-1 divisor, univariate/mod.rs:145-159);
+  // the quotient has max(len, 1) - 1 coefficients, the remainder is p(z)
+  std::pair<DeviceVec, Fr> divide_by_linear(const Fr& z) const {
+    here();
+    DeviceVec q = uninit(len_ ? len_ - 1 : 0);
+    Fr rem;
+    check(ark_hip_poly_divide_linear_device(FIELD_ID, p_, len_, z.limbs.data(), q.p_, rem.limbs.data()), "ark_hip_poly_divide_linear_device");
+    return {std::move(q), rem};
+  }
+  // the same with the quotient written over this vector, which becomes one element shorter; returns the remainder
+  Fr divide_by_linear_in_place(const Fr& z) {
+    here();
+    Fr rem;
+    check(ark_hip_poly_divide_linear_device(FIELD_ID, p_, len_, z.limbs.data(), p_, rem.limbs.data()), "ark_hip_poly_divide_linear_device");
+    if (len_) len_--;
+    return rem;
+  }
+  // DensePolynomial::divide_by_vanishing_poly (dense.rs:168-211): (quotient, remainder); only the domain's size enters
+  std::pair<DeviceVec, DeviceVec> divide_by_vanishing_poly(const Radix2EvaluationDomain<FIELD_ID>& domain) const {
+    here();
+    const size_t m = domain.size();
+    DeviceVec q = uninit(len_ > m ? len_ - m : 0), r = uninit(len_ < m ? len_ : m);
+    check(ark_hip_poly_divide_by_vanishing_device(FIELD_ID, m, p_, len_, q.p_, r.p_), "ark_hip_poly_divide_by_vanishing_device");
+    return {std::move(q), std::move(r)};
+  }
+  // sum_i self[i] * other[i]; waits for its result
+  Fr inner_product(const DeviceVec& o) const {
+    same(o);
+    Fr out;
+    check(ark_hip_fr_inner_product_device(FIELD_ID, p_, o.p_, len_, out.limbs.data()), "ark_hip_fr_inner_product_device");
+    return out;
+  }
+
  private:
   void* p_ = nullptr;
   size_t len_ = 0, cap_ = 0;
@@ -543,6 +592,14 @@ class DeviceVec {
     p_ = nullptr;
   }
 };
+
+template <int FIELD_ID>
+DeviceVec<FIELD_ID> Radix2EvaluationDomain<FIELD_ID>::evaluate_all_lagrange_coefficients(const Fr& tau) const {
+  DeviceVec<FIELD_ID> out = DeviceVec<FIELD_ID>::uninit(size());
+  check(ark_hip_domain_lagrange_coefficients_device(FIELD_ID, &s_, tau.limbs.data(), out.device_ptr()),
+        "ark_hip_domain_lagrange_coefficients_device");
+  return out;
+}
 
 // Evaluations<F, Radix2EvaluationDomain<F>> resident on the device (evaluations/univariate/mod.rs:18-29)
 template <int FIELD_ID>

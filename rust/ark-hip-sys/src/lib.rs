@@ -141,6 +141,22 @@ extern "C" {
     /// `r[i] = a[i] / b[i]`; a zero divisor gives zero (as `ark_ff::batch_inversion` leaves zeros in place).
     pub fn ark_hip_fr_div_device(field: c_int, d_a: *const c_void, d_b: *const c_void, d_r: *mut c_void, n: usize) -> c_int;
     pub fn ark_hip_fr_inverse_device(field: c_int, d_a: *const c_void, d_r: *mut c_void, n: usize) -> c_int;
+    /// `DensePolynomial::evaluate` on device-resident coefficients; `point` / `out`: one element each in host memory.
+    pub fn ark_hip_poly_evaluate_device(field: c_int, d_coeffs: *const c_void, n: usize, point: *const u64, out: *mut u64) -> c_int;
+    /// Division by `x - z`: `max(n, 1) - 1` quotient elements to `d_quot` (may be `d_coeffs` itself), `p(z)` to `out_rem`
+    /// (host; null: asynchronous).
+    pub fn ark_hip_poly_divide_linear_device(field: c_int, d_coeffs: *const c_void, n: usize, z: *const u64, d_quot: *mut c_void,
+                                             out_rem: *mut u64) -> c_int;
+    /// `DensePolynomial::divide_by_vanishing_poly`: the divisor is `x^domain_size - 1`.
+    pub fn ark_hip_poly_divide_by_vanishing_device(field: c_int, domain_size: usize, d_coeffs: *const c_void, n: usize,
+                                                   d_quot: *mut c_void, d_rem: *mut c_void) -> c_int;
+    /// `EvaluationDomain::evaluate_all_lagrange_coefficients` into `dom.size` elements of device memory.
+    pub fn ark_hip_domain_lagrange_coefficients_device(field: c_int, dom: *const ark_hip_radix2_domain, tau: *const u64,
+                                                       d_out: *mut c_void) -> c_int;
+    /// `sum_i a[i] * b[i]` to one element in host memory.
+    pub fn ark_hip_fr_inner_product_device(field: c_int, d_a: *const c_void, d_b: *const c_void, n: usize, out: *mut u64) -> c_int;
+    /// Host only: tile length and scan levels of the two entries above for `n` coefficients.
+    pub fn ark_hip_poly_scan_plan(n: usize, tile: *mut c_int, levels: *mut c_int) -> c_int;
     /// `r[i] = a[i] * k`, `k`: one Montgomery element in host memory (read before the call returns).
     pub fn ark_hip_fr_scale_device(field: c_int, d_a: *const c_void, k: *const u64, d_r: *mut c_void, n: usize) -> c_int;
     pub fn ark_hip_fft_in_place_degree_aware_device(field: c_int, dom: *const ark_hip_radix2_domain, d_data: *mut c_void,
@@ -201,6 +217,11 @@ pub fn fr_field_id<F: Field>() -> Option<c_int> {
 pub fn limbs<F>(x: &F) -> [u64; 4] {
     debug_assert_eq!(core::mem::size_of::<F>(), 32);
     unsafe { *(x as *const F as *const [u64; 4]) }
+}
+/// The inverse of [`limbs`]: a canonical Montgomery residue the library returned, as the field element it is.
+pub fn from_limbs<F: Copy>(x: &[u64; 4]) -> F {
+    debug_assert_eq!(core::mem::size_of::<F>(), 32);
+    unsafe { *(x as *const [u64; 4] as *const F) }
 }
 
 /// `TypeId` of `T` without a `'static` bound (types are compared modulo lifetimes; the coefficient types that matter here --

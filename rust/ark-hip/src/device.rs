@@ -176,6 +176,51 @@ impl<F: FftField> DeviceVec<F> {
         rc(unsafe { sys::ark_hip_fft_in_place_degree_aware_device(self.field, &d, self.ptr, have) })?;
         Ok(DeviceEvaluations { evals: self, domain })
     }
+    /// `DensePolynomial::evaluate` (dense.rs:42-92) on the device; waits for the one element that comes back.
+    pub fn evaluate(&self, point: &F) -> Result<F, DeviceError> {
+        self.here()?;
+        let z = sys::limbs(point);
+        let mut out = [0u64; 4];
+        rc(unsafe { sys::ark_hip_poly_evaluate_device(self.field, self.ptr, self.len, z.as_ptr(), out.as_mut_ptr()) })?;
+        Ok(sys::from_limbs::<F>(&out))
+    }
+    /// `(quotient, remainder)` of the division by `x - z` (`divide_with_q_and_r` for a degree-1 divisor,
+    /// polynomial/univariate/mod.rs:145-159): the KZG witness polynomial and `p(z)`.  The quotient overwrites this vector,
+    /// which becomes one element shorter: no second buffer, no host copy.
+    pub fn divide_by_linear(mut self, z: &F) -> Result<(Self, F), DeviceError> {
+        self.here()?;
+        let zl = sys::limbs(z);
+        let mut rem = [0u64; 4];
+        rc(unsafe { sys::ark_hip_poly_divide_linear_device(self.field, self.ptr, self.len, zl.as_ptr(), self.ptr, rem.as_mut_ptr()) })?;
+        self.len = self.len.saturating_sub(1);
+        Ok((self, sys::from_limbs::<F>(&rem)))
+    }
+    /// `DensePolynomial::divide_by_vanishing_poly` (dense.rs:168-211): `(quotient, remainder)`; as in the reference only the
+    /// size of the domain enters.
+    pub fn divide_by_vanishing_poly(&self, domain: &Radix2EvaluationDomain<F>) -> Result<(Self, Self), DeviceError> {
+        self.here()?;
+        let m = domain.size();
+        let q = Self::alloc(self.len.saturating_sub(m))?;
+        let r = Self::alloc(core::cmp::min(self.len, m))?;
+        rc(unsafe { sys::ark_hip_poly_divide_by_vanishing_device(self.field, m, self.ptr, self.len, q.ptr, r.ptr) })?;
+        Ok((q, r))
+    }
+    /// `sum_i self[i] * other[i]`; waits for the one element that comes back.
+    pub fn inner_product(&self, other: &Self) -> Result<F, DeviceError> {
+        self.same_len(other)?;
+        let mut out = [0u64; 4];
+        rc(unsafe { sys::ark_hip_fr_inner_product_device(self.field, self.ptr, other.ptr, self.len, out.as_mut_ptr()) })?;
+        Ok(sys::from_limbs::<F>(&out))
+    }
+    /// `EvaluationDomain::evaluate_all_lagrange_coefficients` (poly/src/domain/mod.rs:157-222) as a device vector: with
+    /// [`DeviceVec::inner_product`] and the evaluations of `P` over `domain`, that is `P(tau)`.
+    pub fn lagrange_coefficients(domain: &Radix2EvaluationDomain<F>, tau: &F) -> Result<Self, DeviceError> {
+        let v = Self::alloc(domain.size())?;
+        let d = raw_domain(domain);
+        let t = sys::limbs(tau);
+        rc(unsafe { sys::ark_hip_domain_lagrange_coefficients_device(v.field, &d, t.as_ptr(), v.ptr) })?;
+        Ok(v)
+    }
 }
 impl<F: FftField> Drop for DeviceVec<F> {
     fn drop(&mut self) {
