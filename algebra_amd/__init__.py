@@ -5,6 +5,7 @@ HIP library replaces:
 
     ark_ec::VariableBaseMSM            -> algebra_amd.msm   (msm, msm_unchecked, msm_bigint)
     ark_poly::Radix2EvaluationDomain   -> algebra_amd.domain.Radix2EvaluationDomain
+    ark_poly::DenseMultilinearExtension -> algebra_amd.mle.DenseMultilinearExtension
 
 All arithmetic runs in libark_hip.so (hand-written HIP for gfx950) through the C ABI of
 include/ark_hip.h; this package holds no arithmetic and no CPU fallback.
@@ -17,3 +18,4 @@ from .msm import (BatchMulPreprocessing, batch_mul, ChunkedPippenger, HashMapPip
                   base_cache_stats, base_cache_hash_stats, ResidentBases, pin_bases, msm_plan, msm_plan_widths, MSM_WIDTH_TOP)
 from .domain import Radix2EvaluationDomain  # noqa: F401
 from .poly import DeviceVec, poly_mul, poly_mul_host  # noqa: F401
+from .mle import DenseMultilinearExtension, mle_fold_plan, mle_fold_tiles  # noqa: F401

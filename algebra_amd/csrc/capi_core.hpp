@@ -491,6 +491,21 @@ inline int fr_inner_product_dispatch(int field, const void* a, const void* b, si
   ARK_FIELD_SWITCH(field, X);
 #undef X
 }
+inline int mle_fold_dispatch(int field, const void* src, int log_n, int w, const MlePoint& pt, void* dst, hipStream_t st) {
+#define X(NAME) mle_fold_##NAME(src, log_n, w, pt, dst, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int mle_relabel_dispatch(int field, const void* src, size_t n, int a, int b, int k, void* dst, hipStream_t st) {
+#define X(NAME) mle_relabel_##NAME(src, n, a, b, k, dst, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int fr_axpy_dispatch(int field, const void* a, const uint64_t* k4, const void* x, void* r, size_t n, hipStream_t st) {
+#define X(NAME) fr_axpy_##NAME(a, k4, x, r, n, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
 inline int fr_op_dispatch(int field, int op, const void* a, const void* b, void* r, size_t n, hipStream_t st) {
 #define X(NAME) field_op_##NAME(op, a, b, r, n, st)
   ARK_FIELD_SWITCH(field, X);

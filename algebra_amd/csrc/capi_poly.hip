@@ -1,9 +1,10 @@
 // C ABI of libark_hip.so: polynomial operations on device-resident vectors -- evaluation at a point, division by x - z and
-// by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products (see
-// include/ark_hip.h; kernels: polyops.cuh).
+// by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products -- and dense
+// multilinear extensions: fix_variables, evaluate, relabel, a + k x (see include/ark_hip.h; kernels: polyops.cuh, mle.cuh).
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "polyops.cuh"
+#include "mle.cuh"
 using namespace arkhip;
 using namespace arkhip::capi;
 
@@ -100,6 +101,34 @@ int lagrange_constants(const ark_hip_radix2_domain* dom, const uint64_t* tau4, s
   host_pow<FP>(gi, le, 1).store(wstep4);
   *onehot = 0;
   return 0;
+}
+
+// the launches that bind dim variables of a 2^num_vars table, shared by fix_variables and evaluate: the intermediate tables
+// live in Context::poly_work behind the result slot, the last launch writes `last` (nullptr: the result slot)
+inline int mle_fold_run(Context* c, int field, const void* d_evals, unsigned num_vars, const uint64_t* point, unsigned dim, void* last) {
+  int widths[MLE_MAX_PASSES];
+  const int passes = mle_fold_passes((int)dim, widths);
+  size_t scratch = 1;
+  for (int p = 0, m = (int)num_vars; p + 1 < passes; p++) scratch += (size_t)1 << (m -= widths[p]);
+  if (int rc = poly_scratch(c, scratch)) return rc;
+  char* w = (char*)c->poly_work.p + 32;
+  const void* cur = d_evals;
+  int m = (int)num_vars;
+  for (int p = 0; p < passes; p++) {
+    MlePoint pt = {};
+    for (int j = 0; j < widths[p]; j++, point += 4)
+      for (int q = 0; q < 4; q++) { pt.r[j].l[2 * q] = (u32)point[q]; pt.r[j].l[2 * q + 1] = (u32)(point[q] >> 32); }
+    void* dst = p + 1 < passes ? (void*)w : last ? last : c->poly_work.p;
+    if (int rc = mle_fold_dispatch(field, cur, m, widths[p], pt, dst, c->stream)) return rc;
+    m -= widths[p];
+    w += ((size_t)1 << m) * 32;
+    cur = dst;
+  }
+  return 0;
+}
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
 }
 
 }  // namespace
@@ -217,6 +246,81 @@ int ark_hip_fr_inner_product_device(int field, const void* d_a, const void* d_b,
   char* w = (char*)c->poly_work.p;
   if (int rc = fr_inner_product_dispatch(field, d_a, d_b, n, w + 32, w, c->stream)) return rc;
   return result_to_host(c, out);
+}
+
+int ark_hip_mle_fold_plan(unsigned num_vars, unsigned dim, int* tile_log, int* passes, int* widths) {
+  if (!tile_log || !passes || !widths || num_vars >= 64 || dim > num_vars) return ARK_HIP_ERR_ARG;
+  *tile_log = MLE_TILE_LOG;
+  for (int p = 0; p < MLE_MAX_PASSES; p++) widths[p] = 0;
+  *passes = mle_fold_passes((int)dim, widths);
+  return 0;
+}
+
+int ark_hip_mle_fold_tiles(unsigned num_vars, unsigned dim, int* tiles_log) {
+  if (!tiles_log || num_vars >= 64 || dim > num_vars) return ARK_HIP_ERR_ARG;
+  int widths[MLE_MAX_PASSES];
+  const int passes = mle_fold_passes((int)dim, widths);
+  for (int p = 0, m = (int)num_vars; p < MLE_MAX_PASSES; p++) {
+    tiles_log[p] = p < passes ? mle_fold_group_log(m, widths[p]) : 0;
+    if (p < passes) m -= widths[p];
+  }
+  return 0;
+}
+
+int ark_hip_mle_fix_variables_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* partial_point, unsigned dim,
+                                     void* d_out) {
+  if (!field_served(field) || !d_evals || !d_out || num_vars >= 64 || dim > num_vars || (dim && !partial_point)) return ARK_HIP_ERR_ARG;
+  if (num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
+  const size_t n = (size_t)1 << num_vars, n_out = n >> dim;
+  if (ranges_overlap(d_evals, n * 32, d_out, n_out * 32)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (dim == 0) {
+    ARK_HIP_TRY(hipMemcpyAsync(d_out, d_evals, n * 32, hipMemcpyDeviceToDevice, c->stream));
+    return mark_producer(c);
+  }
+  if (int rc = mle_fold_run(c, field, d_evals, num_vars, partial_point, dim, d_out)) return rc;
+  return mark_producer(c);
+}
+
+int ark_hip_mle_evaluate_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* point, uint64_t* out) {
+  if (!field_served(field) || !d_evals || !out || num_vars >= 64 || (num_vars && !point)) return ARK_HIP_ERR_ARG;
+  if (num_vars > 58) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (num_vars == 0) {   // a constant: its one table entry
+    ARK_HIP_TRY(hipMemcpyAsync(out, d_evals, 32, hipMemcpyDeviceToHost, c->stream));
+    ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  if (int rc = mle_fold_run(c, field, d_evals, num_vars, point, num_vars, nullptr)) return rc;
+  return result_to_host(c, out);
+}
+
+int ark_hip_mle_relabel_device(int field, const void* d_evals, unsigned num_vars, unsigned a, unsigned b, unsigned k, void* d_out) {
+  if (!field_served(field) || !d_evals || !d_out || num_vars >= 64) return ARK_HIP_ERR_ARG;
+  if (num_vars > 58) return ARK_HIP_ERR_ARG;
+  if (a > b) { const unsigned t = a; a = b; b = t; }
+  const bool identity = a == b || k == 0;   // the reference returns before its assertions (dense.rs:81-83)
+  if (!identity && ((uint64_t)b + k > num_vars || (uint64_t)a + k > b)) return ARK_HIP_ERR_ARG;
+  const size_t n = (size_t)1 << num_vars;
+  if (d_out != d_evals && ranges_overlap(d_evals, n * 32, d_out, n * 32)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (identity) {
+    if (d_out != d_evals) ARK_HIP_TRY(hipMemcpyAsync(d_out, d_evals, n * 32, hipMemcpyDeviceToDevice, c->stream));
+    return mark_producer(c);
+  }
+  if (int rc = mle_relabel_dispatch(field, d_evals, n, (int)a, (int)b, (int)k, d_out, c->stream)) return rc;
+  return mark_producer(c);
+}
+
+int ark_hip_fr_axpy_device(int field, const void* d_a, const uint64_t* k, const void* d_x, void* d_r, size_t n) {
+  if (!field_served(field) || !k || (n && (!d_a || !d_x || !d_r))) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (int rc = fr_axpy_dispatch(field, d_a, k, d_x, d_r, n, c->stream)) return rc;
+  return mark_producer(c);
 }
 
 }  // extern "C"

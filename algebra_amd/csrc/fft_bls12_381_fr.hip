@@ -1,7 +1,8 @@
-// Instantiation of the radix-2 FFT and the pointwise field kernels and the polynomial kernels for BLS12_381_FR.
+// Instantiation of the radix-2 FFT and the pointwise field kernels and the polynomial and multilinear kernels for BLS12_381_FR.
 #include "fft.cuh"
 #include "devops.cuh"
 #include "polyops.cuh"
+#include "mle.cuh"
 #include "internal.hpp"
 namespace arkhip {
 int fft_run_BLS12_381_FR(FftWorkspace& ws, void* d_data, int k, const uint64_t* root4, const uint64_t* pre4, const uint64_t* post4,
@@ -38,6 +39,15 @@ int poly_lagrange_BLS12_381_FR(const uint64_t* a4, const uint64_t* c4, const uin
 }
 int fr_inner_product_BLS12_381_FR(const void* a, const void* b, size_t n, void* partials, void* out, hipStream_t s) {
   return fr_inner_product_launch<Fp<BLS12_381_FR>>(a, b, n, partials, out, s);
+}
+int mle_fold_BLS12_381_FR(const void* src, int log_n, int w, const MlePoint& pt, void* dst, hipStream_t s) {
+  return mle_fold_launch<Fp<BLS12_381_FR>>(src, log_n, w, pt, dst, s);
+}
+int mle_relabel_BLS12_381_FR(const void* src, size_t n, int a, int b, int k, void* dst, hipStream_t s) {
+  return mle_relabel_launch<Fp<BLS12_381_FR>>(src, n, a, b, k, dst, s);
+}
+int fr_axpy_BLS12_381_FR(const void* a, const uint64_t* k4, const void* x, void* r, size_t n, hipStream_t s) {
+  return fr_axpy_launch<Fp<BLS12_381_FR>>(a, k4, x, r, n, s);
 }
 int fft_axis_BLS12_381_FR(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4, hipStream_t s) {
   return fft_axis_run<BLS12_381_FR>(ws, d_src, d_dst, G, cols, root4, s);

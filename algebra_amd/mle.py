@@ -1,0 +1,207 @@
+"""DenseMultilinearExtension on a device-resident evaluation table -- the Python mirror of ark_poly's type of that name
+(poly/src/evaluations/multivariate/multilinear/dense.rs; C++: include/ark_hip.hpp, Rust: rust/ark-hip/src/mle.rs).  The table
+of 2^num_vars Montgomery elements is a `DeviceVec`: committing to it is an MSM on `evaluations.ptr` with Montgomery
+scalars, binding variables (`fix_variables`, `evaluate`) runs on it where it lies.  Index bit 0 is the first variable.
+No arithmetic happens here: scalars are handed to the library as they are."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib
+from .poly import DeviceVec
+
+
+def mle_fold_plan(num_vars, dim):
+    """(tile_log, [variables bound by each launch]) of fix_variables / evaluate for `dim` variables of a 2^num_vars table"""
+    t, ps = C.c_int(), C.c_int()
+    widths = (C.c_int * 8)()
+    check(lib().ark_hip_mle_fold_plan(num_vars, dim, C.byref(t), C.byref(ps), widths), "ark_hip_mle_fold_plan")
+    return t.value, [widths[i] for i in range(ps.value)]
+
+
+def mle_fold_tiles(num_vars, dim):
+    """[log2 of the tiles one wave takes] for each launch of mle_fold_plan(num_vars, dim): which kernel variant runs"""
+    tiles = (C.c_int * 8)()
+    check(lib().ark_hip_mle_fold_tiles(num_vars, dim, tiles), "ark_hip_mle_fold_tiles")
+    return [tiles[i] for i in range(len(mle_fold_plan(num_vars, dim)[1]))]
+
+
+def _element(x):
+    return np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
+
+
+def _elements(xs, count=None):
+    a = np.ascontiguousarray(xs, dtype=np.uint64).reshape(-1, 4)
+    if count is not None and a.shape[0] != count:
+        raise ValueError("the point has %d coordinates, %d expected" % (a.shape[0], count))
+    return a
+
+
+class DenseMultilinearExtension:
+    def __init__(self, num_vars, evaluations):
+        """takes ownership of the DeviceVec `evaluations` (from_evaluations_vec, dense.rs:58-70)"""
+        if len(evaluations) != 1 << num_vars:
+            raise ValueError("The size of evaluations should be 2^num_vars.")   # the reference's assertion
+        self.num_vars = int(num_vars)
+        self.evaluations = evaluations
+        self.field = evaluations.field
+
+    @classmethod
+    def from_evaluations(cls, field, num_vars, evaluations):
+        """numpy uint64 [2^num_vars, 4] (Montgomery) -> one upload"""
+        a = _elements(evaluations)
+        if a.shape[0] != 1 << num_vars:
+            raise ValueError("The size of evaluations should be 2^num_vars.")
+        return cls(num_vars, DeviceVec.from_host(field, a))
+
+    @classmethod
+    def zero(cls, field):
+        """the constant zero: num_vars = 0 and one zero evaluation (dense.rs:422-427)"""
+        return cls(0, DeviceVec(field, 1))
+
+    def is_zero(self):
+        """num_vars == 0 and the evaluation is zero (dense.rs:429-431): a 32-byte download, and only when num_vars == 0"""
+        return self.num_vars == 0 and not self.evaluations.to_host().any()
+
+    def to_evaluations(self):
+        return self.evaluations.to_host()
+
+    def clone(self):
+        return DenseMultilinearExtension(self.num_vars, self.evaluations.clone())
+
+    def free(self):
+        self.evaluations.free()
+
+    def __len__(self):
+        return len(self.evaluations)
+
+    # ---- binding variables --------------------------------------------------------------------------------------
+    def fix_variables(self, partial_point):
+        """binds the first len(partial_point) variables (dense.rs:224-257); a new polynomial, self is left as it is"""
+        pt = _elements(partial_point)
+        dim = pt.shape[0]
+        if dim > self.num_vars:
+            raise ValueError("invalid size of partial point")
+        out = DeviceVec(self.field, 1 << (self.num_vars - dim), _zero=False)
+        check(lib().ark_hip_mle_fix_variables_device(self.field, self.evaluations.ptr, self.num_vars, pt.ctypes.data_as(C.c_void_p),
+                                                     dim, out.ptr), "ark_hip_mle_fix_variables_device")
+        return DenseMultilinearExtension(self.num_vars - dim, out)
+
+    def evaluate(self, point):
+        """the value at `point` (num_vars coordinates) as a numpy uint64[4]; waits for it (dense.rs:460-465)"""
+        pt = _elements(point, self.num_vars)
+        out = np.zeros(4, dtype=np.uint64)
+        check(lib().ark_hip_mle_evaluate_device(self.field, self.evaluations.ptr, self.num_vars, pt.ctypes.data_as(C.c_void_p),
+                                                out.ctypes.data_as(C.c_void_p)), "ark_hip_mle_evaluate_device")
+        return out
+
+    # ---- relabel ------------------------------------------------------------------------------------------------
+    def _relabel(self, a, b, k, dst):
+        lo, hi = min(a, b), max(a, b)
+        if lo != hi and k != 0:
+            if hi + k > self.num_vars:
+                raise ValueError("invalid relabel argument")
+            if lo + k > hi:
+                raise ValueError("overlapped swap window is not allowed")
+        check(lib().ark_hip_mle_relabel_device(self.field, self.evaluations.ptr, self.num_vars, a, b, k, dst.ptr),
+              "ark_hip_mle_relabel_device")
+
+    def relabel(self, a, b, k):
+        """exchanges the k variables from position a with those from position b (dense.rs:195-199); a new polynomial"""
+        out = DeviceVec(self.field, len(self.evaluations), _zero=False)
+        self._relabel(a, b, k, out)
+        return DenseMultilinearExtension(self.num_vars, out)
+
+    def relabel_in_place(self, a, b, k):
+        self._relabel(a, b, k, self.evaluations)
+        return self
+
+    # ---- concat -------------------------------------------------------------------------------------------------
+    @classmethod
+    def concat(cls, polys):
+        """the tables one after the other, zero-filled up to the next power of two (dense.rs:133-156)"""
+        polys = list(polys)
+        if not polys:
+            raise ValueError("concat of no polynomials")
+        field = polys[0].field
+        total = sum(len(p) for p in polys)
+        num_vars = max(total - 1, 0).bit_length()
+        out = DeviceVec(field, 1 << num_vars, _zero=False)
+        L, at = lib(), 0
+        for p in polys:
+            if p.field != field:
+                raise ValueError("polynomials over different fields")
+            check(L.ark_hip_memcpy_d2d(C.c_void_p(out.ptr.value + at * 32), p.evaluations.ptr, len(p) * 32), "ark_hip_memcpy_d2d")
+            at += len(p)
+        if at < len(out):
+            check(L.ark_hip_memset_device(C.c_void_p(out.ptr.value + at * 32), 0, (len(out) - at) * 32), "ark_hip_memset_device")
+        return cls(num_vars, out)
+
+    # ---- the vector space ---------------------------------------------------------------------------------------
+    def _pointwise(self, entry, other):
+        if other.field != self.field:
+            raise ValueError("polynomials over different fields")
+        out = DeviceVec(self.field, len(self.evaluations), _zero=False)
+        check(getattr(lib(), entry)(self.field, self.evaluations.ptr, other.evaluations.ptr, out.ptr, len(out)), entry)
+        return DenseMultilinearExtension(self.num_vars, out)
+
+    def __add__(self, rhs):
+        """dense.rs:286-305: the constant zero on either side gives a copy of the other, whatever its num_vars"""
+        if rhs.is_zero():
+            return self.clone()
+        if self.is_zero():
+            return rhs.clone()
+        if self.num_vars != rhs.num_vars:
+            raise ValueError("num_vars differ: %d and %d" % (self.num_vars, rhs.num_vars))
+        return self._pointwise("ark_hip_fr_add_device", rhs)
+
+    def __neg__(self):
+        out = DeviceVec(self.field, len(self.evaluations), _zero=False)
+        check(lib().ark_hip_fr_neg_device(self.field, self.evaluations.ptr, out.ptr, len(out)), "ark_hip_fr_neg_device")
+        return DenseMultilinearExtension(self.num_vars, out)
+
+    def __sub__(self, rhs):
+        """self + (-rhs), with the zero cases of + (dense.rs:348-354)"""
+        if rhs.is_zero():
+            return self.clone()
+        if self.is_zero():
+            return -rhs
+        if self.num_vars != rhs.num_vars:
+            raise ValueError("num_vars differ: %d and %d" % (self.num_vars, rhs.num_vars))
+        return self._pointwise("ark_hip_fr_sub_device", rhs)
+
+    def __mul__(self, scalar):
+        """times one field element (numpy uint64[4], Montgomery); times zero gives zero() (dense.rs:376-392)"""
+        k = _element(scalar)
+        if not k.any():
+            return DenseMultilinearExtension.zero(self.field)
+        out = DeviceVec(self.field, len(self.evaluations), _zero=False)
+        check(lib().ark_hip_fr_scale_device(self.field, self.evaluations.ptr, k.ctypes.data_as(C.c_void_p), out.ptr, len(out)),
+              "ark_hip_fr_scale_device")
+        return DenseMultilinearExtension(self.num_vars, out)
+
+    def __iadd__(self, rhs):
+        """`+= other` and `+= (f, other)`: self + f other in one pass over the tables (dense.rs:307-327)"""
+        if not isinstance(rhs, tuple):
+            new = self + rhs
+        else:
+            f, other = rhs
+            k = _element(f)
+            if other.is_zero() or (other.num_vars == 0 and not k.any()):      # f other is the constant zero
+                return self
+            if self.is_zero():                                                # the scaled table itself, also when f is zero
+                out = DeviceVec(self.field, len(other.evaluations), _zero=False)
+                check(lib().ark_hip_fr_scale_device(self.field, other.evaluations.ptr, k.ctypes.data_as(C.c_void_p), out.ptr, len(out)),
+                      "ark_hip_fr_scale_device")
+                new = DenseMultilinearExtension(other.num_vars, out)
+            else:
+                if self.num_vars != other.num_vars:
+                    raise ValueError("num_vars differ: %d and %d" % (self.num_vars, other.num_vars))
+                check(lib().ark_hip_fr_axpy_device(self.field, self.evaluations.ptr, k.ctypes.data_as(C.c_void_p), other.evaluations.ptr,
+                                                   self.evaluations.ptr, len(self.evaluations)), "ark_hip_fr_axpy_device")
+                return self
+        old = self.evaluations
+        self.num_vars, self.evaluations = new.num_vars, new.evaluations
+        new.evaluations = old
+        new.free()
+        return self

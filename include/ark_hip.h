@@ -400,6 +400,41 @@ int ark_hip_fr_inner_product_device(int field, const void* d_a, const void* d_b,
  * `tile`), as ark_hip_msm_plan exposes the MSM's plan. */
 int ark_hip_poly_scan_plan(size_t n, int* tile, int* levels);
 
+/* ---- dense multilinear extensions on device-resident evaluation tables ---------------------------------------------
+ * DenseMultilinearExtension (poly/src/evaluations/multivariate/multilinear/dense.rs): a table of 2^num_vars evaluations over
+ * the boolean hypercube, index bit 0 being the FIRST variable (index 0b1011 is P(1,1,0,1)).  Committing to such a table is
+ * an MSM with scalars_are_montgomery = 1 on the same device vector; these entries bind its variables without the table
+ * leaving the device.  Conventions as for the section above: canonical Montgomery residues, points by HOST pointer read
+ * before the call returns, ARK_HIP_ERR_ARG (also for num_vars >= 64, and for a device table of more than 2^58 elements,
+ * whose bytes a size_t cannot count) before any device is touched. */
+/* MultilinearExtension::fix_variables (dense.rs:224-257): binds the first `dim` variables to partial_point[0 .. dim-1] and
+ * writes the 2^(num_vars - dim) evaluations of what is left to d_out; binding variable 0 maps
+ * out[b] = t[2b] + r (t[2b+1] - t[2b]).  Several variables are bound per kernel launch (ark_hip_mle_fold_plan).  dim = 0
+ * copies; dim > num_vars is ARK_HIP_ERR_ARG.  The input is left untouched.  There is NO in-place form: one workgroup writes
+ * where another still reads, so d_out must not overlap d_evals (ARK_HIP_ERR_ARG).  Asynchronous. */
+int ark_hip_mle_fix_variables_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* partial_point,
+                                     unsigned dim, void* d_out);
+/* Polynomial::evaluate (dense.rs:460-465): binds all num_vars variables to point[0 .. num_vars-1] -- the launches of
+ * fix_variables, the last one writing a result slot.  out is a HOST element; the call waits for it. */
+int ark_hip_mle_evaluate_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* point, uint64_t* out);
+/* relabel / relabel_in_place (dense.rs:76-92, :195-199): d_out[i] = d_evals[swap_bits(i, a, b, k)], exchanging the k
+ * variables from position a with the k from position b.  d_out == d_evals (the same pointer) works in place; any other
+ * overlap is ARK_HIP_ERR_ARG.  After ordering a <= b: a == b or k == 0 copies (in place: nothing happens); otherwise
+ * b + k <= num_vars and a + k <= b must hold (the reference's two assertions), else ARK_HIP_ERR_ARG.  Asynchronous. */
+int ark_hip_mle_relabel_device(int field, const void* d_evals, unsigned num_vars, unsigned a, unsigned b, unsigned k,
+                               void* d_out);
+/* r[i] = a[i] + k x[i] in one pass (AddAssign<(F, &Self)>, dense.rs:319-327); k: HOST pointer to one element; r may alias a
+ * or x.  Asynchronous. */
+int ark_hip_fr_axpy_device(int field, const void* d_a, const uint64_t* k, const void* d_x, void* d_r, size_t n);
+/* Host only, no device needed: the launches that bind `dim` variables of a 2^num_vars table.  *tile_log: the most variables
+ * one launch binds; *passes: the number of launches; widths[0 .. *passes-1]: the variables each binds, in order (the rest of
+ * the 8 entries are set to 0). */
+int ark_hip_mle_fold_plan(unsigned num_vars, unsigned dim, int* tile_log, int* passes, int* widths);
+/* Host only: tiles_log[p] = log2 of the tiles of 2^tile_log elements one wave takes in launch p of that plan (8 entries,
+ * 0 past the last launch).  The fold kernel is compiled once per (variables bound, tiles per wave); more tiles per wave mean
+ * fewer multiplies per element, and large tables get more of them.  Tests read from it which kernel variant a size runs. */
+int ark_hip_mle_fold_tiles(unsigned num_vars, unsigned dim, int* tiles_log);
+
 /* ---- one process per GPU: RCCL inside the library ---------------------------------------------------------------
  * The reference chunks an MSM by base range and sums the chunk results (variable_base/mod.rs:521-557); an FFT shards by
  * coefficient range with ONE transpose between two rounds of local butterflies (the four-step form of the radix-2

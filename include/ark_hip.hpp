@@ -630,4 +630,121 @@ DeviceEvaluations<FIELD_ID> evaluate_over_domain(DeviceVec<FIELD_ID>&& coeffs, c
   return DeviceEvaluations<FIELD_ID>{std::move(coeffs), domain};
 }
 
+// DenseMultilinearExtension<F> resident on the device (poly/src/evaluations/multivariate/multilinear/dense.rs): 2^num_vars
+// evaluations over the boolean hypercube, index bit 0 being the first variable.  Committing to it is an MSM with Montgomery
+// scalars on evaluations().device_ptr(); fix_variables and evaluate bind its variables where the table lies.
+template <int FIELD_ID>
+class DenseMultilinearExtension {
+ public:
+  using Vec = DeviceVec<FIELD_ID>;
+  // from_evaluations_vec (dense.rs:58-70)
+  DenseMultilinearExtension(size_t num_vars, Vec&& evaluations) : num_vars_(num_vars), evals_(std::move(evaluations)) {
+    if (num_vars >= 64 || evals_.len() != (size_t)1 << num_vars) throw Error(ARK_HIP_ERR_ARG, "The size of evaluations should be 2^num_vars.");
+  }
+  static DenseMultilinearExtension from_evaluations_vec(size_t num_vars, const std::vector<Fr>& evaluations) {
+    return DenseMultilinearExtension(num_vars, Vec::from_vec(evaluations));
+  }
+  static DenseMultilinearExtension zero() { return DenseMultilinearExtension(0, Vec(1)); }   // dense.rs:422-427
+  // num_vars == 0 and a zero evaluation (dense.rs:429-431): one element is downloaded, and only when num_vars == 0
+  bool is_zero() const { return num_vars_ == 0 && evals_.to_vec()[0] == Fr{}; }
+  size_t num_vars() const { return num_vars_; }
+  std::vector<Fr> to_evaluations() const { return evals_.to_vec(); }
+  const Vec& evaluations() const { return evals_; }
+  Vec& evaluations() { return evals_; }
+  DenseMultilinearExtension clone() const { return DenseMultilinearExtension(num_vars_, evals_.clone()); }
+
+  // binds the first partial_point.size() variables (dense.rs:224-257)
+  DenseMultilinearExtension fix_variables(const std::vector<Fr>& partial_point) const {
+    const size_t dim = partial_point.size();
+    if (dim > num_vars_) throw Error(ARK_HIP_ERR_ARG, "invalid size of partial point");
+    Vec out = Vec::uninit((size_t)1 << (num_vars_ - dim));
+    check(ark_hip_mle_fix_variables_device(FIELD_ID, evals_.device_ptr(), (unsigned)num_vars_, (const uint64_t*)partial_point.data(),
+                                           (unsigned)dim, out.device_ptr()), "ark_hip_mle_fix_variables_device");
+    return DenseMultilinearExtension(num_vars_ - dim, std::move(out));
+  }
+  // Polynomial::evaluate (dense.rs:460-465); waits for its result
+  Fr evaluate(const std::vector<Fr>& point) const {
+    if (point.size() != num_vars_) throw Error(ARK_HIP_ERR_ARG, "point.len() == self.num_vars");
+    Fr out;
+    check(ark_hip_mle_evaluate_device(FIELD_ID, evals_.device_ptr(), (unsigned)num_vars_, (const uint64_t*)point.data(),
+                                      out.limbs.data()), "ark_hip_mle_evaluate_device");
+    return out;
+  }
+  // exchanges the k variables from position a with those from position b (dense.rs:76-92, :195-199)
+  DenseMultilinearExtension relabel(size_t a, size_t b, size_t k) const {
+    Vec out = Vec::uninit(evals_.len());
+    check(ark_hip_mle_relabel_device(FIELD_ID, evals_.device_ptr(), (unsigned)num_vars_, (unsigned)a, (unsigned)b, (unsigned)k,
+                                     out.device_ptr()), "ark_hip_mle_relabel_device");
+    return DenseMultilinearExtension(num_vars_, std::move(out));
+  }
+  void relabel_in_place(size_t a, size_t b, size_t k) {
+    check(ark_hip_mle_relabel_device(FIELD_ID, evals_.device_ptr(), (unsigned)num_vars_, (unsigned)a, (unsigned)b, (unsigned)k,
+                                     evals_.device_ptr()), "ark_hip_mle_relabel_device");
+  }
+  // the tables one after the other, zero-filled up to the next power of two (dense.rs:133-156)
+  static DenseMultilinearExtension concat(const std::vector<const DenseMultilinearExtension*>& polys) {
+    size_t total = 0, nv = 0;
+    for (auto* q : polys) total += q->evals_.len();
+    while (((size_t)1 << nv) < total) nv++;
+    Vec out = Vec::uninit((size_t)1 << nv);
+    size_t at = 0;
+    for (auto* q : polys) {
+      check(ark_hip_memcpy_d2d((char*)out.device_ptr() + at * 32, q->evals_.device_ptr(), q->evals_.len() * 32), "ark_hip_memcpy_d2d");
+      at += q->evals_.len();
+    }
+    if (at < out.len()) check(ark_hip_memset_device((char*)out.device_ptr() + at * 32, 0, (out.len() - at) * 32), "ark_hip_memset_device");
+    return DenseMultilinearExtension(nv, std::move(out));
+  }
+  // +, - and neg (dense.rs:278-366): the constant zero on either side of + gives a copy of the other operand
+  DenseMultilinearExtension operator+(const DenseMultilinearExtension& o) const {
+    if (o.is_zero()) return clone();
+    if (is_zero()) return o.clone();
+    same(o);
+    Vec out = Vec::uninit(evals_.len());
+    check(ark_hip_fr_add_device(FIELD_ID, evals_.device_ptr(), o.evals_.device_ptr(), out.device_ptr(), out.len()), "ark_hip_fr_add_device");
+    return DenseMultilinearExtension(num_vars_, std::move(out));
+  }
+  DenseMultilinearExtension operator-() const {
+    Vec out = Vec::uninit(evals_.len());
+    check(ark_hip_fr_neg_device(FIELD_ID, evals_.device_ptr(), out.device_ptr(), out.len()), "ark_hip_fr_neg_device");
+    return DenseMultilinearExtension(num_vars_, std::move(out));
+  }
+  DenseMultilinearExtension operator-(const DenseMultilinearExtension& o) const {
+    if (o.is_zero()) return clone();
+    if (is_zero()) return -o;
+    same(o);
+    Vec out = Vec::uninit(evals_.len());
+    check(ark_hip_fr_sub_device(FIELD_ID, evals_.device_ptr(), o.evals_.device_ptr(), out.device_ptr(), out.len()), "ark_hip_fr_sub_device");
+    return DenseMultilinearExtension(num_vars_, std::move(out));
+  }
+  // times one field element; times zero gives zero() (dense.rs:376-392)
+  DenseMultilinearExtension operator*(const Fr& k) const {
+    if (k == Fr{}) return zero();
+    return scaled(k);
+  }
+  // self += f * other in one pass over the tables (AddAssign<(F, &Self)>, dense.rs:319-327)
+  void add_assign_scaled(const Fr& f, const DenseMultilinearExtension& o) {
+    if (o.is_zero() || (o.num_vars_ == 0 && f == Fr{})) return;   // f * other is the constant zero
+    if (is_zero()) { *this = o.scaled(f); return; }
+    same(o);
+    check(ark_hip_fr_axpy_device(FIELD_ID, evals_.device_ptr(), f.limbs.data(), o.evals_.device_ptr(), evals_.device_ptr(), evals_.len()),
+          "ark_hip_fr_axpy_device");
+  }
+  DenseMultilinearExtension& operator+=(const DenseMultilinearExtension& o) { *this = *this + o; return *this; }
+  DenseMultilinearExtension(DenseMultilinearExtension&&) noexcept = default;
+  DenseMultilinearExtension& operator=(DenseMultilinearExtension&&) noexcept = default;
+
+ private:
+  size_t num_vars_ = 0;
+  Vec evals_;
+  void same(const DenseMultilinearExtension& o) const {
+    if (o.num_vars_ != num_vars_) throw Error(ARK_HIP_ERR_ARG, "assert_eq!(self.num_vars, rhs.num_vars)");
+  }
+  DenseMultilinearExtension scaled(const Fr& k) const {
+    Vec out = Vec::uninit(evals_.len());
+    check(ark_hip_fr_scale_device(FIELD_ID, evals_.device_ptr(), k.limbs.data(), out.device_ptr(), out.len()), "ark_hip_fr_scale_device");
+    return DenseMultilinearExtension(num_vars_, std::move(out));
+  }
+};
+
 }  // namespace ark_hip

@@ -3,7 +3,7 @@
 //! surface: ark-ec and ark-poly `#![forbid(unsafe_code)]` (ec/src/lib.rs:10, poly/src/lib.rs:4).
 #![allow(non_camel_case_types)]
 use ark_ff::{FftField, Field, PrimeField};
-use core::ffi::{c_char, c_int, c_longlong, c_void};
+use core::ffi::{c_char, c_int, c_longlong, c_uint, c_void};
 
 // field ids / curve ids of include/ark_hip.h
 pub const BN254_FQ: c_int = 0;
@@ -157,6 +157,21 @@ extern "C" {
     pub fn ark_hip_fr_inner_product_device(field: c_int, d_a: *const c_void, d_b: *const c_void, n: usize, out: *mut u64) -> c_int;
     /// Host only: tile length and scan levels of the two entries above for `n` coefficients.
     pub fn ark_hip_poly_scan_plan(n: usize, tile: *mut c_int, levels: *mut c_int) -> c_int;
+    /// `DenseMultilinearExtension::fix_variables` (multilinear/dense.rs:224-257) on a device table of `2^num_vars` elements:
+    /// binds the first `dim` variables, writes `2^(num_vars - dim)` elements; `d_out` must not overlap `d_evals`.
+    pub fn ark_hip_mle_fix_variables_device(field: c_int, d_evals: *const c_void, num_vars: c_uint, partial_point: *const u64,
+                                            dim: c_uint, d_out: *mut c_void) -> c_int;
+    /// `Polynomial::evaluate` of the same type (dense.rs:460-465); `out`: one host element, the call waits.
+    pub fn ark_hip_mle_evaluate_device(field: c_int, d_evals: *const c_void, num_vars: c_uint, point: *const u64, out: *mut u64) -> c_int;
+    /// `relabel` / `relabel_in_place` (dense.rs:76-92); `d_out == d_evals` works in place.
+    pub fn ark_hip_mle_relabel_device(field: c_int, d_evals: *const c_void, num_vars: c_uint, a: c_uint, b: c_uint, k: c_uint,
+                                      d_out: *mut c_void) -> c_int;
+    /// `r[i] = a[i] + k * x[i]`; `r` may alias `a` or `x`.
+    pub fn ark_hip_fr_axpy_device(field: c_int, d_a: *const c_void, k: *const u64, d_x: *const c_void, d_r: *mut c_void, n: usize) -> c_int;
+    /// Host only: the variables bound by each launch of the two entries above (`widths`: 8 entries).
+    pub fn ark_hip_mle_fold_plan(num_vars: c_uint, dim: c_uint, tile_log: *mut c_int, passes: *mut c_int, widths: *mut c_int) -> c_int;
+    /// Host only: log2 of the tiles one wave takes in each launch of that plan (`tiles_log`: 8 entries).
+    pub fn ark_hip_mle_fold_tiles(num_vars: c_uint, dim: c_uint, tiles_log: *mut c_int) -> c_int;
     /// `r[i] = a[i] * k`, `k`: one Montgomery element in host memory (read before the call returns).
     pub fn ark_hip_fr_scale_device(field: c_int, d_a: *const c_void, k: *const u64, d_r: *mut c_void, n: usize) -> c_int;
     pub fn ark_hip_fft_in_place_degree_aware_device(field: c_int, dom: *const ark_hip_radix2_domain, d_data: *mut c_void,

@@ -56,7 +56,7 @@ impl<F: FftField> DeviceVec<F> {
         }
         sys::fr_field_id::<F>().ok_or(DeviceError::UnsupportedField)
     }
-    fn alloc(len: usize) -> Result<Self, DeviceError> {
+    pub(crate) fn alloc(len: usize) -> Result<Self, DeviceError> {
         let field = Self::field_id()?;
         let mut ptr: *mut c_void = core::ptr::null_mut();
         if len != 0 {
@@ -94,6 +94,9 @@ impl<F: FftField> DeviceVec<F> {
     pub fn len(&self) -> usize {
         self.len
     }
+    pub(crate) fn field(&self) -> c_int {
+        self.field
+    }
     pub fn is_empty(&self) -> bool {
         self.len == 0
     }
@@ -121,7 +124,7 @@ impl<F: FftField> DeviceVec<F> {
         Ok(())
     }
     /// every operation runs on the stream of the thread's CURRENT device: refuse a vector that lives elsewhere
-    fn here(&self) -> Result<(), DeviceError> {
+    pub(crate) fn here(&self) -> Result<(), DeviceError> {
         if self.ptr.is_null() || unsafe { sys::ark_hip_get_device() } == self.device { Ok(()) } else { Err(DeviceError::WrongDevice) }
     }
     fn same_len(&self, other: &Self) -> Result<(), DeviceError> {

@@ -13,6 +13,8 @@
 //! * **chains of transforms**: [`device::DeviceVec`] / [`device::DeviceEvaluations`] keep coefficient and evaluation
 //!   vectors in HBM -- `evaluate_over_domain` -> pointwise `+=`, `-=`, `*=` -> `interpolate` with one upload per input
 //!   and one download, instead of two PCIe crossings per transform through the `EvaluationDomain` hook.
+//! * **multilinear provers**: [`mle::DenseMultilinearExtension`] keeps a table of 2^nu evaluations in HBM -- the commitment
+//!   is an MSM on it, `fix_variables` / `evaluate` / `relabel` bind and move its variables without a PCIe crossing.
 //!
 //! Beyond the reference's surface: [`msm::PreparedBases`] (a fixed SRS resident on the GPU with its per-window
 //! multiples), [`msm::MsmJob`] (asynchronous MSMs), [`msm::msm_multi`] (one MSM over all GPUs of the node).
@@ -21,10 +23,12 @@
 //! tests/ through ctypes and through the compiled C++ mirror (include/ark_hip.hpp).
 pub mod device;
 pub mod domain;
+pub mod mle;
 pub mod msm;
 pub use ark_hip_sys as sys;
 pub use ark_hip_sys::{BLS12_377_G1, BLS12_377_G2, BLS12_381_G1, BLS12_381_G2, BN254_G1};
 pub use device::{DeviceError, DeviceEvaluations, DeviceVec};
+pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension};
 pub use msm::{serve_group_coefficients, sw_msm, sw_msm_bigint, HipServed};
 #[cfg(feature = "ec-hook")]
 pub use msm::{sw_batch_mul, sw_msm_small, sw_normalize_batch};

@@ -1,0 +1,180 @@
+//! `DenseMultilinearExtension` resident on the device: the mirror of ark-poly's type of that name
+//! (poly/src/evaluations/multivariate/multilinear/dense.rs).  The table of `2^num_vars` evaluations is a [`DeviceVec`]:
+//! committing to it is an MSM with Montgomery scalars on `evaluations().as_device_ptr()`, and `fix_variables` / `evaluate`
+//! bind its variables where the table lies.  Index bit 0 is the first variable, as in the reference.
+use crate::device::{DeviceError, DeviceVec};
+use ark_ff::FftField;
+use ark_hip_sys as sys;
+use ark_std::vec::Vec;
+use core::ffi::{c_uint, c_void};
+
+pub struct DeviceMultilinearExtension<F: FftField> {
+    num_vars: usize,
+    evals: DeviceVec<F>,
+}
+/// the reference's name for it
+pub type DenseMultilinearExtension<F> = DeviceMultilinearExtension<F>;
+
+fn rc(code: core::ffi::c_int) -> Result<(), DeviceError> {
+    if code == 0 { Ok(()) } else { Err(DeviceError::Library(code)) }
+}
+fn flat<F: FftField>(point: &[F]) -> Vec<u64> {
+    point.iter().flat_map(|x| sys::limbs(x)).collect()
+}
+
+impl<F: FftField> DeviceMultilinearExtension<F> {
+    /// `from_evaluations_vec` (dense.rs:58-70) for a table already on the device; `Err(Mismatch)` unless it holds
+    /// `2^num_vars` elements.
+    pub fn from_device_vec(num_vars: usize, evals: DeviceVec<F>) -> Result<Self, DeviceError> {
+        if num_vars >= 64 || evals.len() != 1usize << num_vars {
+            return Err(DeviceError::Mismatch);
+        }
+        Ok(Self { num_vars, evals })
+    }
+    /// `from_evaluations_slice`: one upload.
+    pub fn from_evaluations_slice(num_vars: usize, evaluations: &[F]) -> Result<Self, DeviceError> {
+        Self::from_device_vec(num_vars, DeviceVec::from_slice(evaluations)?)
+    }
+    /// the constant zero: `num_vars = 0`, one zero evaluation (dense.rs:422-427)
+    pub fn zero() -> Result<Self, DeviceError> {
+        Self::from_device_vec(0, DeviceVec::zeros(1)?)
+    }
+    /// `num_vars == 0` and a zero evaluation (dense.rs:429-431): one element is downloaded, and only when `num_vars == 0`
+    pub fn is_zero(&self) -> Result<bool, DeviceError> {
+        if self.num_vars != 0 {
+            return Ok(false);
+        }
+        Ok(self.evals.to_vec()?[0].is_zero())
+    }
+    pub fn num_vars(&self) -> usize {
+        self.num_vars
+    }
+    pub fn to_evaluations(&self) -> Result<Vec<F>, DeviceError> {
+        self.evals.to_vec()
+    }
+    pub fn evaluations(&self) -> &DeviceVec<F> {
+        &self.evals
+    }
+    pub fn try_clone(&self) -> Result<Self, DeviceError> {
+        Ok(Self { num_vars: self.num_vars, evals: self.evals.try_clone()? })
+    }
+    /// `MultilinearExtension::fix_variables` (dense.rs:224-257): binds the first `partial_point.len()` variables.
+    pub fn fix_variables(&self, partial_point: &[F]) -> Result<Self, DeviceError> {
+        self.evals.here()?;
+        let dim = partial_point.len();
+        if dim > self.num_vars {
+            return Err(DeviceError::Mismatch);
+        }
+        let mut out = DeviceVec::<F>::alloc(1usize << (self.num_vars - dim))?;
+        let pt = flat(partial_point);
+        rc(unsafe {
+            sys::ark_hip_mle_fix_variables_device(self.evals.field(), self.evals.as_device_ptr(), self.num_vars as c_uint, pt.as_ptr(),
+                                                  dim as c_uint, out.as_device_mut_ptr())
+        })?;
+        Ok(Self { num_vars: self.num_vars - dim, evals: out })
+    }
+    /// `Polynomial::evaluate` (dense.rs:460-465); waits for the one element that comes back.
+    pub fn evaluate(&self, point: &[F]) -> Result<F, DeviceError> {
+        self.evals.here()?;
+        if point.len() != self.num_vars {
+            return Err(DeviceError::Mismatch);
+        }
+        let pt = flat(point);
+        let mut out = [0u64; 4];
+        rc(unsafe {
+            sys::ark_hip_mle_evaluate_device(self.evals.field(), self.evals.as_device_ptr(), self.num_vars as c_uint, pt.as_ptr(),
+                                             out.as_mut_ptr())
+        })?;
+        Ok(sys::from_limbs::<F>(&out))
+    }
+    /// `relabel` (dense.rs:195-199): a new polynomial with the `k` variables from `a` and from `b` exchanged.
+    pub fn relabel(&self, a: usize, b: usize, k: usize) -> Result<Self, DeviceError> {
+        self.evals.here()?;
+        let mut out = DeviceVec::<F>::alloc(self.evals.len())?;
+        rc(unsafe {
+            sys::ark_hip_mle_relabel_device(self.evals.field(), self.evals.as_device_ptr(), self.num_vars as c_uint, a as c_uint,
+                                            b as c_uint, k as c_uint, out.as_device_mut_ptr())
+        })?;
+        Ok(Self { num_vars: self.num_vars, evals: out })
+    }
+    /// `relabel_in_place` (dense.rs:76-92)
+    pub fn relabel_in_place(&mut self, a: usize, b: usize, k: usize) -> Result<(), DeviceError> {
+        self.evals.here()?;
+        let p = self.evals.as_device_mut_ptr();
+        rc(unsafe {
+            sys::ark_hip_mle_relabel_device(self.evals.field(), p as *const c_void, self.num_vars as c_uint, a as c_uint, b as c_uint,
+                                            k as c_uint, p)
+        })
+    }
+    /// `concat` (dense.rs:133-156): the tables one after the other, zero-filled up to the next power of two.
+    pub fn concat(polys: &[&Self]) -> Result<Self, DeviceError> {
+        let total: usize = polys.iter().map(|p| p.evals.len()).sum();
+        let padded = total.next_power_of_two();
+        let mut out = DeviceVec::<F>::alloc(padded)?;
+        let base = out.as_device_mut_ptr() as *mut u8;
+        let mut at = 0usize;
+        for p in polys {
+            p.evals.here()?;
+            rc(unsafe { sys::ark_hip_memcpy_d2d(base.add(at * 32) as *mut c_void, p.evals.as_device_ptr(), p.evals.len() * 32) })?;
+            at += p.evals.len();
+        }
+        if at < padded {
+            rc(unsafe { sys::ark_hip_memset_device(base.add(at * 32) as *mut c_void, 0, (padded - at) * 32) })?;
+        }
+        Ok(Self { num_vars: padded.trailing_zeros() as usize, evals: out })
+    }
+    fn same(&self, other: &Self) -> Result<(), DeviceError> {
+        if self.num_vars == other.num_vars { Ok(()) } else { Err(DeviceError::Mismatch) }
+    }
+    /// `&self + &rhs` (dense.rs:286-305): the constant zero on either side gives a copy of the other operand.
+    pub fn add(&self, rhs: &Self) -> Result<Self, DeviceError> {
+        if rhs.is_zero()? {
+            return self.try_clone();
+        }
+        if self.is_zero()? {
+            return rhs.try_clone();
+        }
+        self.same(rhs)?;
+        let mut out = self.evals.try_clone()?;
+        out.add_assign_pointwise(&rhs.evals)?;
+        Ok(Self { num_vars: self.num_vars, evals: out })
+    }
+    /// `-self` (dense.rs:329-338)
+    pub fn neg(&self) -> Result<Self, DeviceError> {
+        let mut out = self.evals.try_clone()?;
+        out.negate()?;
+        Ok(Self { num_vars: self.num_vars, evals: out })
+    }
+    /// `&self - &rhs` = `self + (-rhs)` (dense.rs:348-354)
+    pub fn sub(&self, rhs: &Self) -> Result<Self, DeviceError> {
+        self.add(&rhs.neg()?)
+    }
+    fn scaled(&self, k: &F) -> Result<Self, DeviceError> {
+        let mut out = self.evals.try_clone()?;
+        out.scale(k)?;
+        Ok(Self { num_vars: self.num_vars, evals: out })
+    }
+    /// `&self * &scalar` (dense.rs:376-392): times zero gives `zero()`.
+    pub fn mul_scalar(&self, scalar: &F) -> Result<Self, DeviceError> {
+        if scalar.is_zero() {
+            return Self::zero();
+        }
+        self.scaled(scalar)
+    }
+    /// `self += (f, other)` (dense.rs:319-327) in one pass over the two tables: no scaled temporary.
+    pub fn add_assign_scaled(&mut self, f: &F, other: &Self) -> Result<(), DeviceError> {
+        if other.is_zero()? || (other.num_vars == 0 && f.is_zero()) {
+            return Ok(()); // f * other is the constant zero
+        }
+        if self.is_zero()? {
+            *self = other.scaled(f)?;
+            return Ok(());
+        }
+        self.same(other)?;
+        self.evals.here()?;
+        let k = sys::limbs(f);
+        let n = self.evals.len();
+        let p = self.evals.as_device_mut_ptr();
+        rc(unsafe { sys::ark_hip_fr_axpy_device(self.evals.field(), p as *const c_void, k.as_ptr(), other.evals.as_device_ptr(), p, n) })
+    }
+}
