@@ -347,16 +347,21 @@ def test_batch_mul_window_geometries(cname, window, monkeypatch):
     t.free()
 
 
-@pytest.mark.parametrize("cname", ["BN254_G1", "BLS12_381_G1", "BLS12_377_G1"])
-def test_batch_mul_unreduced_scalar_hits_the_doubling_branch(cname):
+def unreduced_doubling_scalar(r):
     # "any BigInt<4> is multiplied exactly": s = d 2^252 + (d 2^252 - r) with 0 <= d 2^252 - r < 2^252 makes the sum of
     # the lower 21 rows EQUAL to the top row's entry (d 2^252 g = (d 2^252 - r) g) -- the addition must double.
-    cid = O.CID[cname]
-    fid = sf(cid)
-    r = S.R[O.FIELDS[fid]]
     d = next(d for d in range(1, 16) if 0 <= (d << 252) - r < (1 << 252))
     s = (d << 252) + ((d << 252) - r)
     assert s < (1 << 256)
+    return s
+
+
+@pytest.mark.parametrize("cname", ["BN254_G1", "BLS12_381_G1", "BLS12_377_G1"])
+def test_batch_mul_unreduced_scalar_hits_the_doubling_branch(cname):
+    cid = O.CID[cname]
+    fid = sf(cid)
+    r = S.R[O.FIELDS[fid]]
+    s = unreduced_doubling_scalar(r)
     base = O.scalar_mul(cid, O.generator(cid), np.array([0x5EED, 0, 0, 0], dtype=np.uint64))
     sc = np.stack([P.to_limbs(s, 4), P.to_limbs(5, 4), P.to_limbs(s, 4)]).astype(np.uint64)
     baff = O.to_affine(cid, base)
