@@ -7,6 +7,7 @@
 #include "capi_hostmath.hpp"
 #include "capi_cache.hpp"
 #include "lazytest_api.hpp"
+#include "relaxtest_api.hpp"
 using namespace arkhip;
 using namespace arkhip::capi;
 
@@ -28,6 +29,16 @@ ARK_DECL_LAZYTEST_ACC(BN254_G1) ARK_DECL_LAZYTEST_ACC(BLS12_381_G1) ARK_DECL_LAZ
 ARK_DECL_LAZYTEST_ACC(BLS12_377_G2) ARK_DECL_LAZYTEST_ACC(BLS12_381_G2)
 #undef ARK_DECL_LAZYTEST_RAW
 #undef ARK_DECL_LAZYTEST_ACC
+#define ARK_DECL_RELAXTEST_RAW(NAME) int test_relaxed_raw_op_##NAME(int op, const void* d_in, void* d_out, size_t n, hipStream_t s);
+#define ARK_DECL_RELAXTEST_ACC(NAME) \
+  int test_relaxed_acc_op_##NAME(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s);
+ARK_DECL_RELAXTEST_RAW(BN254_G1) ARK_DECL_RELAXTEST_RAW(BLS12_381_G1) ARK_DECL_RELAXTEST_RAW(BLS12_377_G1)
+ARK_DECL_RELAXTEST_RAW(BLS12_377_G2) ARK_DECL_RELAXTEST_RAW(BLS12_381_G2)
+ARK_DECL_RELAXTEST_RAW(BN254_FR) ARK_DECL_RELAXTEST_RAW(BLS12_381_FR) ARK_DECL_RELAXTEST_RAW(BLS12_377_FR)
+ARK_DECL_RELAXTEST_ACC(BN254_G1) ARK_DECL_RELAXTEST_ACC(BLS12_381_G1) ARK_DECL_RELAXTEST_ACC(BLS12_377_G1)
+ARK_DECL_RELAXTEST_ACC(BLS12_377_G2) ARK_DECL_RELAXTEST_ACC(BLS12_381_G2)
+#undef ARK_DECL_RELAXTEST_RAW
+#undef ARK_DECL_RELAXTEST_ACC
 }  // namespace arkhip
 namespace {
 typedef int (*lazy_raw_fn)(int, int, int, const void*, void*, size_t, hipStream_t);
@@ -53,6 +64,33 @@ elementwise_fn lazy_acc_fn_of(int curve) {
     case 2: return test_lazy_acc_op_BLS12_377_G1;
     case 3: return test_lazy_acc_op_BLS12_377_G2;
     case 4: return test_lazy_acc_op_BLS12_381_G2;
+#endif
+  }
+  return nullptr;
+}
+typedef int (*relaxed_raw_fn)(int, const void*, void*, size_t, hipStream_t);
+// Fp ops: the unit of the field (a base field through the G1 curve over it); Fp2 / Fp2Half ops: the G2 unit over the base field
+relaxed_raw_fn relaxed_raw_fn_of(int field, bool pair) {
+  switch (field) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_FQ: return pair ? nullptr : test_relaxed_raw_op_BN254_G1;
+    case ARK_HIP_BN254_FR: return pair ? nullptr : test_relaxed_raw_op_BN254_FR;
+    case ARK_HIP_BLS12_381_FQ: return pair ? test_relaxed_raw_op_BLS12_381_G2 : test_relaxed_raw_op_BLS12_381_G1;
+    case ARK_HIP_BLS12_381_FR: return pair ? nullptr : test_relaxed_raw_op_BLS12_381_FR;
+    case ARK_HIP_BLS12_377_FQ: return pair ? test_relaxed_raw_op_BLS12_377_G2 : test_relaxed_raw_op_BLS12_377_G1;
+    case ARK_HIP_BLS12_377_FR: return pair ? nullptr : test_relaxed_raw_op_BLS12_377_FR;
+#endif
+  }
+  return nullptr;
+}
+elementwise_fn relaxed_acc_fn_of(int curve) {
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case 0: return test_relaxed_acc_op_BN254_G1;
+    case 1: return test_relaxed_acc_op_BLS12_381_G1;
+    case 2: return test_relaxed_acc_op_BLS12_377_G1;
+    case 3: return test_relaxed_acc_op_BLS12_377_G2;
+    case 4: return test_relaxed_acc_op_BLS12_381_G2;
 #endif
   }
   return nullptr;
@@ -194,6 +232,37 @@ int ark_hip_test_lazy_acc_op(int curve, int kind, const void* acc, const void* o
   const size_t rbytes = n * (kind == ACC_TO_BUCKET ? 4 * fb : slot);
   if (bbytes && !other) return ARK_HIP_ERR_ARG;
   return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, lazy_acc_fn_of(curve), kind, n);
+}
+
+int ark_hip_test_relaxed_raw_op(int field, int op, const uint32_t* in, uint32_t* out, size_t n) {
+  using namespace arkhip::relaxtest;
+  if (field < 0 || field > 5 || !in || !out) return ARK_HIP_ERR_ARG;
+  const Row* row = row_of(op);
+  if (!row || !served(op, field)) return ARK_HIP_ERR_ARG;
+  const bool pair = row->unit != U_FP;
+  relaxed_raw_fn fn = relaxed_raw_fn_of(field, pair);
+  if (!fn || (pair && (n & 1))) return ARK_HIP_ERR_ARG;
+  const size_t N = (field == ARK_HIP_BLS12_381_FQ || field == ARK_HIP_BLS12_377_FQ) ? 12 : 8;
+  const size_t ibytes = n * (size_t)row->arity * N * 4, obytes = n * (N + 1) * 4;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) return 0;
+  if (c->stage_a.ensure(ibytes) || c->stage_c.ensure(obytes)) return ARK_HIP_ERR_NOMEM;
+  ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, ibytes, hipMemcpyHostToDevice, c->stream));
+  const int rc = fn(op, c->stage_a.p, c->stage_c.p, n, c->stream);
+  if (rc) return rc == -1 ? ARK_HIP_ERR_ARG : rc;
+  ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, obytes, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int ark_hip_test_relaxed_acc_op(int curve, int kind, const void* acc, const void* other, void* out, size_t n) {
+  using namespace arkhip::relaxtest;
+  if (curve < 0 || curve > 4 || !acc || !out || kind < 0 || kind >= ACC_KINDS) return ARK_HIP_ERR_ARG;
+  const size_t fb = (size_t)CURVES[curve].fe_words * 8;
+  const size_t bbytes = kind == ACC_MADD ? n * 2 * fb : kind == ACC_ADD ? n * 4 * fb : 0;
+  if (bbytes && !other) return ARK_HIP_ERR_ARG;
+  return run_elementwise(n * 4 * fb, bbytes, n * 4 * fb, acc, bbytes ? other : nullptr, out, relaxed_acc_fn_of(curve), kind, n);
 }
 
 static int host_fold_dispatch(int curve, const uint64_t* parts, int windows, int nbits, u32 l0, const int* widths, uint64_t* out_xyz) {

@@ -903,7 +903,7 @@ struct Fp2Half {
     return q;
   }
   // relaxed product: operands < 2p; the sum of products is < (4 + 4 NEG_BETA) p^2... (24 p^2 for beta = -5 over
-  // BLS12-377, 8 p^2 for beta = -1 over BLS12-381): (sum + m p) / R < 2p for both fields (p/R = 0.0063, 0.102)
+  // BLS12-377, 8 p^2 for beta = -1 over BLS12-381): (sum + m p) / R < 2p for both fields (p/R = 0.0066, 0.102)
   ARK_DEV static Fp2Half mul_r(const Fp2Half& a, const Fp2Half& b) {
     static_assert((P::P[N - 1] >> 29) == 0, "sop2_r without a final subtraction needs 8p <= R");
     const B pa = partner(a.v), pb = partner(b.v);

@@ -3,6 +3,7 @@
 #include "devops.cuh"
 #include "testops.cuh"
 #include "lazytest.cuh"
+#include "relaxtest.cuh"
 #include "internal.hpp"
 #ifndef ARK_TEST_CURVE
 #error "compile with -DARK_TEST_CURVE=BLS12_381_G1 (or another curve of curves.cuh)"
@@ -24,5 +25,14 @@ int ARK_CAT(test_lazy_raw_op_, ARK_TEST_CURVE)(int op, int k, int h, const void*
 }
 int ARK_CAT(test_lazy_acc_op_, ARK_TEST_CURVE)(int kind, const void* acc, const void* other, void* out, size_t n, hipStream_t s) {
   return lazytest::lazy_acc_op_launch<ARK_TEST_CURVE>(kind, acc, other, out, n, s);
+}
+// raw-limb hooks of the relaxed saturated-limb arithmetic (relaxtest.cuh): a G1 unit serves the Fp ops of its base field, a G2
+// unit the Fp2 / Fp2Half ops over it
+int ARK_CAT(test_relaxed_raw_op_, ARK_TEST_CURVE)(int op, const void* in, void* out, size_t n, hipStream_t s) {
+  typedef ARK_TEST_CURVE::FA FA;
+  return relaxtest::relaxed_raw_op_launch<FA::P, relaxtest::NegBetaOf<FA>::v>(op, in, out, n, s);
+}
+int ARK_CAT(test_relaxed_acc_op_, ARK_TEST_CURVE)(int kind, const void* acc, const void* other, void* out, size_t n, hipStream_t s) {
+  return relaxtest::relaxed_acc_op_launch<ARK_TEST_CURVE>(kind, acc, other, out, n, s);
 }
 }  // namespace arkhip

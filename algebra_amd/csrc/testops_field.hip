@@ -1,7 +1,8 @@
-// The raw-limb TEST kernels of one scalar field (lazytest.cuh: the FpL ops and the Fft29 ops of the carry-free FFT pass): compiled
-// once per field with -DARK_TEST_FIELD=<name> and linked into libark_hip_test.so only.
+// The raw-limb TEST kernels of one scalar field (lazytest.cuh: the FpL ops and the Fft29 ops of the carry-free FFT pass;
+// relaxtest.cuh: the relaxed saturated-limb ops of the default FFT pass): compiled once per field with -DARK_TEST_FIELD=<name> and linked into libark_hip_test.so only.
 #define ARK_LAZYTEST_FFT 1
 #include "lazytest.cuh"
+#include "relaxtest.cuh"
 #ifndef ARK_TEST_FIELD
 #error "compile with -DARK_TEST_FIELD=BLS12_381_FR (or another scalar field of params.hpp)"
 #endif
@@ -10,5 +11,8 @@
 namespace arkhip {
 int ARK_CAT(test_lazy_raw_op_, ARK_TEST_FIELD)(int op, int k, int h, const void* in, void* out, size_t n, hipStream_t s) {
   return lazytest::lazy_raw_op_launch<ARK_TEST_FIELD, true, void>(op, k, h, in, out, n, s);
+}
+int ARK_CAT(test_relaxed_raw_op_, ARK_TEST_FIELD)(int op, const void* in, void* out, size_t n, hipStream_t s) {
+  return relaxtest::relaxed_raw_op_launch<ARK_TEST_FIELD, 0>(op, in, out, n, s);
 }
 }  // namespace arkhip

@@ -526,6 +526,16 @@ int ark_hip_test_lazy_raw_op(int field, int op, int k, int h, const uint32_t* in
  * acc = +/- 2 base, 4 acc += stored bucket (other: canonical XYZZ), 5 acc += parked accumulator, 6 acc = 2 acc,
  * 7 from_bucket (acc: canonical XYZZ), 8 to_bucket (out: canonical XYZZ). */
 int ark_hip_test_lazy_acc_op(int curve, int kind, const void* acc, const void* other, void* out, size_t n);
+/* The RELAXED arithmetic on saturated 32-bit limbs (csrc/fp.cuh: residues in [0, 2p), Fp, Fp2, Fp2Half) ONE OP AT A TIME ON RAW
+ * LIMBS: lane t reads `arity` slots of N words (N = 8 or 12: whatever representative the test chose) at in[(t * arity + j) * N]
+ * and writes N + 1 words at out[t * (N + 1)]: the limbs as the function returns them, then its boolean result.  The Fp2 and
+ * Fp2Half ops (op >= 20; field = BLS12-381 / BLS12-377 Fq) own a lane pair per element: even lane c0, odd lane c1, n even.  op,
+ * arity and the fields an op is served on are THE TABLE of csrc/relaxtest_api.hpp; anything else is ARK_HIP_ERR_ARG. */
+int ark_hip_test_relaxed_raw_op(int field, int op, const uint32_t* in, uint32_t* out, size_t n);
+/* The XYZZ additions on relaxed residues (csrc/ec.cuh) over the field of the bucket kernels (Fp; G2: Fp2Half, a lane pair per
+ * point), the accumulator in and out as raw limbs (x | y | zz | zzz).  kind (csrc/relaxtest_api.hpp AccKind): 0 xyzz_madd_relaxed
+ * (other: x2 | y2, y2 as given), 1 xyzz_add_relaxed (other: XYZZ), 2 xyzz_canonical. */
+int ark_hip_test_relaxed_acc_op(int curve, int kind, const void* acc, const void* other, void* out, size_t n);
 
 #endif /* ARK_HIP_TEST_HOOKS */
 

@@ -84,3 +84,23 @@ def lazy_acc_op(curve, kind, acc, other, out_words):
     out = np.zeros((n, out_words), dtype=np.uint32)
     check(test_lib().ark_hip_test_lazy_acc_op(curve, kind, _p(acc), _p(o), _p(out), n), "test_lazy_acc_op")
     return out
+
+
+def relaxed_raw_op(field, op, rows, limbs):
+    """One op of the relaxed saturated-limb arithmetic on RAW limbs (csrc/relaxtest_api.hpp): rows (n lanes, arity * N words)
+    -> (n, N + 1) words, the last one the op's boolean result.  Returns (status, out): an op outside THE TABLE, or not served on
+    this field, comes back as ARK_HIP_ERR_ARG."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint32)
+    n = rows.shape[0]
+    out = np.zeros((n, limbs + 1), dtype=np.uint32)
+    rc = test_lib().ark_hip_test_relaxed_raw_op(field, op, _p(rows), _p(out), n)
+    return rc, out
+
+
+def relaxed_acc_op(curve, kind, acc, other):
+    """xyzz_madd_relaxed / xyzz_add_relaxed / xyzz_canonical with the XYZZ accumulator as raw uint32 limbs on both sides."""
+    acc = np.ascontiguousarray(acc, dtype=np.uint32)
+    o = None if other is None else np.ascontiguousarray(other, dtype=np.uint32)
+    out = np.zeros_like(acc)
+    check(test_lib().ark_hip_test_relaxed_acc_op(curve, kind, _p(acc), _p(o), _p(out), acc.shape[0]), "test_relaxed_acc_op")
+    return out

@@ -18,6 +18,11 @@ def _field_inputs(fid, n, seed):
     rng = np.random.default_rng(seed)
     vals = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, P.from_limbs(O.field_const(fid, 1)),
             (1 << (p.bit_length() - 1)), (1 << (p.bit_length() - 1)) - 1]
+    # limb shapes (32-bit limbs): every low limb 0xffffffff under the largest top limb that stays below p, under a zero top limb,
+    # and one limb at 0xffffffff with the rest zero
+    s = 32 * (2 * words - 1)
+    vals += [(((p >> s) - 1) << s) | ((1 << s) - 1), (1 << s) - 1] + [0xFFFFFFFF << (32 * i) for i in range(2 * words - 1)]
+    assert all(0 <= v < p for v in vals)
     vals = [v % p for v in vals]
     while len(vals) < n:
         vals.append(int.from_bytes(rng.bytes(8 * words + 8), "little") % p)
