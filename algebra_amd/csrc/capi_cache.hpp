@@ -260,7 +260,7 @@ inline void cache_forget(Context* c, int curve, const void* host, size_t n, bool
 inline void cache_maybe_prepare(Context* c, BaseCacheEntry& e) {
   if (c->auto_prepare <= 0 || e.prepared || e.no_prepare || e.hits < (unsigned)c->auto_prepare) return;
   if (e.pins == 0) {   // transparent entries: the table counts against the budget
-    const MsmPlan pl = msm_make_plan(e.n, msm_scalar_bits(e.curve), msm_mul_cost(e.curve), true, msm_lazy28(e.curve));
+    const MsmPlan pl = msm_default_plan(e.curve, e.n, msm_scalar_bits(e.curve), true, nullptr);
     const long long table = (long long)pl.W * (long long)e.n * CURVES[e.curve].fe_words * 16;
     const void* host = e.host;
     const size_t n = e.n;

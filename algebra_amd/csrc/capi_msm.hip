@@ -281,8 +281,7 @@ int ark_hip_msm_cache_hash_stats(uint64_t out[4]) {
 // the window plan the library would use (host arithmetic only: no GPU needed)
 int ark_hip_msm_plan(int curve, size_t n, int prepared, int* window_bits, int* windows) {
   if (curve < 0 || curve > 4) return ARK_HIP_ERR_ARG;
-  const MsmPlan pl = msm_make_plan(n ? n : 1, msm_scalar_bits(curve), msm_mul_cost(curve), prepared != 0, msm_lazy28(curve), nullptr,
-                                   prepared == 0 && msm_lazy_enabled());
+  const MsmPlan pl = msm_default_plan(curve, n ? n : 1, msm_scalar_bits(curve), prepared != 0, nullptr);
   if (window_bits) *window_bits = pl.c;
   if (windows) *windows = pl.W;
   return 0;
@@ -295,7 +294,7 @@ int ark_hip_msm_plan_widths(int curve, size_t n, uint32_t max_bits, const uint32
   MsmWidths w{};
   w.max_bits = max_bits;
   for (int k = 0; k < MSM_WIDTH_CLASSES; k++) w.count[k] = counts[k];
-  const MsmPlan pl = msm_plan_for_widths(n ? n : 1, msm_scalar_bits(curve), msm_mul_cost(curve), msm_lazy28(curve), w);
+  const MsmPlan pl = msm_plan_for_widths(curve, n ? n : 1, w);
   if (window_bits) *window_bits = pl.c;
   if (windows) *windows = pl.W;
   return 0;
@@ -328,7 +327,7 @@ int ark_hip_msm_bases_prepare_device(int curve, const void* d_bases, size_t n, a
   pb->curve = curve;
   pb->logical = c->logical;
   pb->n = n;
-  pb->plan = msm_make_plan(n ? n : 1, msm_scalar_bits(curve), msm_mul_cost(curve), true);
+  pb->plan = msm_default_plan(curve, n ? n : 1, msm_scalar_bits(curve), true, nullptr);
   const size_t row = n * (size_t)CURVES[curve].fe_words * 16;
   if (n) {
     if ((size_t)pb->plan.W * n >= (1ull << 31) || pb->table.ensure((size_t)pb->plan.W * row)) {

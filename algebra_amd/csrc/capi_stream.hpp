@@ -106,13 +106,10 @@ inline int msm_stream(Context* c, int curve, const void* d_bases, const uint64_t
     // measures exactly); the layout stays the full-width one -- a sample cannot bound the widest scalar
     MsmWidths widths{};
     bool skewed = false;
-    static const bool probe_on = [] {
-      const char* e = getenv("ARK_HIP_MSM_PROBE");
-      return !(e && atoi(e) == 0);
-    }();
-    if (probe_on && scalars && n >= ((size_t)1 << 19) && msm_sample_widths_dispatch(curve, scalars, n, mont, &widths) == 0)
+    const MsmKnobs knobs = msm_knobs();
+    if (knobs.probe && scalars && n >= ((size_t)1 << 19) && msm_sample_widths_dispatch(curve, scalars, n, mont, &widths) == 0)
       skewed = msm_widths_skewed(widths);
-    plan = msm_make_plan(n, msm_scalar_bits(curve), msm_mul_cost(curve), false, msm_lazy28(curve), skewed ? &widths : nullptr);
+    plan = msm_default_plan(curve, n, msm_scalar_bits(curve), false, skewed ? &widths : nullptr, knobs, /*streamed=*/true);
     if ((size_t)step * (size_t)plan.W >= (1ull << 32)) return ARK_HIP_ERR_SIZE;
     const size_t need = plan.nbuckets() * (size_t)CURVES[curve].fe_words * 32;  // XYZZ: four field elements
     if (c->piece_buckets.cap < need) {

@@ -288,6 +288,17 @@ int ark_hip_test_msm_host_fold_l0(int curve, const uint64_t* parts, int windows,
     return ARK_HIP_ERR_ARG;
   return host_fold_dispatch(curve, parts, windows, nbits, (u32)l0, widths, out_xyz);
 }
+// Test hook (host only, no device): the bucket reduction's geometry for a plan given as (c, W, narrow, shared), with every
+// knob at its default (msm_plan.hpp: msm_reduce_geometry)
+int ark_hip_test_msm_reduce_geometry(int curve, int c, int W, int narrow, int shared, size_t resident_lanes, uint32_t out[12]) {
+  if (curve < 0 || curve > 4 || !out || c < 2 || c > 26 || W < 1 || W > 256 || narrow < 0 || narrow > W) return ARK_HIP_ERR_ARG;
+  const MsmPlan pl{c, W, narrow, (size_t)W << (c - 1), shared != 0};
+  const MsmReduceGeom g = msm_reduce_geometry(pl, msm_lanes_per_point(curve), msm_scalar_bits(curve), resident_lanes, MsmKnobs{});
+  const uint32_t v[12] = {g.L0, (uint32_t)g.m, (uint32_t)g.mn, (uint32_t)g.nbits, g.Q, g.two_digit ? 1u : 0u, g.d2, g.rows2,
+                          (uint32_t)g.nsum2, g.chunk, g.nchunks, (uint32_t)g.npairs};
+  for (int k = 0; k < 12; k++) out[k] = v[k];
+  return 0;
+}
 // Test hook (host only, no device): the verified cache's tag of `words` u64 words -- tests/test_capi_host.py checks that
 // edits the round-4 hash could not see (a two-word edit built from its published constants) change it.
 int ark_hip_test_base_hash(const uint64_t* p, size_t words, uint64_t out[2]) {

@@ -36,6 +36,7 @@
 #include "ec28.cuh"
 #include "lazyk.cuh"
 #include "msm_sort.cuh"
+#include "msm_plan.hpp"
 
 namespace arkhip {
 
@@ -49,12 +50,6 @@ namespace arkhip {
   } while (0)
 
 static constexpr u32 KEY_NONE = 0xffffffffu;
-
-// Window widths: W windows of c bits, except that the top `narrow` windows are c-1 bits wide, so that the widths
-// add up to the scalar's bit length exactly and no window is left with only a few significant bits.
-__host__ __device__ __forceinline__ int msm_window_width(int w, int c, int W, int narrow) {
-  return w >= W - narrow ? c - 1 : c;
-}
 
 // ---- K1: signed-digit recoding -------------------------------------------------------------------
 // The magnitude the digits are taken from: v = min(s, r - s) of scalar i (canonical value; from Montgomery form first
@@ -121,12 +116,7 @@ __host__ __device__ __forceinline__ u32 msm_scalar_magnitude(const u32* __restri
 // windows only: planned for n full-width scalars they leave most windows empty and most of the 2^(c-1) W buckets -- whose
 // reduction does not shrink with the entries -- unused.  The reference sorts the scalars into the same classes and runs
 // one MSM per class (msm_signed, variable_base/mod.rs:251-336); here ONE pipeline runs, planned for the measured classes.
-static constexpr int MSM_WIDTH_CLASSES = 9;
-static constexpr int MSM_WIDTH_TOP[MSM_WIDTH_CLASSES] = {0, 1, 8, 16, 32, 64, 128, 192, 256};   // class k: TOP[k-1] < b <= TOP[k]
-struct MsmWidths {
-  u32 max_bits;
-  u32 count[MSM_WIDTH_CLASSES];
-};
+// (MSM_WIDTH_TOP, MsmWidths: msm_plan.hpp)
 // chunk > 0 (the exact pass, stride 1): workgroup b owns the contiguous scalars [b chunk, (b + 1) chunk) and also leaves the
 // number of NON-ZERO ones among them in nz_counts[b] -- what the zero-scalar compaction below needs, for free
 template <class SP>
@@ -271,18 +261,6 @@ void msm_sample_widths_host(const void* h_scalars, size_t n, int mont, MsmWidths
   }
   for (int k = 0; k < MSM_WIDTH_CLASSES; k++) out->count[k] = (u32)((double)cnt[k] * (double)n / (double)seen);
 }
-// plan of a plain MSM whose width classes were MEASURED over all n scalars (msm_enqueue after K0; ark_hip_msm_plan_widths):
-// windows for the widest scalar unless fewer than 8 bits would be saved, window size from the digits the classes have
-static inline struct MsmPlan msm_plan_for_widths(size_t n, int field_bits, double mul_cost, bool lazy28, const MsmWidths& w);
-// true when the classes say "not n uniform full-width scalars": fewer than half wider than 128 bits
-static inline bool msm_widths_skewed(const MsmWidths& w) {
-  u64 seen = 0, wide = 0;
-  for (int k = 0; k < MSM_WIDTH_CLASSES; k++) {
-    seen += w.count[k];
-    if (MSM_WIDTH_TOP[k] > 128) wide += w.count[k];
-  }
-  return 2 * wide < seen;
-}
 
 template <class SP>
 __global__ void __launch_bounds__(256) msm_digits_kernel(const u32* __restrict__ scalars, u32 n, int mont, int c,
@@ -358,7 +336,6 @@ __global__ void __launch_bounds__(256) msm_digits_small_kernel(const unsigned ch
 }
 
 // ---- K2: exclusive scan (three small kernels) --------------------------------------------------
-static constexpr int SCAN_TILE = 2048;  // elements per block (256 threads x 8)
 
 static __global__ void __launch_bounds__(256) scan_block_sums(const u32* __restrict__ in, size_t m, u32* __restrict__ sums) {
   __shared__ u32 sh[256];
@@ -476,8 +453,6 @@ static inline void scan_exclusive(const u32* in, size_t m, u32* sums, u32* offse
 // longest bucket (Poisson loads: ~30% of the lanes' time idle at mean 32).  Counting sort of bucket
 // ids by load class (load >> shift, clamped to 255), descending; per-block LDS histograms keep the
 // global atomics out of it.
-static constexpr int ORDER_TILE = 2048;
-static constexpr int ORDER_BINS = 256;
 // A lane owns `wsum` runs (one per window when the windows share a bucket set, else 1) `wstride` slots apart.
 __device__ __forceinline__ u32 msm_lane_load(const u32* __restrict__ offsets, size_t g, int wsum, size_t wstride) {
   u32 cnt = 0;
@@ -875,15 +850,9 @@ __global__ void __launch_bounds__(128) msm_table_step_kernel(const char* __restr
 // many equal scalars) would pin one lane for its whole length.  Buckets above `thresh` are skipped by
 // the lane-per-bucket kernel, cut into chunks of HEAVY_CHUNK entries, each chunk summed by one
 // wave (64 lanes striding + LDS tree), and the chunk partials combined per bucket.
-#ifndef ARK_HEAVY_CHUNK
-#define ARK_HEAVY_CHUNK 1024          // entries per wave of msm_heavy_partial_kernel: 16 serial additions per lane + the wave's
-                                      // LDS tree (2048 / 64 lanes before: bool 1.85 -> 1.71 ms, u8 1.42 -> 1.21, msm_u8 1.20 -> 0.96
-                                      // at 2^20 with the 128-lane combine below; 512 / 256 measured between the two -- profiles/r4_heavy_geometry_ab.txt)
-#endif
 #ifndef ARK_HEAVY_COMBINE_THREADS
 #define ARK_HEAVY_COMBINE_THREADS 128 // workgroup of msm_heavy_combine_kernel: one per heavy run
 #endif
-static constexpr u32 HEAVY_CHUNK = ARK_HEAVY_CHUNK;
 struct HeavyEntry { u32 bucket, first_item, items; };
 // Entries per chunk for a window group with `total` sorted entries: the wave's tree (6 full additions) and the combine
 // kernel's serial walk over a run's partials are fixed costs per chunk, so large inputs take longer chunks -- a 2^23-entry
@@ -940,60 +909,13 @@ static __global__ void __launch_bounds__(256) msm_find_heavy_kernel(const u32* _
 }
 
 // Point additions of the reduction / heavy-run kernels.  `Pt` is a point as it lives in memory (canonical XYZZ over the
-// accumulate field C::FA), `Acc` the form it is summed in:
-//   * saturated limbs (BN254, the Fp2 curves): Acc = Pt on relaxed residues where the field allows it, one element per
-//     lane (Fp) or per lane PAIR (Fp2Half; index arithmetic below is in "slots" = lanes / LANES, every branch uniform
-//     over a pair);
-//   * carry-free 28-bit limbs (the Fp384 G1 curves, C::LAZY_A): Acc = XYZZL, memory operands enter by the shifted
-//     repack (ec28.cuh: xyzz_add_lazy) -- the full addition's 10 products + 2 squares + one two-product sum at the
-//     28-bit product's rate instead of 12 + 2 + 1.5 at the saturated one's.
-#ifndef ARK_REDUCE_LAZY
-#define ARK_REDUCE_LAZY 1   // 0: the reduction / heavy-run kernels of the Fp384 G1 curves on saturated limbs too (A/B builds)
-#endif
-template <class C, bool LAZY = (C::LAZY_A && ARK_REDUCE_LAZY != 0)>
-struct AccOps;
-
+// accumulate field C::FA), `Acc` the form it is summed in: carry-free limbs on every served curve (C::LAZY_A) -- one element
+// per lane (G1) or per lane PAIR (G2; index arithmetic below is in "slots" = lanes / LANES, every branch uniform over a
+// pair).  Memory operands enter by the shifted repack (ec28.cuh: xyzz_add_lazy) -- the full addition's 10 products + 2
+// squares + one two-product sum at the 28-bit product's rate instead of 12 + 2 + 1.5 at the saturated one's.
 template <class C>
-struct AccOps<C, false> {
-  typedef typename C::FA F;
-  typedef XYZZ<F> Pt;
-  typedef Pt Acc;
-  static constexpr u32 LANES = F::LANES;
-  static constexpr size_t ACC_BYTES = Pt::BYTES;   // one accumulator parked in LDS
-  ARK_DEV static Acc zero() { return Pt::zero(); }
-  ARK_DEV static Acc from_pt(const Pt& p) { return p; }
-  // acc += (+-) the non-identity base p gathered from `src` (neg: the digit's sign)
-  ARK_DEV static void madd(Acc& acc, const Affine<F>& p, bool neg, const char*) {
-    if constexpr (C::RELAXED_A) xyzz_madd_relaxed<F>(acc, p.x, neg ? F::neg_r(p.y) : p.y);   // 2p - y: a multiplication operand
-    else xyzz_madd<F>(acc, p.x, F::cond_neg(p.y, neg));
-  }
-  ARK_DEV static void add(Acc& acc, const Pt& b) {
-    if constexpr (C::RELAXED_A) xyzz_add_relaxed<F>(acc, b);
-    else xyzz_add<F>(acc, b);
-  }
-  ARK_DEV static void add_acc(Acc& acc, const Acc& b) { add(acc, b); }
-  ARK_DEV static Pt fin(const Acc& a) {  // canonical form for memory
-    if constexpr (C::RELAXED_A) return xyzz_canonical<F>(a);
-    else return a;
-  }
-  ARK_DEV static void park(const Acc& a, char* slot) { a.store(slot); }
-  ARK_DEV static Acc unpark(const char* slot) { return Pt::load(slot); }
-  // sum over the `width` slots of an LDS array of per-slot partials (width a power of two); result in slot 0's acc
-  ARK_DEV static void tree(Acc& acc, char* sh, u32 slot, u32 width) {
-    park(acc, sh + (size_t)slot * ACC_BYTES);
-    __syncthreads();
-    for (u32 o = width / 2; o > 0; o >>= 1) {
-      if (slot < o) {
-        add_acc(acc, unpark(sh + (size_t)(slot + o) * ACC_BYTES));
-        park(acc, sh + (size_t)slot * ACC_BYTES);
-      }
-      __syncthreads();
-    }
-  }
-};
-
-template <class C>
-struct AccOps<C, true> {
+struct AccOps {
+  static_assert(C::LAZY_A, "the reduction and heavy-run kernels sum on the curve's carry-free form");
   typedef LazyK<C> K;            // carry-free limbs: ec28.cuh (one lane per point) or ec28x2.cuh (G2: one lane pair)
   typedef typename K::FM F;
   typedef XYZZ<F> Pt;
@@ -1379,250 +1301,9 @@ __global__ void __launch_bounds__(64) msm_sum_chunks_kernel(const char* __restri
   if (slot == 0) Ops::fin(acc).store(out + (size_t)t * Pt::BYTES);
 }
 
-// ---- host-side plan / workspace -----------------------------------------------------------------
-struct MsmPlan {
-  int c;          // window bits (widest windows)
-  int W;          // windows
-  int narrow;     // the top `narrow` windows are c-1 bits wide, so that the widths sum to bits exactly and no
-                  // window is left with only a few significant bits (0: uniform widths)
-  size_t nb;      // bucket slots of the sort = W << (c-1)
-  bool shared;    // prepared base set: the W windows share one set of 2^(c-1) buckets
-  unsigned parts = 0;   // small plain MSMs: lanes per (window, bucket) run the accumulate kernel should use (0: its own rule)
-  size_t nbuckets() const { return shared ? ((size_t)1 << (c - 1)) : nb; }
-  int red_windows() const { return shared ? 1 : W; }
-};
-
-// relative cost of one mixed addition (Fp384 G1 = 1): Fp256 ~0.5; Fp2 over Fp384 2.7 (measured: 0.49 ns against
-// 0.18 ns per addition at full occupancy)
-static inline double msm_mul_cost(int curve_id) { return curve_id == 0 ? 0.5 : (curve_id >= 3 ? 2.7 : 1.0); }
-// curves whose additions run on 28-bit limbs (C::LAZY_A: the Fp384 G1 curves)
-static inline bool msm_lazy28(int curve_id) { return curve_id <= 2; }   // (BN254 since round 4: 9 x 29 bits -- the device path plans with C::LAZY_A)
-// ARK_HIP_MSM_LAZY=0: the saturated kernels on those curves too (A/B measurements)
-static inline bool msm_lazy_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("ARK_HIP_MSM_LAZY");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-static inline int msm_scalar_bits(int curve_id) {
-  switch (curve_id) {
-    case 0: return BN254_FR::BITS;
-    case 1: case 4: return BLS12_381_FR::BITS;
-    default: return BLS12_377_FR::BITS;
-  }
-}
-
-static inline void msm_window_layout(int c, int bits, int* W, int* narrow) {
-  // signed digits of a (bits-1)-bit value (after the s -> r-s fold) need bits significant positions in total
-  // (the top window is not recoded and must keep one spare bit).  W windows of c bits, the top `narrow` of them
-  // one bit narrower so that the widths add up exactly.
-  int w = (bits + c - 1) / c;
-  int deficit = w * c - bits;
-  if (deficit > w || c < 3) {  // cannot be spread one bit per window: uniform widths, sparse top window
-    *W = (bits + 1 + c - 1) / c;
-    *narrow = 0;
-    return;
-  }
-  *W = w;
-  *narrow = deficit;
-}
-// bit offset of window w (sum of the widths below it): the weight 2^offset of its digits
-static inline int msm_window_offset(int w, int c, int W, int narrow) {
-  int off = 0;
-  for (int k = 0; k < w; k++) off += msm_window_width(k, c, W, narrow);
-  return off;
-}
-
-// Window size.  Model (seconds) of the phases that depend on c, from this chip's measured rates
-// (profiles/): mixed additions stream at ~5.5e9/s (Fp384; scaled by `mul_cost` for other fields) but a
-// single bucket is a serial chain (~14 us per addition on a lightly loaded SIMD), the first reduction
-// level costs 2 full additions per bucket, the bit-sliced remainder ~0.5 ms.  With a prepared base set
-// (`shared`) only one bucket set is reduced, which moves the optimum to wider windows.
-static inline MsmPlan msm_make_plan(size_t n, int bits, double mul_cost, bool shared, bool lazy28 = false,
-                                    const MsmWidths* widths = nullptr, bool split_runs = false) {
-  const double plain_k = lazy28 ? 0.79 : 1.0;   // plain path only: see the accumulate model below
-  int best_c = 3;
-  double best = 1e300;
-  const char* env = getenv(shared ? "ARK_HIP_MSM_C_PREPARED" : "ARK_HIP_MSM_C");
-  if (env && atoi(env) >= 3 && atoi(env) <= 26) {
-    best_c = atoi(env);
-  } else {
-    // c <= bits: a window wider than the scalar only adds empty buckets to sort and reduce (msm_u16 at 2^24: the model's
-    // c = 19 took 8.2 ms, c = 17 -- one window of exactly the 2^16 buckets the digits reach -- 4.1 ms;
-    // profiles/r4_narrow_scalars.txt)
-    const int c_max = shared ? 25 : 23;
-    for (int c = 3; c <= (bits < c_max ? (bits < 3 ? 3 : bits) : c_max); c++) {
-      int W, narrow;
-      msm_window_layout(c, bits, &W, &narrow);
-      double nbk = (double)(W - narrow) * (double)(1u << (c - 1)) + (double)narrow * (double)(1u << (c - 2));
-      if (shared) nbk = (double)(1u << (c - 1));
-      double entries = (double)n * W;
-      if (widths) {
-        // measured width classes (K0): a scalar of b bits has digits in the windows below bit b + 1 only
-        entries = 0.0;
-        for (int k = 1; k < MSM_WIDTH_CLASSES; k++) {
-          int need = (MSM_WIDTH_TOP[k] + 1 + c - 1) / c;
-          if (need > W) need = W;
-          entries += (double)widths->count[k] * need;
-        }
-        if (entries < 1.0) entries = 1.0;
-      }
-      const double madd = 1.0 / 5.5e9 * mul_cost, fadd = 1.4 / 5.5e9 * mul_cost;
-      const bool fp2 = mul_cost > 2.0;  // a lane PAIR per bucket
-      // accumulate: throughput-bound when the buckets make several rounds over the chip's resident lanes (2 waves x 4
-      // SIMDs x 256 CUs x 64 lanes; a G2 bucket takes a lane pair); with a single round the kernel lasts as long as
-      // its most loaded lane (Poisson tail): ~24 us per addition on a fully occupied SIMD, ~14 us with one wave per SIMD
-      // (profiles/r2_small_n_sweep.txt)
-      double acc = entries * madd;
-      if (shared) {
-        const double lanes = 131072.0 / (fp2 ? 2.0 : 1.0);
-        const double load = entries / nbk, lmax = load + 3.0 * sqrt(load) + 2.0;
-        // one dependent addition: a wave alone on its SIMD runs a chain faster; over Fp2 ~30 us whatever the occupancy
-        // (BLS12-377 G2 2^16, c = 15 / 16 / 17: 25 / 28 / 31 us -- profiles/r2_msm_sweeps.txt)
-        const double per_add = fp2 ? 30e-6 : (nbk <= lanes / 2 ? 14e-6 : 24e-6) * mul_cost;
-        const double walk = lmax * per_add + W * 5e-6;                          // + run switches of a shared bucket
-        if (nbk <= lanes || walk > acc) acc = walk;
-      } else if (fp2) {
-        // G2 plain path on the carry-free lane-pair kernels, fitted on BLS12-377 G2 2^16 / 2^20 / 2^22, c = 13 .. 21
-        // (profiles/r4_planner_sweeps.txt): 0.40 ns per entry, rising for narrow windows (c = 15: 0.47, c = 14: 0.63); one
-        // lane pair walks one (window, bucket) run at 38 us per dependent addition, the most loaded run sets the floor
-        acc = entries * 0.40e-9 * (1.0 + ldexp(1.0, 13 - c));
-        const double load = entries / nbk;
-        const double chain = (load + 3.0 * sqrt(load) + 2.0) * 38e-6;
-        if (chain > acc) acc = chain;
-      } else {
-        // G1 on carry-free limbs (round 3; BN254 since round 4, scaled by its mul_cost): 7.0e9 instead of 5.5e9 mixed
-        // additions/s (plain_k = 0.79).
-        // One lane walks one (window, bucket) run, and the kernel lasts at least as long as its most loaded lane: measured
-        // 19 us per dependent addition for BLS12-381 whatever the occupancy (2^15 / 2^16, mean loads 2 .. 128:
-        // profiles/r3_window_sweep.txt), 14-18 us for BN254.
-        const double load = entries / nbk;
-        // (round 5, profiles/r5_window_sweep_mid_sizes.txt) the first point of a bucket is a copy, not an addition:
-        // entries - occupied buckets additions (2^19, c = 16 / 17: 7.86e6 / 6.88e6 additions in 1.13 / 1.00 ms; 2^20, c = 17:
-        // 1.475e7 in 2.07 ms), and a launch of only ~2 rounds over the chip's 131 072 resident lanes pays for its ragged last
-        // round: c = 15 (2.78e5 lanes) runs 5-9 % over the rate at 2^18 / 2^19 where c = 16 (four rounds) and wider match it
-        // That saving is there while the bucket array stays in the 256 MB last-level cache (<= ~1e6 buckets of 192 B); beyond,
-        // a bucket's first touch and its store cost what the copy saves (2^22: c = 19 / 20, 2.2e6 / 5.5e6 buckets, run at
-        // 6.5e9 entries/s against c = 17's 6.8e9): the credit fades out between 1e6 and 4e6 buckets.
-        const double rounds = nbk / 131072.0;
-        const double credit = nbk <= 1e6 ? 1.0 : (nbk >= 4e6 ? 0.0 : (4e6 - nbk) / 3e6);
-        acc = (entries - credit * nbk * (1.0 - exp(-load))) * madd * plain_k * (rounds >= 1.0 ? 1.0 + 0.3 / (rounds * rounds) : 1.0);
-        const double lmax = load + 3.0 * sqrt(load) + 2.0;
-        // one dependent addition: 19 us on 14 x 28-bit limbs, 13.5 us on BN254's 9 x 29 (2^17, c = 15 / 16: 0.24 / 0.165 ms)
-        const double chain = lmax * (lazy28 ? (mul_cost < 1.0 ? 13.5e-6 : 19e-6) : 32e-6 * mul_cost);
-        if (chain > acc) acc = chain;
-        if (!widths && (narrow > 0 || W * c == bits)) {
-          // the TOP window: scalars below r (folded below r / 2) reach only r / 2^bits of its buckets -- 0.58 for BLS12-377's
-          // r = 0x12ab..., 0.76 for BN254's, 0.91 for BLS12-381's -- so its runs are that much longer than the layout says and,
-          // sorted to the front, are what the kernel's last waves are still walking: ~11 us per dependent addition once few
-          // waves are left (BLS12-377 G1 2^18: accumulate 0.89 ms with c = 15, 0.57 with c = 16, where BLS12-381 takes 0.63 /
-          // 0.55; 2^17: 0.51 / 0.32; 2^16, c = 14: 0.47 against 0.36)
-          const double frac = bits == 253 ? 0.583 : (bits == 254 ? 0.756 : (bits == 255 ? 0.906 : 1.0));
-          const int wt = narrow > 0 ? c - 1 : c;
-          const double load_top = (double)n / (frac * ldexp(1.0, wt - 1));
-          const double chain_top = (load_top + 3.0 * sqrt(load_top) + 2.0) * 11e-6 * (mul_cost < 1.0 ? 0.7 : 1.0);
-          if (chain_top > acc) acc = chain_top;
-        }
-      }
-      // level 0 of the reduction: 2 full additions per bucket; over Fp2 with ONE bucket set (a lane PAIR per bucket: half
-      // the lanes, the same chain length) the kernels run at ~40 % of the addition throughput (measured: BLS12-377 G2 2^16, 2^18 buckets 1.7 ms,
-      // 2^16 buckets 0.76 ms; 2^22, 2^19 buckets 2.2 ms -- profiles/r2_msm_sweeps.txt)
-      double red0 = nbk * 2.0 * fadd * (fp2 && shared ? 2.5 : 1.0);
-      const double red0_lat = (fp2 && shared) ? 0.6e-3 : 2.0 * 8.0 * 21e-6 * mul_cost;  // latency floor of the reduction (G2: measured 0.62-0.76 ms for 2^12..2^16 buckets)
-      if (red0_lat > red0) red0 = red0_lat;
-      double bits_stage = 0.5e-3 * mul_cost;                    // bit-sliced stage + host tail
-      if (!shared && fp2) {
-        // measured reduction of the plain G2 path: 0.45 ms + 2.6 ns per bucket up to ~10^6 buckets (short level-0 chunks: the
-        // bit-sliced stage is almost half of it), 1.25 ns per bucket beyond (same sweeps)
-        // (round 5 refit, profiles/r5_g2_window_sweep.txt: the lane-pair kernels of round 4 reduce 1.97e6 buckets in 4.6 ms,
-        // 4.98e6 in 10.6, 1.36e7 in 23 -- 1.7 ns per bucket beyond the first 1.2e6, not the 1.25 of the saturated kernels this
-        // line was fitted on; the old figure made c = 19 look 1.7 ms cheaper than it is and cost BLS12-377 G2 2^20 14 %)
-        // (the L0 = 16 rule of the same round made 2.8e5 .. 9.8e5 buckets 0.3-0.5 ms cheaper than this line says; a refit on that moved
-        // 2^20 to c = 17 and lost 8 % on BLS12-381 G2 -- 9.72 against 8.98 ms, profiles/r5_window_sweep_mid_sizes.txt -- so it stays)
-        red0 = 0.45e-3 + (nbk < 1.2e6 ? nbk : 1.2e6) * 2.6e-9 + (nbk > 1.2e6 ? nbk - 1.2e6 : 0.0) * 1.7e-9;
-        bits_stage = 0.0;
-      }
-      if (!shared && !fp2) {
-        // plain path, fitted on BLS12-381 2^16 .. 2^24 (profiles/r3_window_sweep.txt): 0.2 ms + 0.45 ns per bucket
-        // + 1.4 ns per bucket for the first 3e5 (few buckets leave the chip's lanes idle, the chains dominate)
-        // (round 5 refit on the split-level kernels, BLS12-381 G1: 1.56e5 buckets 0.43 ms, 2.8e5 0.54, 5.2e5 0.65-0.71, 9.8e5
-        // 0.95, 3.7e6 2.1, 6.8e6 3.6; BN254 half of that: 0.40 ms + 0.47 ns per bucket + 0.10 ns for the first 1e6.  The older
-        // fit -- 0.2 ms + 0.40 ns + 1.4 ns for the first 3e5 -- was 0.1 ms high between 3e5 and 1e6 buckets, 0.25 ms low at 6.8e6)
-        // Counted half way between the occupied slots and W 2^(c-1): the reduction walks every window at full width, and the
-        // empty upper half of a narrow one costs it its lanes' launch and barriers but no additions (2^23, c = 19: 2.09 ms with
-        // 11 of 14 windows narrow on BLS12-381, 1.67 with 13 of 14 on BLS12-377; c = 18, uniform, 1.26)
-        const double nred = 0.5 * (nbk + (double)W * ldexp(1.0, c - 1));
-        red0 = (nred * 0.47e-9 + (nred < 1e6 ? nred : 1e6) * 0.10e-9) * mul_cost;
-        bits_stage = 0.40e-3 * mul_cost;
-      }
-      // partition sort: per entry, plus a per-(window, bucket) term.  On the shared path at n >= 2^23 the latter is
-      // measured nearly flat up to c = 22 (9 super-bucket bits + 12 bits finished in LDS, msm_part_split); beyond that the
-      // super-bucket histogram grows and so do both sort passes (2^25: c = 24 costs +2.8 ms of sort and +7 ms of
-      // reduction for -4.7 ms of accumulation; BN254 2^23 / 2^24: c = 22 beats 20 by 6-7 %; profiles/r2_msm_sweeps.txt)
-      const double per_bucket = (shared && n >= ((size_t)1 << 23) && c <= 22) ? 1.5e-11 : 1.0e-10;
-      const double sort = (double)n * W * 2.0e-11 + (double)W * (double)(1u << (c - 1)) * per_bucket;   // every key is read, live or not
-      double cost = acc + red0 + bits_stage + sort;
-      if (narrow == W) continue;  // every window one bit narrower: the layout of c - 1 with twice the buckets
-      if (narrow == 0) {
-        // uniform widths: a top window with only a few significant bits funnels n/2^tb points into each of 2^tb
-        // buckets: correct (heavy-bucket path) but measured ~1.4x slower on the plain path and ~2x on a prepared set
-        // (BLS12-377 G2 2^16: c = 18 3.7 ms against 1.9 ms at c = 17; 2^24 G1: c = 21, 23)
-        const int tb = (bits - 1) - (W - 1) * c;
-        if (tb >= (shared ? 0 : 1) && tb <= 5) cost *= shared ? 2.0 : 1.4;
-        // narrow scalars (two to five windows): a top window that is more than two bits short of full is a large share
-        // of the work and loses more -- msm_u32 with c = 18 (18 + 15 bits) 12.5 ms at 2^24 against 8.8 ms for the exact
-        // 17 + 16 layout; only a top window that holds nothing but the carry bit (tb = 0: one heavy bucket) is cheap
-        else if (!shared && !fp2 && bits <= 129 && tb > 5 && tb < c - 3) cost *= 1.4;
-      }
-      if ((size_t)n * (size_t)W >= (1ull << 32)) continue;  // 32-bit sort positions
-      static const bool dbg = getenv("ARK_HIP_PLAN_DEBUG") != nullptr;   // the model's terms per candidate, on stderr
-      if (dbg)
-        fprintf(stderr, "plan n=%zu c=%d W=%d narrow=%d: accumulate %.3f reduce %.3f + %.3f sort %.3f -> %.3f ms\n", n, c, W, narrow,
-                acc * 1e3, red0 * 1e3, bits_stage * 1e3, sort * 1e3, cost * 1e3);
-      if (cost < best) { best = cost; best_c = c; }
-    }
-  }
-  unsigned parts = 0;
-  if (split_runs && !shared && !widths && bits > 128 && !(env && atoi(env) >= 3 && atoi(env) <= 26)) {
-    // Small plain MSMs (round 5, profiles/r5_small_n_run_parts.txt).  Below ~2^17 pairs the accumulate kernel lasts as long as
-    // its most loaded bucket (a Poisson tail of dependent additions at ~17 us each) and the model above answers with wide
-    // windows -- few points per bucket, many buckets to reduce.  Narrower windows with every run walked by 4 or 8 lanes
-    // (msm_accumulate_parts_kernel: the chain is cut, the pieces are summed by msm_sum_parts_kernel) win on both sides:
-    // BLS12-381 G1 2^16 c = 14 -> 12: reduce 0.43 -> 0.27 ms, accumulate 0.36 -> 0.40, call 1.11 -> 0.99 ms; 2^14 0.91 -> 0.79;
-    // 2^12 0.80 -> 0.71; 2^8 0.69 -> 0.60; BN254 2^16 0.67 -> 0.60; BLS12-377 G2 2^14 2.00 -> 1.61, 2^12 1.74 -> 1.39.
-    // From 2^17 (G2: 2^16) the model's choice with one lane per run is the faster one again.  BLS12-377 G1 leaves the rule at
-    // 2^15 already (1.09 against 1.07 ms, 2^16 1.29 against 1.22; 2^14 0.81 against 0.99): r = 0x12ab... x 2^240 fills only
-    // 0.58 of its top window's buckets, whose runs are then twice as long as anybody else's and set the kernel's time.
-    static const bool on = [] { const char* e = getenv("ARK_HIP_MSM_SMALL_SPLIT"); return !(e && e[0] == '0'); }();
-    const bool fp2 = mul_cost > 2.0;
-    int logn = 0;
-    while (((size_t)1 << logn) < n) logn++;
-    if (on && n >= 256 && n <= (fp2 ? (size_t)24576 : bits == 253 ? (size_t)20480 : (size_t)73728)) {
-      const int cap = fp2 ? 11 : 12;
-      best_c = logn - 2 < cap ? logn - 2 : cap;
-      parts = (!fp2 && (n >> (best_c - 1)) >= 32) ? 8u : 4u;
-    }
-  }
-  MsmPlan p;
-  p.c = best_c;
-  p.shared = shared;
-  p.parts = parts;
-  msm_window_layout(best_c, bits, &p.W, &p.narrow);
-  if (!shared && getenv("ARK_HIP_MSM_UNIFORM")) {  // A/B knob: the older uniform-width layout
-    p.W = (bits + 1 + best_c - 1) / best_c;
-    p.narrow = 0;
-  }
-  p.nb = (size_t)p.W << (best_c - 1);
-  return p;
-}
-
-static inline MsmPlan msm_plan_for_widths(size_t n, int field_bits, double mul_cost, bool lazy28, const MsmWidths& w) {
-  const int slack = 8;
-  int bits = field_bits;
-  if ((int)w.max_bits + 1 + slack <= field_bits) bits = (w.max_bits ? (int)w.max_bits : 1) + 1;
-  return msm_make_plan(n, bits, mul_cost, false, lazy28, &w);
-}
+// ---- host-side workspace (the plan and the geometry: msm_plan.hpp) -------------------------------
+// ARK_HIP_MSM_LAZY=0: the saturated kernels on every curve (A/B measurements)
+static inline bool msm_lazy_enabled() { static const bool on = msm_knobs().lazy; return on; }
 
 struct DevBuf {
   void* p = nullptr;
@@ -1689,6 +1370,42 @@ struct MsmWorkspace {
   u32* probe_host = nullptr;   // pinned word the width probe reads back into (a pageable target costs a staged copy)
   DevBuf nzcnt, cscal, cidx;   // zero-scalar compaction (K0c): per-chunk non-zero counts + their scan, the compacted scalars, their indices
   bool probe_allowed = true;   // set per call by the C ABI: the *_async entries must not wait for the lane's stream to drain
+  // Every buffer one msm_enqueue call needs behind the probe, grown here and nowhere else; non-zero: out of memory.
+  // pt_bytes: one XYZZ point; own_buckets: not a piece of a streamed MSM (whose bucket array is the stream's)
+  int reserve(size_t n, const MsmPlan& pl, const MsmSortGeom& sg, const MsmReduceGeom& rg, const MsmHeavyGeom& hg, size_t pt_bytes,
+              bool compacted, bool own_buckets, u32 run_parts) {
+    const size_t W = (size_t)pl.W, Wr = (size_t)pl.red_windows(), nbk = pl.nbuckets(), B = pt_bytes;
+    const bool fail =
+        (compacted && (cscal.ensure(n * 32) || cidx.ensure(n * 4))) ||
+        keys.ensure(W * n * 4) || sorted.ensure(W * n * 4) || part.ensure(W * n * 8) ||
+        thist.ensure(sg.nthist * 4) || toff.ensure((sg.nthist + 2) * 4) ||   // (+1 per window group)
+        offsets.ensure((pl.nb + 2) * 4) || sums.ensure(2 * sg.nsums * 4) ||   // one scan scratch per window group
+        order.ensure(nbk * 4) || ohist.ensure((sg.nohist + ORDER_BINS) * 4) || ooff.ensure((sg.nohist + ORDER_BINS + 2) * 4) ||
+        (own_buckets && buckets.ensure(nbk * B)) ||
+        lvlS[0].ensure(rg.m * Wr * B) || lvlA[0].ensure(rg.m * Wr * B) || lvlS[1].ensure(rg.npart * B) ||
+        (rg.nchunks > 1 && lvlA[1].ensure(rg.npairs * B)) || (rg.two_digit && lvlA[1].ensure(Wr * rg.nsum2 * B)) ||
+        hctr.ensure(64) || hlist.ensure((hg.max_heavy + 1) * sizeof(HeavyEntry)) || hitems.ensure((hg.max_items + 1) * 8) ||
+        hpart.ensure((hg.max_items + 1) * B) || (pl.shared && hfinal.ensure(hg.max_heavy * B)) ||
+        (sg.big_on && big.ensure(2 * sg.big_region * 4)) || (run_parts > 1 && parts.ensure(2 * (size_t)run_parts * pl.nb * B));
+    return fail ? -3 : 0;
+  }
+  // what the launches need besides memory: the side stream and its events (two window groups, heavy runs on the side), and
+  // the opt-in for more than 64 KiB of dynamic LDS (once per device; the workspace is per device)
+  int launch_resources(bool need_side) {
+    if (need_side) {
+      if (!side) ARK_HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+      for (auto& e : grp_ev)
+        if (!e) ARK_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (!attr_set) {
+      ARK_HIP_TRY(hipFuncSetAttribute((const void*)msm_part_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)PART_SCATTER_LDS_MAX));
+      ARK_HIP_TRY(hipFuncSetAttribute((const void*)msm_part_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      160 * 1024 - 64));
+      attr_set = true;
+    }
+    return 0;
+  }
   void release() {
     if (probe_host) (void)hipHostFree(probe_host);
     probe_host = nullptr;
@@ -1724,6 +1441,17 @@ static inline int msm_job_pinned(MsmJob& j, size_t bytes) {
   return 0;
 }
 
+// the slot's staging area for `bytes` of results, its completion events and (timing) its six timing events
+static inline int msm_job_resources(MsmJob& j, size_t bytes, bool timing) {
+  if (int rc = msm_job_pinned(j, bytes)) return rc;
+  if (!j.done) ARK_HIP_TRY(hipEventCreateWithFlags(&j.done, hipEventDisableTiming));
+  if (!j.acc_done) ARK_HIP_TRY(hipEventCreateWithFlags(&j.acc_done, hipEventDisableTiming));
+  if (timing)
+    for (auto& e : j.ev)
+      if (!e) ARK_HIP_TRY(hipEventCreate(&e));
+  return 0;
+}
+
 // One piece of a STREAMED MSM (capi.hip msm_stream: the host-pointer entry points).  The pairs of one MSM arrive in
 // pieces (uploads overlapping compute); every piece is digit-recoded and sorted on its own, but all pieces accumulate into
 // ONE bucket array laid out by the plan of the whole job, and only the last piece runs the bucket reduction: cutting an
@@ -1737,18 +1465,353 @@ struct MsmPiece {
   hipEvent_t after_this;   // recorded behind this piece's accumulate kernels
 };
 
+// What K0 found out about the scalars of one call (msm_probe_widths)
+struct MsmProbe {
+  MsmWidths widths{};
+  bool have_widths = false;      // the plan is made for the measured classes
+  bool measured_exact = false;   // the exact pass ran in chunks that left their non-zero counts (K0c can follow)
+  u32 nz_chunk = 0, nz_blocks = 0;
+};
+
+// K0.  Width classes of full-width scalars: one 40-byte read-back decides the plan, so the probe runs only where that round
+// trip (~30 us; 2 % of a 2^18 call, measured) is small against the call (n >= 2^19) and nothing else of this workspace is in
+// flight to wait behind (a pipelined caller keeps the plan for n uniform 255-bit scalars).  ARK_HIP_MSM_PROBE=0 turns it off.
+// (The probe waits for its read-back, i.e. for everything already queued on this stream -- a device transform producing the
+// scalars, say: the asynchronous entry points skip it and keep the uniform-scalar plan)
+// A prepared call whose scalars turn out no wider than 48 bits leaves here as a plain one (`prepared`, `wstride` reset).
+template <class C>
+int msm_probe_widths(MsmWorkspace& ws, const void* d_scalars, size_t n, int scalars_mont, hipStream_t stream, const MsmKnobs& knobs,
+                     const MsmPlan*& prepared, size_t& wstride, MsmProbe& pr) {
+  bool idle = true;
+  for (int i = 0; i < MSM_JOBS; i++) idle = idle && !ws.jobs[i].busy;
+  if (!(knobs.probe && idle && ws.probe_allowed)) return 0;
+  constexpr size_t PW = (1 + MSM_WIDTH_CLASSES) * 4;
+  if (ws.probe.ensure(PW)) return -3;
+  if (!ws.probe_host) ARK_HIP_TRY(hipHostMalloc((void**)&ws.probe_host, 64, hipHostMallocDefault));
+  auto measure = [&](u32 stride, MsmWidths* w) -> int {
+    const u32 cnt = (u32)((n + stride - 1) / stride);
+    u32 blocks = cnt <= 8192 ? 1u : (cnt + 1023) / 1024;
+    if (blocks > 1024) blocks = 1024;
+    if (blocks > 1) ARK_HIP_TRY(hipMemsetAsync(ws.probe.p, 0, PW, stream));
+    const bool chunked = stride == 1 && blocks > 1;
+    if (chunked) {
+      // the exact pass in contiguous chunks, one per workgroup, each leaving its non-zero count (K0c)
+      pr.nz_chunk = (u32)(((n + blocks - 1) / blocks + 1023) / 1024 * 1024);
+      pr.nz_blocks = blocks = (u32)((n + pr.nz_chunk - 1) / pr.nz_chunk);
+      if (ws.nzcnt.ensure((size_t)(2 * pr.nz_blocks + 2) * 4)) return -3;
+    }
+    hipLaunchKernelGGL((msm_scalar_bits_kernel<typename C::S>), dim3(blocks), dim3(1024), 0, stream, (const u32*)d_scalars, (u32)n,
+                       stride, scalars_mont, (u32*)ws.probe.p, chunked ? pr.nz_chunk : 0u, chunked ? (u32*)ws.nzcnt.p : (u32*)nullptr);
+    ARK_HIP_TRY(hipMemcpyAsync(ws.probe_host, ws.probe.p, PW, hipMemcpyDeviceToHost, stream));
+    ARK_HIP_TRY(hipStreamSynchronize(stream));
+    w->max_bits = ws.probe_host[0];
+    for (int k = 0; k < MSM_WIDTH_CLASSES; k++) w->count[k] = ws.probe_host[1 + k];
+    return 0;
+  };
+  // a spread sample of 4096 scalars first: uniform scalars stop here (more than half of the sample wider than 128 bits)
+  MsmWidths sample{};
+  if (int rc = measure((u32)(n / 4096), &sample)) return rc;
+  if (!msm_widths_skewed(sample)) return 0;
+  if (int rc = measure(1u, &pr.widths)) return rc;
+  pr.measured_exact = pr.nz_blocks > 1;
+  if (!prepared) {
+    pr.have_widths = true;
+  } else if (pr.widths.max_bits <= 48) {   // (u32: 8.9 ms prepared, 6.8 plain; u64: 11.0 prepared, 12.4 plain -- at 2^24)
+    // A prepared set shares ONE bucket set of 2^(c-1) buckets (c = 22 at 2^24) between all windows: right for
+    // n x 12 digits, wrong for scalars that have one to four -- u16 at 2^24: 12.8 ms against the plain path's 3.8.
+    // Row 0 of the table is the base set itself (2^0 P_i): scalars no wider than 48 bits take the plain pipeline on it.
+    prepared = nullptr;
+    wstride = 0;
+    pr.have_widths = true;
+  }
+  return 0;
+}
+
+// chunks the level-0 kernel of curve C keeps resident on the chip, from the occupancy it was built with (0: unknown);
+// asked once per curve
+template <class C>
+size_t msm_resident_lanes() {
+  static const size_t resident = [] {
+    int dev = 0, cus = 0, blocks = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_reduce_level_kernel<C>, 128, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      return (size_t)0;
+    }
+    return (size_t)blocks * (size_t)cus * 128;
+  }();
+  return resident;
+}
+
+// One msm_enqueue call from the digits on: what its stages share.  The stages only enqueue; every size was decided before.
+template <class C>
+struct MsmCall {
+  typedef XYZZ<typename C::F> Pt;
+  MsmWorkspace& ws;
+  MsmJob& job;
+  hipStream_t stream;
+  bool timing;
+  const void* d_points;     // the bases, or a prepared set's [W][wstride] table
+  size_t wstride;
+  const void* d_scalars;    // the n scalars the pipeline carries (after K0c: the compacted ones)
+  size_t n;
+  int scalars_mont;
+  const MsmPiece* piece;
+  MsmPlan pl;
+  MsmSortGeom sg;
+  MsmReduceGeom rg;
+  MsmHeavyGeom hg;
+  int ngroups;
+  bool heavy_side, lazy, compacted;
+  u32 run_parts;
+  int split_level;          // MsmKnobs::split_level
+  char* d_buckets;
+  int accum;                // 1: a later piece of a streamed MSM adds to the buckets
+
+  // A window group: every kernel works on a range of windows through its base pointers (keys, pairs, sorted indices,
+  // offsets, order and buckets are window-major), so a group is nothing but offsets into the same arrays.
+  struct Group {
+    int w0, Wg;
+    size_t slot0, nslots, nbk_g;   // first sort slot, sort slots, accumulated buckets
+    u32 *keys, *sorted, *offsets, *thist, *toff, *order, *sums, *ohist, *ooff, *hctr;
+    u32* big;                      // sliced pass B (msm_sort.cuh): [list of super-buckets, counters[nslots], cursors[nslots]]
+    u32* big_count;                // their number (hctr[8 + g], zeroed with the other counters)
+    uint2* part;
+    HeavyEntry* hlist;
+    uint2* hitems;
+    char *hpart, *buckets, *parts;
+    size_t max_heavy;
+  } grp[2];
+
+  void make_groups() {
+    const int W = pl.W, Bbits = pl.c - 1;
+    const size_t nbk = pl.nbuckets();
+    const int W0 = ngroups == 2 ? (W + 1) / 2 : W;   // windows of group 0
+    for (int g = 0; g < ngroups; g++) {
+      Group& G = grp[g];
+      G.w0 = g == 0 ? 0 : W0;
+      G.Wg = g == 0 ? W0 : W - W0;
+      G.slot0 = (size_t)G.w0 << Bbits;
+      G.nslots = (size_t)G.Wg << Bbits;
+      G.nbk_g = pl.shared ? nbk : G.nslots;
+      G.keys = (u32*)ws.keys.p + (size_t)G.w0 * n;
+      G.sorted = (u32*)ws.sorted.p + (size_t)G.w0 * n;
+      G.part = (uint2*)ws.part.p + (size_t)G.w0 * n;
+      G.offsets = (u32*)ws.offsets.p + G.slot0 + (size_t)g;                     // nslots + 1 entries each
+      G.thist = (u32*)ws.thist.p + ((size_t)G.w0 << sg.HB) * sg.ntiles;
+      G.toff = (u32*)ws.toff.p + ((size_t)G.w0 << sg.HB) * sg.ntiles + (size_t)g;     // (Wg << HB) * ntiles + 1 entries each
+      G.order = (u32*)ws.order.p + G.slot0;
+      G.sums = (u32*)ws.sums.p + (size_t)g * sg.nsums;
+      const size_t noblk0 = ((size_t)(pl.shared ? nbk : ((size_t)W0 << Bbits)) + ORDER_TILE - 1) / ORDER_TILE;
+      G.ohist = (u32*)ws.ohist.p + (size_t)g * noblk0 * ORDER_BINS;
+      G.ooff = (u32*)ws.ooff.p + (size_t)g * (noblk0 * ORDER_BINS + 1);
+      G.hctr = (u32*)ws.hctr.p + 4 * g;
+      G.big = sg.big_on ? (u32*)ws.big.p + (size_t)g * sg.big_region : nullptr;
+      G.big_count = (u32*)ws.hctr.p + 8 + g;
+      const size_t ent0 = (size_t)n * W0;
+      const size_t mh0 = ent0 / 64 + 1, mi0 = ent0 / HEAVY_CHUNK + mh0 + 1;   // group 0's share of the heavy-run arrays
+      G.max_heavy = g == 0 ? (ngroups == 2 ? mh0 : hg.max_heavy) : hg.max_heavy - mh0;
+      G.hlist = (HeavyEntry*)ws.hlist.p + (g == 0 ? 0 : mh0);
+      G.hitems = (uint2*)ws.hitems.p + (g == 0 ? 0 : mi0);
+      G.hpart = (char*)ws.hpart.p + (g == 0 ? 0 : mi0) * Pt::BYTES;
+      G.buckets = d_buckets + (pl.shared ? 0 : G.slot0 * Pt::BYTES);
+      G.parts = run_parts > 1 ? (char*)ws.parts.p + (size_t)g * run_parts * pl.nb * Pt::BYTES : nullptr;
+    }
+  }
+
+  // K0c: the non-zero scalars of the call's n_all, compacted (their base indices go to ws.cidx)
+  void compact(const void* d_scalars_all, size_t n_all, const MsmProbe& pr) {
+    u32* const cnt = (u32*)ws.nzcnt.p;
+    u32* const off = cnt + pr.nz_blocks + 1;
+    scan_exclusive(cnt, pr.nz_blocks, nullptr, off, stream);   // (nz_blocks <= 1024: the one-workgroup scan)
+    hipLaunchKernelGGL((msm_compact_scalars_kernel<typename C::S>), dim3(pr.nz_blocks), dim3(1024), 0, stream,
+                       (const u32*)d_scalars_all, (u32)n_all, scalars_mont, pr.nz_chunk, (const u32*)off, (u32*)ws.hctr.p + 3,
+                       (u32*)ws.cscal.p, (u32*)ws.cidx.p, (u32)n);
+  }
+
+  // K1: one key per (window, scalar).  sbytes != 0: narrow unsigned scalars (K1n)
+  void digits(int sbytes, int sbits) {
+    const int c = pl.c, W = pl.W;
+    u32* const keys = (u32*)ws.keys.p;
+    const u32 nblk = (u32)((n + 255) / 256);
+    if (sbytes) {
+      const u64 vmask = sbits >= 64 ? ~0ull : ((1ull << sbits) - 1ull);
+      const unsigned char* sp = (const unsigned char*)d_scalars;
+      const auto kernel = sbytes == 1 ? msm_digits_small_kernel<1> : sbytes == 2 ? msm_digits_small_kernel<2>
+                          : sbytes == 4 ? msm_digits_small_kernel<4> : msm_digits_small_kernel<8>;
+      hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, stream, sp, (u32)n, c, W, pl.narrow, vmask, keys);
+    } else {
+      hipLaunchKernelGGL((msm_digits_kernel<typename C::S>), dim3(nblk), dim3(256), 0, stream, (const u32*)d_scalars,
+                         (u32)n, scalars_mont, c, W, pl.narrow, keys, (u32*)ws.hctr.p + 3);
+    }
+  }
+
+  // K2, K3.  Partition sort of one group: (A) split by the low bucket bits with LDS counters, (B) finish each super-bucket
+  // in LDS; then the processing order of its buckets, heaviest load class first
+  int sort_group(const Group& G, hipStream_t st, bool mark) {
+    const int HB = sg.HB, LB = sg.LB;
+    const u32 ntiles = sg.ntiles;
+    const size_t mwin = (size_t)1 << (pl.c - 1);
+    const u32 nsuper_g = (u32)G.Wg << HB;
+    const size_t nthist_g = (size_t)nsuper_g * ntiles;
+    hipLaunchKernelGGL(msm_part_hist_kernel, dim3(ntiles, G.Wg), dim3(256), (size_t)4 << HB, st, G.keys, (u32)n, HB, LB,
+                       ntiles, sg.tile, G.thist);
+    scan_exclusive(G.thist, nthist_g, G.sums, G.toff, st);
+    if (mark && timing) ARK_HIP_TRY(hipEventRecord(job.ev[2], st));
+    hipLaunchKernelGGL(msm_part_scatter_kernel, dim3(ntiles, G.Wg), dim3(1024), sg.lds_a, st, G.keys, (u32)n, HB, LB, ntiles,
+                       sg.tile, G.toff, G.part, compacted ? (const u32*)ws.cidx.p : (const u32*)nullptr);
+    hipLaunchKernelGGL(msm_part_finish_kernel, dim3(nsuper_g), dim3(1024), sg.lds_b, st, G.part, G.toff, ntiles, LB, nsuper_g,
+                       sg.stage_cap, sg.big_on ? PART_BIG : 0u, G.big_count, G.big, G.offsets, G.sorted);
+    if (sg.big_on) {
+      u32* const bigcnt = G.big + nsuper_g;     // counters and cursors of a listed super-bucket: zeroed by the finish kernel
+      u32* const cursor = bigcnt + G.nslots;
+      hipLaunchKernelGGL(msm_part_big_hist_kernel, dim3(PART_BIG_SLICES, PART_BIG_GRID_Y), dim3(1024), (size_t)4 << LB, st,
+                         G.part, G.toff, ntiles, LB, G.big_count, G.big, bigcnt);
+      hipLaunchKernelGGL(msm_part_big_place_kernel, dim3(PART_BIG_SLICES, PART_BIG_GRID_Y), dim3(1024),
+                         ((size_t)8 << LB) + 4096, st, G.part, G.toff, ntiles, LB, G.big_count, G.big, bigcnt, cursor, G.offsets,
+                         G.sorted);
+    }
+    int shift = 0;  // class width 2^shift so that the mean load falls around class 32..63
+    while ((hg.mean_load >> shift) >= 64) shift++;
+    const u32 noblk_g = (u32)((G.nbk_g + ORDER_TILE - 1) / ORDER_TILE);
+    const int wsum = pl.shared ? pl.W : 1;
+    hipLaunchKernelGGL(msm_order_hist_kernel, dim3(noblk_g), dim3(256), 0, st, G.offsets, G.nbk_g, shift, noblk_g, wsum, mwin,
+                       G.ohist);
+    scan_exclusive(G.ohist, (size_t)noblk_g * ORDER_BINS, G.sums, G.ooff, st);
+    hipLaunchKernelGGL(msm_order_scatter_kernel, dim3(noblk_g), dim3(256), 0, st, G.offsets, G.nbk_g, shift, noblk_g, wsum, mwin,
+                       G.ooff, G.order);
+    return 0;
+  }
+
+  // K4h, K4, K4s: heavy runs + the lane-per-bucket kernel of one group
+  int accumulate_group(const Group& G, hipStream_t st) {   // (st is reassigned below)
+    const int W = pl.W, Bbits = pl.c - 1, HB = sg.HB, LB = sg.LB;
+    const size_t nbk = pl.nbuckets();
+    // runs too long for one lane: chunk partials by one wave each, combined per run (empty for uniform scalars)
+    hipLaunchKernelGGL(msm_find_heavy_kernel, dim3((u32)((G.nslots + 255) / 256)), dim3(256), 0, st, G.offsets, (u32)G.nslots,
+                       hg.forced_thresh, G.hctr, G.hlist, G.hitems);
+    constexpr u32 LN = C::FA::LANES;                        // lanes per element of the accumulate field
+    constexpr size_t ACCB = AccOps<C>::ACC_BYTES;           // one parked accumulator (the form the kernels sum in)
+    const u32 hthreads = ACCB * (256 / LN) > 49152 ? 128 : 256;  // one LDS tree per wave, <= 48 KiB per workgroup
+    hipStream_t const acc_st = st;
+    if (heavy_side) {
+      ARK_HIP_TRY(hipEventRecord(ws.grp_ev[0], st));
+      ARK_HIP_TRY(hipStreamWaitEvent(ws.side, ws.grp_ev[0], 0));
+      st = ws.side;
+    }
+    hipLaunchKernelGGL((msm_heavy_partial_kernel<C>), dim3(1024), dim3(hthreads), (hthreads / LN) * ACCB, st,
+                       (const char*)d_points, G.sorted, G.offsets, G.hctr, (const uint2*)G.hitems, wstride, Bbits, (u32)G.nslots, G.hpart);
+    const u32 combine_grid = G.max_heavy < 16384 ? (u32)G.max_heavy : 16384u;  // grid-stride over the heavy runs
+    // (a prepared set's heavy runs are summed aside, in ws.hfinal, and applied behind the accumulate kernel)
+    hipLaunchKernelGGL((pl.shared ? msm_heavy_combine_kernel<C, true> : msm_heavy_combine_kernel<C, false>), dim3(combine_grid),
+                       dim3(ARK_HEAVY_COMBINE_THREADS), (ARK_HEAVY_COMBINE_THREADS / LN) * ACCB, st, G.hctr, (const HeavyEntry*)G.hlist,
+                       (const char*)G.hpart, HB, LB, G.offsets, G.sorted, pl.shared ? 0 : accum, pl.shared ? (char*)ws.hfinal.p : G.buckets);
+    if (heavy_side) {
+      ARK_HIP_TRY(hipEventRecord(ws.grp_ev[1], ws.side));
+      st = acc_st;
+    }
+    if (pl.shared) {
+      hipLaunchKernelGGL((lazy ? msm_accumulate_shared_lazy_kernel<C> : msm_accumulate_shared_kernel<C>),
+                         dim3((u32)((nbk * LN + 255) / 256)), dim3(256), 0, st, (const char*)d_points, wstride, G.sorted, G.offsets,
+                         G.order, (u32)nbk, W, Bbits, (const u32*)G.hctr + 2, HB, LB, G.buckets);
+      if (heavy_side) ARK_HIP_TRY(hipStreamWaitEvent(st, ws.grp_ev[1], 0));
+      hipLaunchKernelGGL((msm_apply_heavy_kernel<C>), dim3(1024), dim3(64), 0, st, (const u32*)G.hctr,
+                         (const HeavyEntry*)G.hlist, G.offsets, G.sorted, (const char*)ws.hfinal.p, W, Bbits, HB, LB, G.buckets);
+    } else if (lazy && run_parts > 1) {
+      hipLaunchKernelGGL((msm_accumulate_parts_kernel<C>), dim3((u32)((G.nslots * run_parts * LN + 255) / 256)), dim3(256), 0, st,
+                         (const char*)d_points, G.sorted, G.offsets, G.order, (u32)G.nslots, (const u32*)G.hctr + 2, HB, LB,
+                         run_parts, G.parts);
+      hipLaunchKernelGGL((msm_sum_parts_kernel<C>), dim3((u32)((G.nslots * LN + 255) / 256)), dim3(256), 0, st, G.offsets,
+                         (u32)G.nslots, (const u32*)G.hctr + 2, HB, LB, run_parts, (const char*)G.parts, accum, G.buckets);
+    } else {
+      hipLaunchKernelGGL((lazy ? msm_accumulate_lazy_kernel<C> : msm_accumulate_kernel<C>), dim3((u32)((G.nslots * LN + 255) / 256)),
+                         dim3(256), 0, st, (const char*)d_points, G.sorted, G.offsets, G.order, (u32)G.nslots,
+                         (const u32*)G.hctr + 2, HB, LB, accum, G.buckets);
+    }
+    if (!pl.shared && heavy_side) ARK_HIP_TRY(hipStreamWaitEvent(st, ws.grp_ev[1], 0));
+    return 0;
+  }
+
+  // K5.  Bucket reduction of all windows: level 0 (chunked running sums), the bit-sliced sums, the chunk sums
+  void reduce(hipStream_t st) {
+    constexpr u32 LNr = C::FA::LANES;
+    const size_t wg = (size_t)pl.red_windows(), mwin = (size_t)1 << (pl.c - 1), m = rg.m;
+    // level 0: the two chains of a chunk on one lane (2 L0 dependent additions) or on two waves (L0 + 1, twice the lanes):
+    // the split form where its lanes still fit the chip's resident ones -- 2 waves x 1024 SIMDs (ARK_HIP_MSM_SPLIT_LEVEL=0/1 forces)
+    // measured (profiles/r5_reduce_split_level.txt, BLS12-381 G1): 2^16 0.48 -> 0.44 ms, 2^18 0.70 -> 0.54, 2^20 0.89 -> 0.71
+    // (split lanes <= 131 072: one round of the chip); 2^23 2.31 -> 2.00 (L0 = 32: 33 steps instead of 64 outweigh the 1.75
+    // rounds of 229 376 lanes); 2^21 / 2^22 (L0 = 8, 245 760 lanes) 1.15 -> 1.21 / equal; 2^24, 2^26 equal; the lane-pair
+    // curves (G2) lose 2-3 % everywhere: off there
+    const u32 nfull = rg.red_full;   // full windows
+    const MsmLevelGeom geom{rg.L0, (u32)mwin, (u32)m, (u32)rg.mn, nfull, (u32)(nfull * m + (wg - nfull) * rg.mn)};
+    const size_t split_lanes = m * wg * 2;   // (the rule was fitted on the windows' nominal lanes)
+    const bool split = split_level >= 0 ? split_level != 0
+                                        : (LNr == 1 && rg.L0 >= 2 && (split_lanes <= 131072 || (rg.L0 >= 16 && split_lanes <= 262144)));
+    const size_t per_block = split ? 64 : 128;   // chunks per workgroup of 128 lanes
+    hipLaunchKernelGGL((split ? msm_reduce_level_split_kernel<C> : msm_reduce_level_kernel<C>),
+                       dim3((u32)(((size_t)geom.total * LNr + per_block - 1) / per_block)), dim3(128), 0, st, (const char*)d_buckets, geom,
+                       (char*)ws.lvlS[0].p, (char*)ws.lvlA[0].p);
+    constexpr size_t ACCBr = AccOps<C>::ACC_BYTES;
+    const u32 rthreads = ACCBr * (256 / LNr) > 49152 ? 128 : 256;  // LDS tree within 48 KiB
+    if (rg.two_digit) {
+      // lanes per row / column sum: the longest is walked in <= 8 steps by each (12 dependent additions with the tree at
+      // 128-element rows), which at 2^24 pairs is 1.2 waves per SIMD
+      constexpr u32 NSr = 64 / LNr;
+      const u32 longest = std::max<u32>(rg.rows2, 1u << rg.d2);
+      u32 lps = 1;
+      while (lps < NSr && lps * 8 < longest) lps <<= 1;
+      char* const rc = (char*)ws.lvlA[1].p;
+      hipLaunchKernelGGL((msm_reduce_rowcol_kernel<C>), dim3((u32)((rg.nsum2 + NSr / lps - 1) / (NSr / lps)), (u32)wg), dim3(64), 0, st,
+                         (const char*)ws.lvlS[0].p, (const char*)ws.lvlA[0].p, (u32)m, (u32)rg.mn, nfull, rg.d2, rg.rows2, lps, rc);
+      hipLaunchKernelGGL((msm_reduce_bits2_kernel<C>), dim3(rg.Q, (u32)wg), dim3(rthreads), (rthreads / LNr) * ACCBr, st,
+                         (const char*)rc, rg.d2, rg.rows2, rg.nbits, (char*)ws.lvlS[1].p);
+      return;
+    }
+    hipLaunchKernelGGL((msm_reduce_bits_kernel<C>), dim3(rg.nchunks, rg.Q, (u32)wg), dim3(rthreads), (rthreads / LNr) * ACCBr, st,
+                       (const char*)ws.lvlS[0].p, (const char*)ws.lvlA[0].p, (u32)m, (u32)rg.mn, nfull, rg.nbits, rg.chunk,
+                       (char*)ws.lvlS[1].p);
+    if (rg.nchunks > 1)
+      hipLaunchKernelGGL((msm_sum_chunks_kernel<C>), dim3((u32)(wg * rg.Q)), dim3(64), (64 / LNr) * AccOps<C>::ACC_BYTES, st,
+                         (const char*)ws.lvlS[1].p, (u32)(wg * rg.Q), rg.nchunks, (char*)ws.lvlA[1].p);
+  }
+
+  // Read-back and the job record.  d_sums: the part sums of a whole job; nullptr: a non-final piece of a streamed MSM, whose
+  // reduction belongs to the last piece -- only the scalar-range flag goes back
+  int finish(const char* d_sums) {
+    const size_t sums_bytes = rg.npairs * Pt::BYTES;
+    ARK_HIP_TRY(hipGetLastError());
+    if (d_sums) ARK_HIP_TRY(hipMemcpyAsync(job.pinned, d_sums, sums_bytes, hipMemcpyDeviceToHost, stream));
+    ARK_HIP_TRY(hipMemcpyAsync((char*)job.pinned + sums_bytes, (const u32*)ws.hctr.p + 3, 4, hipMemcpyDeviceToHost, stream));
+    if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[5], stream));
+    ARK_HIP_TRY(hipEventRecord(job.done, stream));
+    job.pl = pl;
+    job.npairs = rg.npairs;
+    job.timing = timing;
+    job.no_result = d_sums == nullptr;
+    if (d_sums) {
+      job.nbits = rg.nbits;
+      job.L0 = rg.L0;
+      job.short_job = (double)n * (double)pl.W <= 6.0e6;   // (up to ~2^18 full-width pairs)
+      job.Q = rg.Q;
+      job.d_sums = d_sums;
+    }
+    job.busy = true;
+    return 0;
+  }
+};
+
 // Enqueue one single-GPU MSM with device-resident inputs on `stream`; returns the job slot (>= 0) or a negative code.
 //   points / wstride / prepared:  plain call: points = the n bases, wstride = 0, prepared = nullptr;
 //                                 prepared base set: points = the [W][wstride] table of per-window multiples and
 //                                 `prepared` = the plan it was built for (msm_prepare_table).
+//   sbytes != 0: narrow unsigned scalars of sbytes bytes with at most sbits significant bits (K1n); never with `prepared`
+//   piece != nullptr: see MsmPiece (never with `prepared`; n > 0)
+// The stages are those of DESIGN.md section 4; every size comes from msm_plan.hpp.
 template <class C>
 int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const MsmPlan* prepared, const void* d_scalars,
                 size_t n, int scalars_mont, hipStream_t stream, bool timing, int sbytes = 0, int sbits = 0,
                 const MsmPiece* piece = nullptr) {
-  // sbytes != 0: narrow unsigned scalars of sbytes bytes with at most sbits significant bits (K1n); never with `prepared`
-  // piece != nullptr: see MsmPiece (never with `prepared`; n > 0)
-  typedef typename C::F F;
-  typedef XYZZ<F> Pt;
+  typedef XYZZ<typename C::F> Pt;
   std::lock_guard<std::mutex> lock(ws.mu);
   int slot = -1;
   for (int i = 0; i < MSM_JOBS; i++)
@@ -1766,627 +1829,75 @@ int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const Ms
   if (n >= (1ull << 31)) return -2;
   if (sbytes && (prepared || (sbytes != 1 && sbytes != 2 && sbytes != 4 && sbytes != 8) || sbits < 1 || sbits > 8 * sbytes))
     return -1;
-  // Width classes of full-width scalars (K0 above): one 40-byte read-back decides the plan, so the probe runs only where
-  // that round trip (~30 us; 2 % of a 2^18 call, measured) is small against the call (n >= 2^19) and nothing else of this workspace is in flight to wait
-  // behind (a pipelined caller keeps the plan for n uniform 255-bit scalars).  ARK_HIP_MSM_PROBE=0 turns it off.
-  int plan_bits = sbytes ? sbits + 1 : C::S::BITS;
-  MsmWidths widths{};
-  bool have_widths = false;
-  u32 nz_chunk = 0, nz_blocks = 0;   // the exact probe's chunks (K0c)
-  bool measured_exact = false;
-  if (!sbytes && !piece && n >= ((size_t)1 << 19)) {
-    static const bool probe_on = [] {
-      const char* e = getenv("ARK_HIP_MSM_PROBE");
-      return !(e && atoi(e) == 0);
-    }();
-    bool idle = true;
-    for (int i = 0; i < MSM_JOBS; i++) idle = idle && !ws.jobs[i].busy;
-    // (the probe waits for its 40-byte read-back, i.e. for everything already queued on this stream -- a device transform
-    //  producing the scalars, say: the asynchronous entry points skip it and keep the uniform-scalar plan)
-    if (probe_on && idle && ws.probe_allowed) {
-      constexpr size_t PW = (1 + MSM_WIDTH_CLASSES) * 4;
-      if (ws.probe.ensure(PW)) return -3;
-      if (!ws.probe_host) ARK_HIP_TRY(hipHostMalloc((void**)&ws.probe_host, 64, hipHostMallocDefault));
-      auto measure = [&](u32 stride, MsmWidths* w) -> int {
-        const u32 cnt = (u32)((n + stride - 1) / stride);
-        u32 blocks = cnt <= 8192 ? 1u : (cnt + 1023) / 1024;
-        if (blocks > 1024) blocks = 1024;
-        if (blocks > 1) ARK_HIP_TRY(hipMemsetAsync(ws.probe.p, 0, PW, stream));
-        if (stride == 1 && blocks > 1) {
-          // the exact pass in contiguous chunks, one per workgroup, each leaving its non-zero count (K0c)
-          nz_chunk = (u32)(((n + blocks - 1) / blocks + 1023) / 1024 * 1024);
-          nz_blocks = (u32)((n + nz_chunk - 1) / nz_chunk);
-          if (ws.nzcnt.ensure((size_t)(2 * nz_blocks + 2) * 4)) return -3;
-          hipLaunchKernelGGL((msm_scalar_bits_kernel<typename C::S>), dim3(nz_blocks), dim3(1024), 0, stream,
-                             (const u32*)d_scalars, (u32)n, stride, scalars_mont, (u32*)ws.probe.p, nz_chunk, (u32*)ws.nzcnt.p);
-        } else
-        hipLaunchKernelGGL((msm_scalar_bits_kernel<typename C::S>), dim3(blocks), dim3(1024), 0, stream,
-                           (const u32*)d_scalars, (u32)n, stride, scalars_mont, (u32*)ws.probe.p);
-        ARK_HIP_TRY(hipMemcpyAsync(ws.probe_host, ws.probe.p, PW, hipMemcpyDeviceToHost, stream));
-        ARK_HIP_TRY(hipStreamSynchronize(stream));
-        w->max_bits = ws.probe_host[0];
-        for (int k = 0; k < MSM_WIDTH_CLASSES; k++) w->count[k] = ws.probe_host[1 + k];
-        return 0;
-      };
-      // a spread sample of 4096 scalars first: uniform scalars stop here (more than half of the sample wider than 128 bits)
-      MsmWidths sample{};
-      if (int rc = measure((u32)(n / 4096), &sample)) return rc;
-      if (msm_widths_skewed(sample)) {
-        if (int rc = measure(1u, &widths)) return rc;
-        measured_exact = nz_blocks > 1;
-        if (!prepared) {
-          have_widths = true;
-        } else if (widths.max_bits <= 48) {   // (u32: 8.9 ms prepared, 6.8 plain; u64: 11.0 prepared, 12.4 plain -- at 2^24)
-          // A prepared set shares ONE bucket set of 2^(c-1) buckets (c = 22 at 2^24) between all windows: right for
-          // n x 12 digits, wrong for scalars that have one to four -- u16 at 2^24: 12.8 ms against the plain path's 3.8.
-          // Row 0 of the table is the base set itself (2^0 P_i): scalars no wider than 48 bits take the plain pipeline on it.
-          prepared = nullptr;
-          wstride = 0;
-          have_widths = true;
-        }
-      }
-    }
-  }
+  const MsmKnobs knobs = msm_knobs();
+
+  MsmProbe pr;   // K0
+  if (!sbytes && !piece && n >= ((size_t)1 << 19))
+    if (int rc = msm_probe_widths<C>(ws, d_scalars, n, scalars_mont, stream, knobs, prepared, wstride, pr)) return rc;
   const MsmPlan pl = prepared ? *prepared
                      : piece  ? *piece->plan
-                     : have_widths ? msm_plan_for_widths(n, C::S::BITS, msm_mul_cost(C::ID), C::LAZY_A, widths)
-                                   : msm_make_plan(n, plan_bits, msm_mul_cost(C::ID), false, C::LAZY_A, nullptr,
-                                                   C::LAZY_A && msm_lazy_enabled());
+                     : pr.have_widths ? msm_plan_for_widths(C::ID, n, pr.widths, knobs)
+                                      : msm_default_plan(C::ID, n, sbytes ? sbits + 1 : C::S::BITS, false, nullptr, knobs);
   // K0c: a quarter or more of the scalars zero (known exactly from the probe's class 0) -> they leave before the sort.
   // From here on `n` is the number of scalars the pipeline carries; base indices come back through ws.cidx after the sort.
-  const size_t n_all = n;
-  const void* const d_scalars_all = d_scalars;
-  bool compacted = false;
-  if (measured_exact && !sbytes && !piece) {
-    static const bool compact_env = [] { const char* e = getenv("ARK_HIP_MSM_COMPACT"); return !(e && e[0] == '0'); }();
-    const size_t zeros = widths.count[0];
-    // what the compaction saves grows with zeros x windows (the keys that are never written, counted and scattered), what it
-    // costs with n (one more pass over the scalars): witness-like 2^24 (60 % zeros, 15 windows) 6.52 -> 5.90 ms, a bool vector
-    // (half zeros, ONE window) 3.22 -> 3.32 -- so: at least a quarter zeros and zeros x W >= 3 n (profiles/r5_zero_compaction.txt)
-    if (compact_env && zeros * 4 >= n && zeros < n && zeros * (size_t)pl.W >= 3 * n) {
-      const size_t nz = n - zeros;
-      if (ws.cscal.ensure(nz * 32) || ws.cidx.ensure(nz * 4)) return -3;
-      compacted = true;
-      n = nz;
-      d_scalars = ws.cscal.p;
-    }
-  }
-  const int c = pl.c, W = pl.W;
-  const size_t nb = pl.nb;                      // sort slots
-  const size_t nbk = pl.nbuckets();             // accumulated buckets
-  const int Wr = pl.red_windows();
-  if ((size_t)n * (size_t)W >= (1ull << 32)) return -2;  // sort positions are 32-bit
-  if (prepared && (wstride < n || (size_t)W * wstride >= (1ull << 31))) return -2;
-  const size_t mwin = (size_t)1 << (c - 1);
+  // What the compaction saves grows with zeros x windows (the keys that are never written, counted and scattered), what it
+  // costs with n (one more pass over the scalars): witness-like 2^24 (60 % zeros, 15 windows) 6.52 -> 5.90 ms, a bool vector
+  // (half zeros, ONE window) 3.22 -> 3.32 -- so: at least a quarter zeros and zeros x W >= 3 n (profiles/r5_zero_compaction.txt)
+  const size_t n_all = n, zeros = pr.widths.count[0];
+  const bool compacted = pr.measured_exact && knobs.compact && zeros * 4 >= n && zeros < n && zeros * (size_t)pl.W >= 3 * n;
+  if (compacted) n = n_all - zeros;
+  if ((size_t)n * (size_t)pl.W >= (1ull << 32)) return -2;  // sort positions are 32-bit
+  if (prepared && (wstride < n || (size_t)pl.W * wstride >= (1ull << 31))) return -2;
 
-  // bucket-id split for the two-pass partition sort (msm_sort.cuh)
-  const int Bbits = c - 1;
-  int HB, LB;
-  msm_part_split(n, Bbits, &HB, &LB);
-  const u32 nsuper = (u32)W << HB;
-  const u32 ptile = msm_part_tile(HB);
-  const u32 ntiles = (u32)((n + ptile - 1) / ptile);
-  const size_t nthist = (size_t)nsuper * ntiles;
-  if (ws.keys.ensure((size_t)W * n * 4)) return -3;
-  if (ws.sorted.ensure((size_t)W * n * 4)) return -3;
-  if (ws.part.ensure((size_t)W * n * 8)) return -3;
-  if (ws.thist.ensure(nthist * 4) || ws.toff.ensure((nthist + 2) * 4)) return -3;   // (+1 per window group)
-  if (ws.offsets.ensure((nb + 2) * 4)) return -3;
-  const u32 ntscan = (u32)((nthist + SCAN_TILE - 1) / SCAN_TILE);
-  const u32 noblk = (u32)((nbk + ORDER_TILE - 1) / ORDER_TILE);
-  const size_t nohist = (size_t)noblk * ORDER_BINS;
-  const u32 noscan = (u32)((nohist + SCAN_TILE - 1) / SCAN_TILE);
-  const size_t nsums = (size_t)(ntscan > noscan ? ntscan : noscan) + 2;
-  if (ws.sums.ensure(2 * nsums * 4)) return -3;   // one scan scratch per window group
-  if (ws.order.ensure(nbk * 4) || ws.ohist.ensure((nohist + ORDER_BINS) * 4) || ws.ooff.ensure((nohist + ORDER_BINS + 2) * 4)) return -3;
-  if (!piece && ws.buckets.ensure(nbk * Pt::BYTES)) return -3;
-  char* const d_buckets = piece ? (char*)piece->buckets : (char*)ws.buckets.p;
-  const int accum = (piece && !piece->first) ? 1 : 0;
-
-  // bucket reduction geometry: level 0 (chunked running sums over L0 buckets per lane), then the bit-sliced sums
-  // a window's own bucket count: the narrow windows (the top pl.narrow ones of a plain job) fill the lower half of their cells
-  const u32 red_narrow = (!pl.shared && mwin >= 2) ? (u32)pl.narrow : 0u;
-  const u32 red_full = (u32)Wr - red_narrow;
-  u32 L0 = 32;
-  {
-    size_t want = (mwin * (size_t)Wr) >> 17;  // keep ~1e5 (S, A) pairs for the bit-sliced stage
-    u32 p2 = 1;
-    while (p2 < want) p2 <<= 1;
-    // few buckets: short chains beat fewer pairs (measured: 2^15 buckets L0 = 2, 2^16..2^17 L0 = 4, profiles/r2_msm_sweeps.txt)
-    const size_t nbr = mwin * (size_t)Wr;
-    const u32 l0_min = nbr <= ((size_t)1 << 15) ? 2 : (nbr <= ((size_t)1 << 17) ? 4 : 8);
-    if (p2 < l0_min) p2 = l0_min;
-    if (p2 < L0) L0 = p2;
-    // one shared bucket set (prepared base set), measured per bucket count (profiles/r2_msm_sweeps.txt, sessions L0 / AN):
-    // 2^18 buckets L0 = 8, 2^19 .. 2^21 L0 = 16 (2^19: reduction 1.32 -> 0.99 ms against L0 = 8)
-    if (Wr == 1 && nbr > ((size_t)1 << 18)) L0 = nbr <= ((size_t)1 << 21) ? 16 : 32;
-    // (round 5) 2^19 .. 2^20 buckets on the one-lane-per-point curves (c = 17: 2^21 / 2^22 pairs): with L0 = 16 the two-wave
-    // level-0 form still fits one round of the chip (2 x 61 440 lanes, 17 steps) and hands the bit-sliced stage half the pairs
-    // of L0 = 8, whose 245 760 split lanes do not fit and whose one-wave form walks 16 steps: reduction 1.18 -> 0.95 ms,
-    // 2^21 6.35 -> 5.99 ms, 2^22 11.20 -> 10.82 (profiles/r5_reduce_geometry_sweep.txt, session r5rs2)
-    if (Wr > 1 && C::FA::LANES == 1 && nbr > ((size_t)1 << 19) && nbr <= ((size_t)1 << 20)) L0 = 16;
-    // (round 5) the lane-pair curves (G2) from 2^18 buckets (c >= 15: 2^17 pairs and up): their bit-sliced stage is the
-    // expensive half, and twice the chain for half the pairs pays -- BLS12-377 G2 reduction 1.58 -> 1.28 ms at 2.8e5 buckets
-    // (2^18: 4.65 -> 4.25 ms), 1.70 -> 1.38 at 5.2e5 (2^19 6.69 -> 6.30, 2^20 10.49 -> 10.10; BLS12-381 G2 2^20 10.13 -> 9.64),
-    // 2.93 -> 2.46 at 9.8e5 (2^21 18.04 -> 17.52); at 1.6e5 buckets L0 = 8 stays the best cell (same sweeps, sessions r5g2r / r5g2r2)
-    // -- and the same holds further up: 9.8e5 buckets L0 = 32 (2.46 -> 2.13 ms); 3.7e6 (2^22, c = 19) L0 = 64 on BLS12-377 G2 (13 of
-    // its 14 windows are narrow: 4.32 -> 3.95 ms, session r5g2l) but 32 on BLS12-381 G2 (11 narrow: 5.85 against 6.5 ms, r5g2l3).
-    // One rule covers every cell measured: the power of two at or above buckets / 32 768, from 8 to 32 (BLS12-377: 64).
-    if (Wr > 1 && C::FA::LANES == 2 && nbr > ((size_t)1 << 18)) {
-      const u32 cap = C::S::BITS == 253 ? 64u : 32u;
-      u32 g = 8;
-      while (g < cap && (size_t)g * 32768 < nbr) g <<= 1;
-      L0 = g;
-    }
-    // Large plain jobs on the one-lane-per-point curves (the rules above say 32): the chunks that hold buckets are a
-    // non-integer number of rounds of the chip's resident lanes (2^24, c = 20: 172 032 chunks on 131 072 lanes = 1.31 rounds of a
-    // 64-addition chain, the second at a third of the occupancy).  Keep the number of rounds and shorten the chain until they are
-    // full: the smallest L0 whose chunks still fit k rounds (2^24: k = 2, L0 = 22).  ARK_HIP_MSM_L0_FILL=0: the power of two.
-    static const bool fill_env = [] { const char* e = getenv("ARK_HIP_MSM_L0_FILL"); return !(e && e[0] == '0'); }();
-    if (fill_env && Wr > 1 && C::FA::LANES == 1 && L0 == 32 && nbr > ((size_t)1 << 21)) {
-      static const size_t resident = [] {   // chunks the level-0 kernel keeps resident, from the occupancy it was built with
-        int dev = 0, cus = 0, blocks = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_reduce_level_kernel<C>, 128, 0) != hipSuccess) {
-          (void)hipGetLastError();
-          return (size_t)0;
-        }
-        return (size_t)blocks * (size_t)cus * 128;
-      }();
-      auto chunks = [&](u32 L) { return red_full * ((mwin + L - 1) / L) + red_narrow * ((mwin / 2 + L - 1) / L); };
-      if (resident) {
-        const size_t rounds = (chunks(32) + resident - 1) / resident;
-        while (L0 > 8 && chunks(L0 - 1) <= rounds * resident) L0--;
-      }
-    }
-    if (const char* e0 = getenv("ARK_HIP_MSM_L0")) {  // tuning knob: any chunk length 1 .. 128
-      int v = atoi(e0);
-      if (v >= 1 && v <= 128) L0 = (u32)v;
-    }
-    if (L0 > mwin) L0 = (u32)mwin;
-  }
-  const size_t m = (mwin + L0 - 1) / L0;         // pairs per full window after level 0 (the last chunk may be ragged)
-  const size_t mn = red_narrow ? (mwin / 2 + L0 - 1) / L0 : m;   // ... per narrow window
-  int nbits = 0;
-  while (((size_t)1 << nbits) < m) nbits++;
-  const u32 Q = (u32)nbits + 1;
-  // second stage: the two-digit form (row and column sums, then the bit-sliced sums of those) from 2048 pairs per window
-  // (a lane pair per point: 1024), the one-kernel form below that (ARK_HIP_MSM_STAGE2=0 / 1 forces one).  Measured
-  // (profiles/reduce_geometry_free_l0.txt, reduction in ms, one-kernel form at its best chunk -> two digits): BLS12-381 G1
-  // m = 512 (2^16) 0.27 -> 0.34, m = 2048 (2^18) 0.53 -> 0.50, m = 4096 (2^20 / 2^22) 0.75 -> 0.62 / 1.08 -> 0.85, m = 16 384
-  // (2^24, L0 = 32) 3.58 -> 3.06; BN254 m = 512 0.16 -> 0.20, m = 4096 0.32 -> 0.29; BLS12-377 G2 m = 1024 (2^18) 1.25 -> 1.08,
-  // m = 2048 (2^20) 1.57 -> 1.20, m = 4096 (2^22) 4.39 -> 3.35
-  bool two_digit = m >= (C::FA::LANES == 2 ? 1024u : 2048u);
-  if (const char* e2 = getenv("ARK_HIP_MSM_STAGE2")) {
-    if (e2[0] == '0') two_digit = false;
-    if (e2[0] == '1') two_digit = true;
-  }
-  const u32 d2 = (u32)nbits / 2;                                   // low digit: D = 2^d2 columns
-  const u32 rows2 = (u32)((m + ((size_t)1 << d2) - 1) >> d2);      // high digit: rows of D pairs
-  const size_t nsum2 = 2 * (size_t)rows2 + ((size_t)1 << d2);      // R, RA, C of one window
-  // chunk of the bit-sliced stage: a workgroup's 256 lanes stride over it (chunk/256 serial additions each) before the
-  // 8-step LDS tree -- both pure latency, so chunks are kept short once there are enough of them to fill the chip
-  // (few workgroups, e.g. one window of a prepared set at small n: latency only, 2^16 1.39 -> 1.11 ms; many: throughput)
-  u32 chunk = (size_t)Wr * Q * ((m + 4095) / 4096) < 512 ? 1024 : 4096;
-  if (Wr == 1) chunk = m <= 16384 ? 1024 : (m <= 65536 ? 2048 : 4096);  // measured: m = 2^15 pairs 2048 (0.77 -> 0.70 ms)
-  if (const char* ec = getenv("ARK_HIP_MSM_CHUNK")) {
-    int v = atoi(ec);
-    if (v == 256 || v == 512 || v == 1024 || v == 2048 || v == 4096 || v == 8192 || v == 16384) chunk = (u32)v;
-  }
-  if (chunk > m || two_digit) chunk = (u32)m;    // (the two-digit form writes the part sums themselves: no chunk partials)
-  const u32 nchunks = (u32)((m + chunk - 1) / chunk);
-  const size_t npart = (size_t)Wr * Q * nchunks;
-  const size_t npairs = (size_t)Wr * Q;
-  if (ws.lvlS[0].ensure(m * Wr * Pt::BYTES) || ws.lvlA[0].ensure(m * Wr * Pt::BYTES)) return -3;
-  if (ws.lvlS[1].ensure(npart * Pt::BYTES)) return -3;
-  if (nchunks > 1 && ws.lvlA[1].ensure(npairs * Pt::BYTES)) return -3;
-  if (two_digit && ws.lvlA[1].ensure((size_t)Wr * nsum2 * Pt::BYTES)) return -3;
-  {
-    int rc = msm_job_pinned(job, npairs * Pt::BYTES + 64);
-    if (rc) return rc;
-  }
-  if (!job.done) ARK_HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming));
-  if (!job.acc_done) ARK_HIP_TRY(hipEventCreateWithFlags(&job.acc_done, hipEventDisableTiming));
-  if (timing) {
-    for (auto& e : job.ev)
-      if (!e) ARK_HIP_TRY(hipEventCreate(&e));
-    ARK_HIP_TRY(hipEventRecord(job.ev[0], stream));
-  }
-
-  u32* keys = (u32*)ws.keys.p;
-  u32* sorted = (u32*)ws.sorted.p;
-  u32* offsets = (u32*)ws.offsets.p;
-  u32* thist = (u32*)ws.thist.p;
-  u32* toff = (u32*)ws.toff.p;
-  uint2* part = (uint2*)ws.part.p;
-  u32* order = (u32*)ws.order.p;
-  u32* sums = (u32*)ws.sums.p;
-
-  // heavy runs: a lane walks its bucket serially (~28 us per entry with two or three waves per SIMD) and
-  // the heaviest buckets start first; a run is "heavy" when its walk would outlast the kernel's
-  // throughput-bound duration (entries / 5.5e9 per s).  At 2^24 x 13 windows that is ~1400 entries, so the
-  // sparse top window (1024 per bucket) still rides along; skewed scalar distributions do not.
-  const size_t total_entries = (size_t)n * W;
-  size_t mean_load = total_entries / nbk;        // per lane (a lane of a prepared set walks W runs)
-  u32 forced_thresh = 0;  // 0: computed on the device from the number of non-zero entries (msm_thresh_kernel)
-  if (const char* hv = getenv("ARK_HIP_MSM_HEAVY")) {
-    if (atoi(hv) >= 64) forced_thresh = (u32)atoi(hv);
-  }
-  const size_t max_heavy = total_entries / 64 + 1;  // the threshold is never below 64
-  const size_t max_items = total_entries / HEAVY_CHUNK + max_heavy + 1;
-  if (ws.hctr.ensure(64) || ws.hlist.ensure((max_heavy + 1) * sizeof(HeavyEntry)) || ws.hitems.ensure((max_items + 1) * 8) ||
-      ws.hpart.ensure((max_items + 1) * Pt::BYTES))
-    return -3;
-  if (pl.shared && ws.hfinal.ensure(max_heavy * Pt::BYTES)) return -3;
-  ARK_HIP_TRY(hipMemsetAsync(ws.hctr.p, 0, 64, stream));  // per window group: [chunk items, heavy runs, threshold, -]; [3]: scalar-range error flag; [8 + g]: super-buckets of group g left to the sliced pass B
-  if (compacted) {
-    u32* const cnt = (u32*)ws.nzcnt.p;
-    u32* const off = cnt + nz_blocks + 1;
-    scan_exclusive(cnt, nz_blocks, nullptr, off, stream);   // (nz_blocks <= 1024: the one-workgroup scan)
-    hipLaunchKernelGGL((msm_compact_scalars_kernel<typename C::S>), dim3(nz_blocks), dim3(1024), 0, stream,
-                       (const u32*)d_scalars_all, (u32)n_all, scalars_mont, nz_chunk, (const u32*)off, (u32*)ws.hctr.p + 3,
-                       (u32*)ws.cscal.p, (u32*)ws.cidx.p, (u32)n);
-  }
-  const u32 nblk = (u32)((n + 255) / 256);
-  if (sbytes) {
-    const u64 vmask = sbits >= 64 ? ~0ull : ((1ull << sbits) - 1ull);
-    const unsigned char* sp = (const unsigned char*)d_scalars;
-    switch (sbytes) {
-      case 1: hipLaunchKernelGGL((msm_digits_small_kernel<1>), dim3(nblk), dim3(256), 0, stream, sp, (u32)n, c, W, pl.narrow, vmask, keys); break;
-      case 2: hipLaunchKernelGGL((msm_digits_small_kernel<2>), dim3(nblk), dim3(256), 0, stream, sp, (u32)n, c, W, pl.narrow, vmask, keys); break;
-      case 4: hipLaunchKernelGGL((msm_digits_small_kernel<4>), dim3(nblk), dim3(256), 0, stream, sp, (u32)n, c, W, pl.narrow, vmask, keys); break;
-      default: hipLaunchKernelGGL((msm_digits_small_kernel<8>), dim3(nblk), dim3(256), 0, stream, sp, (u32)n, c, W, pl.narrow, vmask, keys); break;
-    }
-  } else {
-    hipLaunchKernelGGL((msm_digits_kernel<typename C::S>), dim3(nblk), dim3(256), 0, stream, (const u32*)d_scalars,
-                       (u32)n, scalars_mont, c, W, pl.narrow, keys, (u32*)ws.hctr.p + 3);
-  }
-  if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[1], stream));
-
-  // ---- window groups -------------------------------------------------------------------------------------------
-  // The sort is memory / LDS bound and small (8-28 VGPRs per lane), the accumulate kernel is multiply bound, uses no LDS
-  // and leaves 70 of the 512 registers per SIMD lane free: the two overlap well.  A plain MSM is therefore cut into TWO
-  // groups of windows: group 0 is sorted and accumulated on `stream`; group 1's sort runs on a side stream UNDER group
-  // 0's accumulate kernel and its accumulate kernel follows on `stream`.  Every kernel below already works on a range
-  // of windows through its base pointers (keys, pairs, sorted indices, offsets, order and buckets are window-major), so
-  // a group is nothing but offsets into the same arrays.  One group: a prepared set (its windows share one bucket set),
-  // a piece of a streamed MSM, few windows, and n < 2^25 -- measured (profiles/r3_window_groups_ab.txt): the sort kernels
-  // slow the accumulate kernel they run under by about what they hide up to 2^24 (38.6 against 38.5 ms; 2^20 4.27 against
-  // 4.14), and win where the sort is a larger share: 2^26 136.4 against 139.7 ms.  ARK_HIP_MSM_GROUPS=1 / =2 force it.
-  int ngroups = 1;
-  if (!pl.shared && !piece && W >= 6 && n >= ((size_t)1 << 19)) {
-    static const int groups_env = [] {
-      const char* e = getenv("ARK_HIP_MSM_GROUPS");
-      return e ? atoi(e) : 0;
-    }();
-    if (groups_env == 2 || (groups_env != 1 && n >= ((size_t)1 << 25))) ngroups = 2;
-  }
+  const MsmSortGeom sg = msm_sort_geometry(n, pl, knobs);
+  if (sg.lds_a > PART_SCATTER_LDS_MAX) return -2;   // 2^14 super-buckets and more: beyond the n W < 2^32 the sort serves anyway
+  const MsmReduceGeom rg = msm_reduce_geometry(pl, C::FA::LANES, C::S::BITS, C::FA::LANES == 1 ? msm_resident_lanes<C>() : 0, knobs);
+  const MsmHeavyGeom hg = msm_heavy_geometry(n, pl, knobs);
+  const bool lazy = knobs.lazy;  // the accumulate kernels on carry-free limbs (fp28.cuh); ARK_HIP_MSM_LAZY=0: saturated
+  const u32 run_parts = (lazy && !piece && !pl.shared) ? msm_run_parts(n, pl, pr.have_widths ? &pr.widths : nullptr, knobs) : 1u;
+  const int ngroups = msm_window_groups(n, pl, piece != nullptr, knobs);
   // Heavy runs (skewed scalars) and the lane-per-bucket kernel touch disjoint buckets: with one window group and a call
   // long enough to pay two event hops, the chunk / combine kernels -- chains of dependent additions on a few hundred
   // waves -- run on the side stream UNDER the accumulate kernel (witness-like 2^24: 1.7 ms of heavy kernels in front of
   // 2.1 ms of accumulation; profiles/r4_skewed_sort_ab.txt).  ARK_HIP_MSM_HEAVY_SIDE=0 keeps them in line.
-  static const bool heavy_side_env = [] {
-    const char* e = getenv("ARK_HIP_MSM_HEAVY_SIDE");
-    return !(e && atoi(e) == 0);
-  }();
-  static const int heavy_side_min_log = [] {
-    const char* e = getenv("ARK_HIP_MSM_HEAVY_SIDE_MIN_LOG");   // tuning knob: smallest log2 n that takes the side stream
-    return e ? atoi(e) : 20;
-  }();
-  const bool heavy_side = heavy_side_env && ngroups == 1 && !piece && n >= ((size_t)1 << heavy_side_min_log);
-  if (ngroups == 2 || heavy_side) {
-    if (!ws.side) ARK_HIP_TRY(hipStreamCreateWithFlags(&ws.side, hipStreamNonBlocking));
-    for (auto& e : ws.grp_ev)
-      if (!e) ARK_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  const size_t lds_a = ((size_t)8 << HB) + (size_t)ptile * 8;
-  if (lds_a > PART_SCATTER_LDS_MAX) return -2;   // 2^14 super-buckets and more: beyond the n W < 2^32 the sort serves anyway
-  const u32 stage_cap = msm_part_stage_cap(LB);
-  const size_t lds_b = ((size_t)(1 << LB) + 1024 + stage_cap) * 4;
-  if (!ws.attr_set) {  // > 64 KiB of dynamic LDS needs the opt-in attribute (once per device; the workspace is per device)
-    ARK_HIP_TRY(hipFuncSetAttribute((const void*)msm_part_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)PART_SCATTER_LDS_MAX));
-    ARK_HIP_TRY(hipFuncSetAttribute((const void*)msm_part_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024 - 64));
-    ws.attr_set = true;
-  }
-  // super-buckets too large for one workgroup of pass B (skewed scalars) are finished in slices; below 2^18 keys per
-  // window none can exist (PART_BIG = 2^17 and a window of uniform digits is spread over all its super-buckets anyway)
-  static const bool big_env = [] {
-    const char* e = getenv("ARK_HIP_MSM_BIG_SLICES");
-    return !(e && atoi(e) == 0);
-  }();
-  const bool big_on = big_env && n > (size_t)2 * PART_BIG;
-  const size_t big_region = (size_t)nsuper + 2 * nb;   // u32 words per window group (each group's share is smaller)
-  if (big_on && ws.big.ensure(2 * big_region * 4)) return -3;
-  bool lazy = false;  // Fp384 G1: the accumulate kernels on carry-free 28-bit limbs (fp28.cuh); ARK_HIP_MSM_LAZY=0: saturated
-  if constexpr (C::LAZY_A) lazy = msm_lazy_enabled();
-  // Few slots with long runs (narrow scalars in one or two windows at large n): each run is walked by `run_parts` lanes
-  // (msm_accumulate_parts_kernel) until the lanes make two rounds over the chip's resident ones (2 waves x 4 SIMDs x 256 CUs x 64)
-  u32 run_parts = 1;
-  size_t parts_region = 0;
-  if (lazy && !pl.shared && !piece) {
-    static const size_t lanes_target = [] {
-      const char* e = getenv("ARK_HIP_MSM_PARTS_LANES");   // 0: never split runs
-      return e ? (size_t)atol(e) : (size_t)262144;   // two rounds of the resident lanes: measured better than one (u16 2^24 4.24 -> 3.82 ms,
-                                                     // u32 8.85 -> 6.88), four / eight rounds no better (profiles/r4_narrow_scalars.txt)
-    }();
-    double expect = (double)n * W;   // sorted entries: from the width classes where they were measured
-    if (have_widths) {
-      expect = 0.0;
-      for (int k = 1; k < MSM_WIDTH_CLASSES; k++) {
-        int need = (MSM_WIDTH_TOP[k] + 1 + c - 1) / c;
-        expect += (double)widths.count[k] * (need > W ? W : need);
-      }
-    }
-    const double mean_run = expect / (double)nb;
-    while (run_parts < 8 && nb * (size_t)(2 * run_parts) <= lanes_target && mean_run >= 32.0 * (2 * run_parts)) run_parts *= 2;
-    if (pl.parts) run_parts = pl.parts;   // small plain MSMs: the plan's narrow windows count on split runs (msm_make_plan)
-    if (const char* e = getenv("ARK_HIP_MSM_RUN_PARTS")) {   // test / tuning knob: force 1, 2, 4 or 8 lanes per run
-      const int v = atoi(e);
-      if (v == 1 || v == 2 || v == 4 || v == 8) run_parts = (u32)v;
-    }
-    if (run_parts > 1) {
-      parts_region = (size_t)run_parts * nb * Pt::BYTES;
-      if (ws.parts.ensure(2 * parts_region)) return -3;
-    }
-  }
-  const int W0 = ngroups == 2 ? (W + 1) / 2 : W;   // windows of group 0
-  struct Group {
-    int w0, Wg;
-    size_t slot0, nslots, nbk_g;   // first sort slot, sort slots, accumulated buckets
-    u32 *keys, *sorted, *offsets, *thist, *toff, *order, *sums, *ohist, *ooff, *hctr;
-    u32* big;                      // sliced pass B (msm_sort.cuh): [list of super-buckets, counters[nslots], cursors[nslots]]
-    u32* big_count;                // their number (hctr[8 + g], zeroed with the other counters)
-    uint2* part;
-    HeavyEntry* hlist;
-    uint2* hitems;
-    char *hpart, *buckets;
-    size_t max_heavy;
-  } grp[2];
-  for (int g = 0; g < ngroups; g++) {
-    Group& G = grp[g];
-    G.w0 = g == 0 ? 0 : W0;
-    G.Wg = g == 0 ? W0 : W - W0;
-    G.slot0 = (size_t)G.w0 << Bbits;
-    G.nslots = (size_t)G.Wg << Bbits;
-    G.nbk_g = pl.shared ? nbk : G.nslots;
-    G.keys = keys + (size_t)G.w0 * n;
-    G.sorted = sorted + (size_t)G.w0 * n;
-    G.part = part + (size_t)G.w0 * n;
-    G.offsets = offsets + G.slot0 + (size_t)g;                     // nslots + 1 entries each
-    G.thist = thist + ((size_t)G.w0 << HB) * ntiles;
-    G.toff = toff + ((size_t)G.w0 << HB) * ntiles + (size_t)g;     // (Wg << HB) * ntiles + 1 entries each
-    G.order = order + G.slot0;
-    G.sums = sums + (size_t)g * nsums;
-    const size_t noblk0 = ((size_t)(pl.shared ? nbk : ((size_t)W0 << Bbits)) + ORDER_TILE - 1) / ORDER_TILE;
-    G.ohist = (u32*)ws.ohist.p + (size_t)g * noblk0 * ORDER_BINS;
-    G.ooff = (u32*)ws.ooff.p + (size_t)g * (noblk0 * ORDER_BINS + 1);
-    G.hctr = (u32*)ws.hctr.p + 4 * g;
-    G.big = big_on ? (u32*)ws.big.p + (size_t)g * big_region : nullptr;
-    G.big_count = (u32*)ws.hctr.p + 8 + g;
-    const size_t ent0 = (size_t)n * W0;
-    const size_t mh0 = ent0 / 64 + 1, mi0 = ent0 / HEAVY_CHUNK + mh0 + 1;   // group 0's share of the heavy-run arrays
-    G.max_heavy = g == 0 ? (ngroups == 2 ? mh0 : max_heavy) : max_heavy - mh0;
-    G.hlist = (HeavyEntry*)ws.hlist.p + (g == 0 ? 0 : mh0);
-    G.hitems = (uint2*)ws.hitems.p + (g == 0 ? 0 : mi0);
-    G.hpart = (char*)ws.hpart.p + (g == 0 ? 0 : mi0) * Pt::BYTES;
-    G.buckets = d_buckets + (pl.shared ? 0 : G.slot0 * Pt::BYTES);
-  }
-  // partition sort of one group: (A) split by the low bucket bits with LDS counters, (B) finish each super-bucket in LDS;
-  // then the processing order of its buckets, heaviest load class first
-  auto sort_group = [&](const Group& G, hipStream_t st, bool mark) -> int {
-    const u32 nsuper_g = (u32)G.Wg << HB;
-    const size_t nthist_g = (size_t)nsuper_g * ntiles;
-    hipLaunchKernelGGL(msm_part_hist_kernel, dim3(ntiles, G.Wg), dim3(256), (size_t)4 << HB, st, G.keys, (u32)n, HB, LB,
-                       ntiles, ptile, G.thist);
-    scan_exclusive(G.thist, nthist_g, G.sums, G.toff, st);
-    if (mark && timing) ARK_HIP_TRY(hipEventRecord(job.ev[2], st));
-    hipLaunchKernelGGL(msm_part_scatter_kernel, dim3(ntiles, G.Wg), dim3(1024), lds_a, st, G.keys, (u32)n, HB, LB, ntiles,
-                       ptile, G.toff, G.part, compacted ? (const u32*)ws.cidx.p : (const u32*)nullptr);
-    hipLaunchKernelGGL(msm_part_finish_kernel, dim3(nsuper_g), dim3(1024), lds_b, st, G.part, G.toff, ntiles, LB, nsuper_g,
-                       stage_cap, big_on ? PART_BIG : 0u, G.big_count, G.big, G.offsets, G.sorted);
-    if (big_on) {
-      u32* const bigcnt = G.big + nsuper_g;     // counters and cursors of a listed super-bucket: zeroed by the finish kernel
-      u32* const cursor = bigcnt + G.nslots;
-      hipLaunchKernelGGL(msm_part_big_hist_kernel, dim3(PART_BIG_SLICES, PART_BIG_GRID_Y), dim3(1024), (size_t)4 << LB, st,
-                         G.part, G.toff, ntiles, LB, G.big_count, G.big, bigcnt);
-      hipLaunchKernelGGL(msm_part_big_place_kernel, dim3(PART_BIG_SLICES, PART_BIG_GRID_Y), dim3(1024),
-                         ((size_t)8 << LB) + 4096, st, G.part, G.toff, ntiles, LB, G.big_count, G.big, bigcnt, cursor, G.offsets,
-                         G.sorted);
-    }
-    int shift = 0;  // class width 2^shift so that the mean load falls around class 32..63
-    while ((mean_load >> shift) >= 64) shift++;
-    const u32 noblk_g = (u32)((G.nbk_g + ORDER_TILE - 1) / ORDER_TILE);
-    const int wsum = pl.shared ? W : 1;
-    hipLaunchKernelGGL(msm_order_hist_kernel, dim3(noblk_g), dim3(256), 0, st, G.offsets, G.nbk_g, shift, noblk_g, wsum, mwin,
-                       G.ohist);
-    scan_exclusive(G.ohist, (size_t)noblk_g * ORDER_BINS, G.sums, G.ooff, st);
-    hipLaunchKernelGGL(msm_order_scatter_kernel, dim3(noblk_g), dim3(256), 0, st, G.offsets, G.nbk_g, shift, noblk_g, wsum, mwin,
-                       G.ooff, G.order);
-    return 0;
-  };
-  // heavy runs + the lane-per-bucket kernel of one group
-  auto accumulate_group = [&](const Group& G, hipStream_t st) -> int {   // (st is reassigned below)
-    // runs too long for one lane: chunk partials by one wave each, combined per run (empty for uniform scalars)
-    hipLaunchKernelGGL(msm_find_heavy_kernel, dim3((u32)((G.nslots + 255) / 256)), dim3(256), 0, st, G.offsets, (u32)G.nslots,
-                       forced_thresh, G.hctr, G.hlist, G.hitems);
-    constexpr u32 LN = C::FA::LANES;                        // lanes per element of the accumulate field
-    constexpr size_t ACCB = AccOps<C>::ACC_BYTES;           // one parked accumulator (the form the kernels sum in)
-    const u32 hthreads = ACCB * (256 / LN) > 49152 ? 128 : 256;  // one LDS tree per wave, <= 48 KiB per workgroup
-    hipStream_t const acc_st = st;
-    if (heavy_side) {
-      ARK_HIP_TRY(hipEventRecord(ws.grp_ev[0], st));
-      ARK_HIP_TRY(hipStreamWaitEvent(ws.side, ws.grp_ev[0], 0));
-      st = ws.side;
-    }
-    hipLaunchKernelGGL((msm_heavy_partial_kernel<C>), dim3(1024), dim3(hthreads), (hthreads / LN) * ACCB, st,
-                       (const char*)d_points, G.sorted, G.offsets, G.hctr, (const uint2*)G.hitems, wstride, Bbits, (u32)G.nslots, G.hpart);
-    const u32 combine_grid = G.max_heavy < 16384 ? (u32)G.max_heavy : 16384u;  // grid-stride over the heavy runs
-    if (pl.shared)
-      hipLaunchKernelGGL((msm_heavy_combine_kernel<C, true>), dim3(combine_grid), dim3(ARK_HEAVY_COMBINE_THREADS), (ARK_HEAVY_COMBINE_THREADS / LN) * ACCB, st, G.hctr,
-                         (const HeavyEntry*)G.hlist, (const char*)G.hpart, HB, LB, G.offsets, G.sorted, 0, (char*)ws.hfinal.p);
-    else
-      hipLaunchKernelGGL((msm_heavy_combine_kernel<C, false>), dim3(combine_grid), dim3(ARK_HEAVY_COMBINE_THREADS), (ARK_HEAVY_COMBINE_THREADS / LN) * ACCB, st, G.hctr,
-                         (const HeavyEntry*)G.hlist, (const char*)G.hpart, HB, LB, G.offsets, G.sorted, accum, G.buckets);
-    if (heavy_side) {
-      ARK_HIP_TRY(hipEventRecord(ws.grp_ev[1], ws.side));
-      st = acc_st;
-    }
-    if (pl.shared) {
-      if constexpr (C::LAZY_A) {
-        if (lazy)
-          hipLaunchKernelGGL((msm_accumulate_shared_lazy_kernel<C>), dim3((u32)((nbk * C::FA::LANES + 255) / 256)), dim3(256), 0, st,
-                             (const char*)d_points, wstride, G.sorted, G.offsets, G.order, (u32)nbk, W, Bbits,
-                             (const u32*)G.hctr + 2, HB, LB, G.buckets);
-      }
-      if (!lazy)
-        hipLaunchKernelGGL((msm_accumulate_shared_kernel<C>), dim3((u32)((nbk * C::FA::LANES + 255) / 256)), dim3(256), 0, st,
-                           (const char*)d_points, wstride, G.sorted, G.offsets, G.order, (u32)nbk, W, Bbits,
-                           (const u32*)G.hctr + 2, HB, LB, G.buckets);
-      if (heavy_side) ARK_HIP_TRY(hipStreamWaitEvent(st, ws.grp_ev[1], 0));
-      hipLaunchKernelGGL((msm_apply_heavy_kernel<C>), dim3(1024), dim3(64), 0, st, (const u32*)G.hctr,
-                         (const HeavyEntry*)G.hlist, G.offsets, G.sorted, (const char*)ws.hfinal.p, W, Bbits, HB, LB, G.buckets);
-    } else {
-      if constexpr (C::LAZY_A) {
-        if (lazy && run_parts > 1) {
-          char* const pbuf = (char*)ws.parts.p + (size_t)(&G - grp) * parts_region;
-          hipLaunchKernelGGL((msm_accumulate_parts_kernel<C>), dim3((u32)((G.nslots * run_parts * C::FA::LANES + 255) / 256)),
-                             dim3(256), 0, st, (const char*)d_points, G.sorted, G.offsets, G.order, (u32)G.nslots,
-                             (const u32*)G.hctr + 2, HB, LB, run_parts, pbuf);
-          hipLaunchKernelGGL((msm_sum_parts_kernel<C>), dim3((u32)((G.nslots * C::FA::LANES + 255) / 256)), dim3(256), 0, st,
-                             G.offsets, (u32)G.nslots, (const u32*)G.hctr + 2, HB, LB, run_parts, (const char*)pbuf, accum,
-                             G.buckets);
-        } else if (lazy) {
-          hipLaunchKernelGGL((msm_accumulate_lazy_kernel<C>), dim3((u32)((G.nslots * C::FA::LANES + 255) / 256)), dim3(256), 0, st,
-                             (const char*)d_points, G.sorted, G.offsets, G.order, (u32)G.nslots, (const u32*)G.hctr + 2, HB, LB,
-                             accum, G.buckets);
-        }
-      }
-      if (!lazy)
-        hipLaunchKernelGGL((msm_accumulate_kernel<C>), dim3((u32)((G.nslots * C::FA::LANES + 255) / 256)), dim3(256), 0, st,
-                           (const char*)d_points, G.sorted, G.offsets, G.order, (u32)G.nslots, (const u32*)G.hctr + 2, HB, LB,
-                           accum, G.buckets);
-      if (heavy_side) ARK_HIP_TRY(hipStreamWaitEvent(st, ws.grp_ev[1], 0));
-    }
-    return 0;
-  };
-  if (int rc = sort_group(grp[0], stream, true)) return rc;
+  const bool heavy_side = knobs.heavy_side && ngroups == 1 && !piece && n >= ((size_t)1 << 20);
+
+  if (ws.reserve(n, pl, sg, rg, hg, Pt::BYTES, compacted, !piece, run_parts)) return -3;
+  if (int rc = msm_job_resources(job, rg.npairs * Pt::BYTES + 64, timing)) return rc;
+  if (int rc = ws.launch_resources(ngroups == 2 || heavy_side)) return rc;
+
+  MsmCall<C> call{ws, job, stream, timing, d_points, wstride, compacted ? ws.cscal.p : d_scalars, n, scalars_mont, piece,
+                  pl, sg, rg, hg, ngroups, heavy_side, lazy, compacted, run_parts, knobs.split_level,
+                  piece ? (char*)piece->buckets : (char*)ws.buckets.p, (piece && !piece->first) ? 1 : 0};
+  call.make_groups();
+  if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[0], stream));
+  ARK_HIP_TRY(hipMemsetAsync(ws.hctr.p, 0, 64, stream));  // per window group: [chunk items, heavy runs, threshold, -]; [3]: scalar-range error flag; [8 + g]: super-buckets of group g left to the sliced pass B
+  if (compacted) call.compact(d_scalars, n_all, pr);
+  call.digits(sbytes, sbits);
+  if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[1], stream));
+  if (int rc = call.sort_group(call.grp[0], stream, true)) return rc;
   if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[3], stream));
   if (ngroups == 2) {   // group 1's sort starts when group 0's accumulate kernel does
     ARK_HIP_TRY(hipEventRecord(ws.grp_ev[0], stream));
     ARK_HIP_TRY(hipStreamWaitEvent(ws.side, ws.grp_ev[0], 0));
-    if (int rc = sort_group(grp[1], ws.side, false)) return rc;
+    if (int rc = call.sort_group(call.grp[1], ws.side, false)) return rc;
     ARK_HIP_TRY(hipEventRecord(ws.grp_ev[1], ws.side));
   }
   if (piece && piece->after_prev) ARK_HIP_TRY(hipStreamWaitEvent(stream, piece->after_prev, 0));  // the buckets' previous writer
-  // bucket reduction of the windows [w0, w0 + wg): level 0 (chunked running sums), the bit-sliced sums, the chunk sums
-  constexpr u32 LNr = C::FA::LANES;
-  const bool two_level = nchunks > 1;
-  auto reduce_windows = [&](size_t w0, size_t wg, hipStream_t st) {
-    const size_t bo = w0 * m * Pt::BYTES;                       // (S, A) pairs of window w0
-    const size_t po = w0 * (size_t)Q * nchunks * Pt::BYTES;     // chunk partials of window w0
-    // level 0: the two chains of a chunk on one lane (2 L0 dependent additions) or on two waves (L0 + 1, twice the lanes):
-    // the split form where its lanes still fit the chip's resident ones -- 2 waves x 1024 SIMDs (ARK_HIP_MSM_SPLIT_LEVEL=0/1 forces)
-    static const int split_env = [] { const char* e = getenv("ARK_HIP_MSM_SPLIT_LEVEL"); return e ? atoi(e) : -1; }();
-    // measured (profiles/r5_reduce_split_level.txt, BLS12-381 G1): 2^16 0.48 -> 0.44 ms, 2^18 0.70 -> 0.54, 2^20 0.89 -> 0.71
-    // (split lanes <= 131 072: one round of the chip); 2^23 2.31 -> 2.00 (L0 = 32: 33 steps instead of 64 outweigh the 1.75
-    // rounds of 229 376 lanes); 2^21 / 2^22 (L0 = 8, 245 760 lanes) 1.15 -> 1.21 / equal; 2^24, 2^26 equal; the lane-pair
-    // curves (G2) lose 2-3 % everywhere: off there
-    const u32 nfull_g = w0 >= red_full ? 0u : (u32)std::min<size_t>(wg, red_full - w0);   // full windows among [w0, w0 + wg)
-    const MsmLevelGeom geom{L0, (u32)mwin, (u32)m, (u32)mn, nfull_g, (u32)(nfull_g * m + (wg - nfull_g) * mn)};
-    const size_t split_lanes = m * wg * 2;   // (the rule was fitted on the windows' nominal lanes)
-    const bool split_level = split_env >= 0 ? split_env != 0
-                                            : (LNr == 1 && L0 >= 2 && (split_lanes <= 131072 || (L0 >= 16 && split_lanes <= 262144)));
-    if (split_level)
-      hipLaunchKernelGGL((msm_reduce_level_split_kernel<C>), dim3((u32)(((size_t)geom.total * LNr + 63) / 64)), dim3(128), 0, st,
-                         (const char*)d_buckets + w0 * mwin * Pt::BYTES, geom, (char*)ws.lvlS[0].p + bo,
-                         (char*)ws.lvlA[0].p + bo);
-    else
-    hipLaunchKernelGGL((msm_reduce_level_kernel<C>), dim3((u32)(((size_t)geom.total * LNr + 127) / 128)), dim3(128), 0, st,
-                       (const char*)d_buckets + w0 * mwin * Pt::BYTES, geom, (char*)ws.lvlS[0].p + bo,
-                       (char*)ws.lvlA[0].p + bo);
-    constexpr size_t ACCBr = AccOps<C>::ACC_BYTES;
-    const u32 rthreads = ACCBr * (256 / LNr) > 49152 ? 128 : 256;  // LDS tree within 48 KiB
-    if (two_digit) {
-      // lanes per row / column sum: the longest is walked in <= 8 steps by each (12 dependent additions with the tree at
-      // 128-element rows), which at 2^24 pairs is 1.2 waves per SIMD
-      constexpr u32 NSr = 64 / LNr;
-      const u32 longest = std::max<u32>(rows2, 1u << d2);
-      u32 lps = 1;
-      while (lps < NSr && lps * 8 < longest) lps <<= 1;
-      char* const rc = (char*)ws.lvlA[1].p + w0 * nsum2 * Pt::BYTES;
-      hipLaunchKernelGGL((msm_reduce_rowcol_kernel<C>), dim3((u32)((nsum2 + NSr / lps - 1) / (NSr / lps)), (u32)wg), dim3(64), 0, st,
-                         (const char*)ws.lvlS[0].p + bo, (const char*)ws.lvlA[0].p + bo, (u32)m, (u32)mn, nfull_g, d2, rows2, lps, rc);
-      hipLaunchKernelGGL((msm_reduce_bits2_kernel<C>), dim3(Q, (u32)wg), dim3(rthreads), (rthreads / LNr) * ACCBr, st,
-                         (const char*)rc, d2, rows2, nbits, (char*)ws.lvlS[1].p + po);
-      return;
-    }
-    hipLaunchKernelGGL((msm_reduce_bits_kernel<C>), dim3(nchunks, Q, (u32)wg), dim3(rthreads), (rthreads / LNr) * ACCBr, st,
-                       (const char*)ws.lvlS[0].p + bo, (const char*)ws.lvlA[0].p + bo, (u32)m, (u32)mn, nfull_g, nbits, chunk,
-                       (char*)ws.lvlS[1].p + po);
-    if (two_level)
-      hipLaunchKernelGGL((msm_sum_chunks_kernel<C>), dim3((u32)(wg * Q)), dim3(64), (64 / LNr) * AccOps<C>::ACC_BYTES, st,
-                         (const char*)ws.lvlS[1].p + po, (u32)(wg * Q), nchunks, (char*)ws.lvlA[1].p + w0 * Q * Pt::BYTES);
-  };
-  const bool whole_job = !piece || piece->last;   // (a non-final piece of a streamed MSM leaves the reduction to the last one)
-  // Two window groups: group 0's reduction -- latency-bound chains and LDS trees below ~2^22 pairs -- runs on the side stream
-  // UNDER group 1's accumulate kernel (the side stream has finished group 1's sort by then).
-  // Measured and OFF by default (ARK_HIP_MSM_SPLIT_REDUCE=1 enables): the reduction's additions compete with the accumulate
-  // kernel for the same vector ALU, and what the overlap hides is less than what two half-size launches add -- 2^20 3.82 ->
-  // 4.05 ms, 2^22 11.33 -> 11.66, 2^24 36.8 -> 37.9 with both overlaps on (profiles/r4_split_reduce_window_groups_ab.txt).
-  static const bool split_env = getenv("ARK_HIP_MSM_SPLIT_REDUCE") && getenv("ARK_HIP_MSM_SPLIT_REDUCE")[0] == '1';
-  const bool split_reduce = split_env && ngroups == 2 && whole_job && Wr == W;
-  if (int rc = accumulate_group(grp[0], stream)) return rc;
+  if (int rc = call.accumulate_group(call.grp[0], stream)) return rc;
   if (ngroups == 2) {
-    if (split_reduce) {
-      ARK_HIP_TRY(hipEventRecord(ws.grp_ev[0], stream));
-      ARK_HIP_TRY(hipStreamWaitEvent(ws.side, ws.grp_ev[0], 0));
-    }
     ARK_HIP_TRY(hipStreamWaitEvent(stream, ws.grp_ev[1], 0));
-    if (split_reduce) {
-      reduce_windows(0, (size_t)grp[0].Wg, ws.side);
-      ARK_HIP_TRY(hipEventRecord(ws.grp_ev[1], ws.side));
-    }
-    if (int rc = accumulate_group(grp[1], stream)) return rc;
+    if (int rc = call.accumulate_group(call.grp[1], stream)) return rc;
   }
   if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[4], stream));
   if (piece) ARK_HIP_TRY(hipEventRecord(piece->after_this, stream));
-  if (piece && !piece->last) {  // the reduction belongs to the last piece: only the scalar-range flag goes back
-    ARK_HIP_TRY(hipGetLastError());
-    ARK_HIP_TRY(hipMemcpyAsync((char*)job.pinned + npairs * Pt::BYTES, (const u32*)ws.hctr.p + 3, 4, hipMemcpyDeviceToHost, stream));
-    if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[5], stream));
-    ARK_HIP_TRY(hipEventRecord(job.done, stream));
-    job.pl = pl;
-    job.npairs = npairs;
-    job.timing = timing;
-    job.no_result = true;
-    job.busy = true;
-    return slot;
+  const char* d_sums = nullptr;
+  if (!piece || piece->last) {   // (a non-final piece of a streamed MSM leaves the reduction to the last one)
+    ARK_HIP_TRY(hipEventRecord(job.acc_done, stream));   // the accumulate kernels are through: the reduction's 0.4-9 ms remain
+    call.reduce(stream);
+    d_sums = rg.nchunks > 1 ? (const char*)ws.lvlA[1].p : (const char*)ws.lvlS[1].p;
   }
-
-  ARK_HIP_TRY(hipEventRecord(job.acc_done, stream));   // the accumulate kernels are through: the reduction's 0.4-9 ms remain
-  if (split_reduce) {
-    reduce_windows((size_t)grp[1].w0, (size_t)grp[1].Wg, stream);
-    ARK_HIP_TRY(hipStreamWaitEvent(stream, ws.grp_ev[1], 0));   // group 0's sums
-  } else {
-    reduce_windows(0, (size_t)Wr, stream);
-  }
-  const char* d_sums = two_level ? (const char*)ws.lvlA[1].p : (const char*)ws.lvlS[1].p;
-  ARK_HIP_TRY(hipGetLastError());
-  ARK_HIP_TRY(hipMemcpyAsync(job.pinned, d_sums, npairs * Pt::BYTES, hipMemcpyDeviceToHost, stream));
-  ARK_HIP_TRY(hipMemcpyAsync((char*)job.pinned + npairs * Pt::BYTES, (const u32*)ws.hctr.p + 3, 4, hipMemcpyDeviceToHost, stream));
-  if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[5], stream));
-  ARK_HIP_TRY(hipEventRecord(job.done, stream));
-  job.pl = pl;
-  job.nbits = nbits;
-  job.L0 = L0;
-  job.short_job = (double)n * (double)W <= 6.0e6;   // (up to ~2^18 full-width pairs)
-  job.Q = Q;
-  job.npairs = npairs;
-  job.d_sums = d_sums;
-  job.timing = timing;
-  job.busy = true;
+  if (int rc = call.finish(d_sums)) return rc;
   return slot;
 }
 

@@ -24,63 +24,11 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "fp.cuh"
+#include "msm_plan.hpp"
 
 namespace arkhip {
 
-static constexpr int PART_LO_BITS = 10;        // buckets per super-bucket = 2^10 by default (2^9 measured no better) ...
-static constexpr int PART_LO_BITS_MAX = 12;    // ... up to 2^12 where the window is wide (msm_part_split)
-static constexpr u32 PART_LDS_WORDS = (160 * 1024 - 64) / 4;  // dynamic LDS of the finish kernel, u32 words
-
-// Split of the B = c-1 bucket bits into HB super-bucket bits (pass A) and LB bits finished in LDS (pass B).  Pass A
-// keeps 2^HB counters per (window, 8192-key tile): its histogram array -- W * 2^HB * n/8192 counters, written and
-// scanned in bin-major order -- is what grows with wide windows, so HB is kept as small as pass B allows: a
-// super-bucket (n / 2^HB entries on average) must fit the finish kernel's LDS staging area (~32 K entries) and has at
-// most 2^12 buckets.
-static inline void msm_part_split(size_t n, int B, int* HB, int* LB) {
-  int hb = 0;
-  if (B > PART_LO_BITS) {
-    hb = B - PART_LO_BITS;                       // 2^10 buckets per super-bucket ...
-    if (hb > 9) {                                // ... unless that needs more than 2^9 counters per tile
-      hb = B - PART_LO_BITS_MAX;
-      if (hb < 9) hb = 9;
-    }
-    int lg = 0;
-    while (((size_t)1 << lg) < n) lg++;
-    if (hb < lg - 15) hb = lg - 15;              // super-bucket (n / 2^hb entries) within the LDS staging area
-    if (hb > B) hb = B;
-    if (const char* e = getenv("ARK_HIP_MSM_HB")) {   // tuning knob (tools/): super-bucket bits of pass A
-      const int v = atoi(e);
-      if (v >= 0 && v <= B && B - v <= PART_LO_BITS_MAX) hb = v;
-    }
-  } else {
-    // few buckets per window (narrow scalars: msm_u8 plans ONE window of 2^8): still split, or a single workgroup of
-    // pass B finishes the whole window (2^24 keys through one CU)
-    int lg = 0;
-    while (((size_t)1 << lg) < n) lg++;
-    hb = lg - 15;
-    if (hb < 0) hb = 0;
-    if (hb > B) hb = B;
-  }
-  *HB = hb;
-  *LB = B - hb;
-}
-// staging entries of the finish kernel for a given LB
-static inline u32 msm_part_stage_cap(int LB) { return PART_LDS_WORDS - 1024u - (1u << LB) - 16u; }
-static constexpr int PART_TILE = 8192;         // keys per workgroup in pass A (64 KiB of staged pairs) ...
-static constexpr int PART_TILE_BIG = 16384;    // ... 128 KiB where pass A has >= 2^11 super-buckets (n >= 2^26): the per-tile
-                                               // histogram array halves and the runs a tile writes per super-bucket double
-                                               // (2^26, c = 22: 4 entries = 32 B per run with 8192 keys)
-static constexpr size_t PART_SCATTER_LDS_MAX = 160 * 1024 - 4096 - 64;   // dynamic LDS the scatter kernel may ask for
-static inline u32 msm_part_tile(int HB) {
-  if (const char* e = getenv("ARK_HIP_MSM_TILE")) {   // tuning knob
-    const int v = atoi(e);
-    if (v == PART_TILE || (v == PART_TILE_BIG && ((size_t)8 << HB) + (size_t)PART_TILE_BIG * 8 <= PART_SCATTER_LDS_MAX)) return (u32)v;
-  }
-  // the big tile must fit the scatter kernel's LDS beside its 2 x 2^HB counters (HB = 11: 16 + 128 KiB; from HB = 12,
-  // i.e. n >= 2^27, it does not -- 32 + 128 KiB -- and the 8192-key tile stays)
-  const bool fits = ((size_t)8 << HB) + (size_t)PART_TILE_BIG * 8 <= PART_SCATTER_LDS_MAX;
-  return (HB >= 11 && fits) ? (u32)PART_TILE_BIG : (u32)PART_TILE;
-}
+// (the bucket-id split, the tile of pass A and the LDS budgets: msm_plan.hpp, msm_sort_geometry)
 static constexpr u32 PART_KEY_NONE = 0xffffffffu;
 static constexpr int PART_MLP = 8;             // global loads a lane keeps in flight in the sweeps of the sort kernels
 static constexpr int PART_OUT_MLP = 4;         // ... in the scatter kernel's output loop (8-byte pairs; 64 VGPRs keep two workgroups per CU)
@@ -361,7 +309,6 @@ static __global__ void __launch_bounds__(1024) msm_part_finish_kernel(const uint
 //   big_place   every slice scans the global counters (-> bucket offsets, written by slice 0), counts its slice again,
 //               reserves its share of every bucket with one global atomic per non-empty bucket, and places its entries.
 // The order inside a bucket depends on the order the slices reserve in -- unspecified already (see the header).
-static constexpr u32 PART_BIG = 1u << 17;
 static constexpr u32 PART_BIG_SLICES = 16;
 static constexpr u32 PART_BIG_GRID_Y = 32;     // listed super-buckets are walked with this stride
 

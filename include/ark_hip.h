@@ -515,6 +515,11 @@ int ark_hip_test_msm_host_fold(int curve, const uint64_t* parts, int windows, in
  * out = sum_w 2^(off_w) (A_w + l0 sum_b 2^b U_(w,b)). */
 int ark_hip_test_msm_host_fold_l0(int curve, const uint64_t* parts, int windows, int nbits, int l0, const int* widths,
                                   uint64_t* out_xyz);
+/* HOST-ONLY test hook: the geometry of the bucket reduction (csrc/msm_plan.hpp, msm_reduce_geometry, every knob at its default)
+ * for the plan (c window bits, W windows, the top `narrow` one bit narrower, shared: a prepared set) on `curve`;
+ * resident_lanes: chunks the level-0 kernel keeps resident on the chip (0: unknown).
+ * out = L0, m, mn, nbits, Q, two_digit, d2, rows2, nsum2, chunk, nchunks, npairs. */
+int ark_hip_test_msm_reduce_geometry(int curve, int c, int W, int narrow, int shared, size_t resident_lanes, uint32_t out[12]);
 /* The carry-free limb arithmetic (csrc/fp28.cuh, fp28x2.cuh, fft.cuh Fft29) ONE OP AT A TIME ON RAW LIMBS: lane t reads `arity`
  * slots of L words (u32[L]: the W-bit limbs as the test chose them, not canonical words) at in[(t * arity + j) * L] and writes
  * L + 1 words at out[t * (L + 1)] (word L: the op's boolean result).  The Fp2L ops (op >= 40; field = BLS12-381 / BLS12-377 Fq)

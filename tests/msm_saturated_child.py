@@ -8,16 +8,16 @@ What the switch replaces, and which input below reaches it:
                                       latter).  Reached by batch_mul() below: about 700 scalars per G1 curve, among them 0, 1,
                                       r - 1, 2^256 - 1 and the unreduced scalar whose lower rows add up to the top row's entry,
                                       where the plain xyzz_madd must double.
-  msm_run, plain path (msm.cuh:2103)  msm_accumulate_lazy_kernel<C>, or msm_accumulate_parts_kernel<C> + msm_sum_parts_kernel<C>
-                                      when a run is walked by several lanes, -> msm_accumulate_kernel<C>, on every curve.
+  msm_run, plain path (msm.cuh,       msm_accumulate_lazy_kernel<C>, or msm_accumulate_parts_kernel<C> + msm_sum_parts_kernel<C>
+   MsmCall::accumulate_group)         when a run is walked by several lanes, -> msm_accumulate_kernel<C>, on every curve.
                                       Reached by every plain MSM below: the random vectors at n = 33, 1000, 4096, the edge
                                       cases (identity bases, P with P and P with -P in one bucket, one bucket per window),
                                       every base twice (the mixed addition's doubling branch in most buckets, msm_u16
                                       included) and thousands of copies of one base (the run of a lane-per-bucket lane
                                       holds the same point again and again; the heavy-run kernels are not switched).
-  msm_run, prepared set (:2238)       msm_accumulate_shared_lazy_kernel<C> -> msm_accumulate_shared_kernel<C>.  Reached by the
+  msm_run, prepared set (the same)    msm_accumulate_shared_lazy_kernel<C> -> msm_accumulate_shared_kernel<C>.  Reached by the
                                       PreparedBases runs of "every base twice" and "identical bases".
-  the plan (:1834, capi_msm.hip:285)  msm_make_plan(..., split_runs = false): between 256 and 73 728 pairs (G2: 24 576,
+  the plan (msm_plan.hpp)             msm_default_plan: msm_make_plan(..., split_runs = false): between 256 and 73 728 pairs (G2: 24 576,
                                       BLS12-377 G1: 20 480) the plain path no longer takes the narrow windows that count on
                                       split runs but the model's own width, so n = 1000 and 4096 run another window layout
                                       than in the parent process.  plan() below checks that ark_hip_msm_plan reports the

@@ -32,6 +32,13 @@ def test_every_chunk_length_and_stage2_form_matches_the_oracle(l0, form):
     child("grid", l0, form)
 
 
+@pytest.mark.parametrize("l0,form", [(21, "two_digit"), (7, "one_kernel")])
+def test_two_window_groups_match_the_oracle(l0, form):
+    """The same grid with two window groups forced (by default from 2^25 pairs): at 2^19 -- the smallest size that takes them
+    -- the second group's sort runs on the side stream under the first group's accumulate kernel."""
+    child("grid", l0, form, ARK_HIP_MSM_GROUPS="2")
+
+
 @pytest.mark.parametrize("l0,form", [(3, "two_digit"), (7, "two_digit"), (16, "two_digit"), (21, "two_digit"), (3, "one_kernel"),
                                      (32, "one_kernel")])
 def test_rare_branches(l0, form):
