@@ -48,6 +48,7 @@ void ark_hip_shutdown(void) {
       c->stage_b.release();
       c->stage_c.release();
       c->poly_work.release();
+      c->check_work.release();
       for (int j = 0; j < 2; j++) {
         c->ring_s[j].release();
         c->ring_b[j].release();
@@ -222,6 +223,75 @@ int ark_hip_sw_normalize_batch(int curve, const uint64_t* jac_points, size_t n, 
   ARK_HIP_TRY(hipMemcpyAsync(out_xy, c->stage_b.p, n * 2 * fb, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+// ---- base-set validation (pointcheck.cuh): coordinates are field elements, on the curve, in the prime-order subgroup ----
+static int sw_check_args(int curve, int checks, int method) {
+  if (curve < 0 || curve > 4 || checks < 1 || checks > 3 || method < 0 || method > 2) return ARK_HIP_ERR_ARG;
+  if (method == 2 && curve != ARK_HIP_BLS12_381_G1) return ARK_HIP_ERR_ARG;   // the endomorphism test is proven for this curve only
+  return 0;
+}
+// the summary words in context scratch, initialised on the stream in front of the first launch: {all ones, 0, 0, 0} -- the
+// first word is an atomicMin target, "nothing found" reads back as all ones and is reported as n
+static int sw_check_begin(Context* c) {
+  if (c->check_work.ensure(4 * sizeof(uint64_t))) return ARK_HIP_ERR_NOMEM;
+  ARK_HIP_TRY(hipMemsetAsync(c->check_work.p, 0xff, sizeof(uint64_t), c->stream));
+  ARK_HIP_TRY(hipMemsetAsync((char*)c->check_work.p + sizeof(uint64_t), 0, 3 * sizeof(uint64_t), c->stream));
+  return 0;
+}
+static int sw_check_end(Context* c, size_t n, uint64_t out[4]) {
+  ARK_HIP_TRY(hipMemcpyAsync(out, c->check_work.p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  if (out[0] > (uint64_t)n) out[0] = (uint64_t)n;
+  return 0;
+}
+
+int ark_hip_sw_check_device(int curve, const void* d_bases_xy, size_t n, int checks, int method, void* d_status, uint64_t out[4]) {
+  if (int rc = sw_check_args(curve, checks, method)) return rc;
+  if (!out || (n && !d_bases_xy)) return ARK_HIP_ERR_ARG;
+  if (n == 0) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    return 0;
+  }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (int rc = sw_check_begin(c)) return rc;
+  if (int rc = sw_check_dispatch(curve, d_bases_xy, n, 0, checks, method, d_status, c->check_work.p, c->stream)) return rc;
+  return sw_check_end(c, n, out);
+}
+
+// The same for a HOST slice: staged upload in chunks (ARK_HIP_CHECK_CHUNK_POINTS points each; default: 64 MiB of points), one
+// launch per chunk into the same summary words, the status bytes of a chunk downloaded behind its launch.
+int ark_hip_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, int method, uint8_t* status, uint64_t out[4]) {
+  if (int rc = sw_check_args(curve, checks, method)) return rc;
+  if (!out || (n && !bases_xy)) return ARK_HIP_ERR_ARG;
+  if (n == 0) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    return 0;
+  }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  const size_t ab = (size_t)CURVES[curve].fe_words * 16;
+  size_t chunk = ((size_t)64 << 20) / ab;
+  if (const char* e = getenv("ARK_HIP_CHECK_CHUNK_POINTS")) {
+    const long long v = atoll(e);
+    if (v > 0) chunk = (size_t)v;
+  }
+  if (chunk > n) chunk = n;
+  if (c->stage_a.cap < chunk * ab || (status && c->stage_b.cap < chunk)) {
+    if (int rc = sync_compute(c)) return rc;
+    if (c->stage_a.ensure(chunk * ab) || (status && c->stage_b.ensure(chunk))) return ARK_HIP_ERR_NOMEM;
+  }
+  if (int rc = sw_check_begin(c)) return rc;
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = n - off < chunk ? n - off : chunk;
+    if (int rc = c->stager.upload(c->stage_a.p, (const char*)bases_xy + off * ab, m * ab, c->stream)) return rc;
+    if (int rc = sw_check_dispatch(curve, c->stage_a.p, m, off, checks, method, status ? c->stage_b.p : nullptr, c->check_work.p,
+                                   c->stream))
+      return rc;
+    if (status) ARK_HIP_TRY(hipMemcpyAsync(status + off, c->stage_b.p, m, hipMemcpyDeviceToHost, c->stream));
+  }
+  return sw_check_end(c, n, out);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "capi_cache.hpp"
+#include "pointcheck.cuh"
 #include "lazytest_api.hpp"
 #include "relaxtest_api.hpp"
 using namespace arkhip;
@@ -181,6 +182,22 @@ int ark_hip_test_host_basefield_op(int curve, int op, const uint64_t* a, const u
     case ARK_HIP_BLS12_381_G2: host_field_ops<BLS12_381_G2::F>(op, a, b, r, n); return 0;
 #endif
     case ARK_HIP_BLS12_381_G1: host_field_ops<BLS12_381_G1::F>(op, a, b, r, n); return 0;
+  }
+  return ARK_HIP_ERR_ARG;
+}
+
+// sw_check_point (pointcheck.cuh) on the calling thread: the HOST build of the function the check kernel runs, no GPU involved
+int ark_hip_test_host_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, int method, uint8_t* status) {
+  if (curve < 0 || curve > 4 || checks < 1 || checks > 3 || method < 0 || method > 2 || (n && (!bases_xy || !status))) return ARK_HIP_ERR_ARG;
+  if (method == 2 && curve != ARK_HIP_BLS12_381_G1) return ARK_HIP_ERR_ARG;
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_G1: sw_check_host<BN254_G1>(bases_xy, n, checks, method, status); return 0;
+    case ARK_HIP_BLS12_377_G1: sw_check_host<BLS12_377_G1>(bases_xy, n, checks, method, status); return 0;
+    case ARK_HIP_BLS12_377_G2: sw_check_host<BLS12_377_G2>(bases_xy, n, checks, method, status); return 0;
+    case ARK_HIP_BLS12_381_G2: sw_check_host<BLS12_381_G2>(bases_xy, n, checks, method, status); return 0;
+#endif
+    case ARK_HIP_BLS12_381_G1: sw_check_host<BLS12_381_G1>(bases_xy, n, checks, method, status); return 0;
   }
   return ARK_HIP_ERR_ARG;
 }

@@ -33,6 +33,7 @@ struct MlePoint;
   int test_point_op_##NAME(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s); \
   int sw_add_affine_##NAME(const void* d_in, void* d_out, size_t n, const void* d_delta, hipStream_t s);        \
   int sw_normalize_batch_##NAME(const void* d_in, void* d_out, size_t n, hipStream_t s);                          \
+  int sw_check_##NAME(const void* d_in, size_t n, size_t base, int checks, int method, void* d_status, void* d_out, hipStream_t s); \
   int gfft_run_##NAME(void* d_jac, int k, const uint32_t* d_roots, const uint32_t* d_pre, const uint32_t* d_post, \
                       void* d_work, hipStream_t s);                                                                 \
   size_t gfft_work_bytes_##NAME(int k);

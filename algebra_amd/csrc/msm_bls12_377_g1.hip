@@ -4,6 +4,7 @@
 #include "batchmul.cuh"
 #include "devops.cuh"
 #include "gfft.cuh"
+#include "pointcheck.cuh"
 #include "internal.hpp"
 namespace arkhip {
 int msm_enqueue_BLS12_377_G1(MsmWorkspace& ws, const void* d_points, size_t wstride, const MsmPlan* prepared, const void* d_scalars,
@@ -35,6 +36,9 @@ int sw_add_affine_BLS12_377_G1(const void* in, void* out, size_t n, const void* 
 }
 int sw_normalize_batch_BLS12_377_G1(const void* in, void* out, size_t n, hipStream_t s) {
   return sw_normalize_batch_launch<BLS12_377_G1>(in, out, n, s);
+}
+int sw_check_BLS12_377_G1(const void* in, size_t n, size_t base, int checks, int method, void* d_status, void* d_out, hipStream_t s) {
+  return sw_check_launch<BLS12_377_G1>(in, n, base, checks, method, d_status, d_out, s);
 }
 int gfft_run_BLS12_377_G1(void* d_jac, int k, const uint32_t* d_roots, const uint32_t* d_pre, const uint32_t* d_post, void* d_work, hipStream_t s) {
   return gfft_run<BLS12_377_G1>(d_jac, k, d_roots, d_pre, d_post, d_work, s);

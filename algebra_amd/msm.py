@@ -9,6 +9,7 @@ Points and scalars are numpy uint64 arrays (host) or torch tensors on the GPU (d
 reference's in-memory layout: bases[n, 2*fe_words] (x|y Montgomery limbs, identity all-zero),
 scalars[n, 4]; the result is a numpy uint64 array of 3*fe_words limbs (Jacobian x|y|z).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -558,3 +559,38 @@ def normalize_batch(curve, points):
     torch.cuda.current_stream().synchronize()
     check(lib().ark_hip_sw_normalize_batch_device(cid, points.data_ptr(), out.data_ptr(), n), "normalize_batch")
     return out
+
+
+class BaseCheck(collections.namedtuple("BaseCheck", "ok first_bad not_reduced off_curve off_subgroup status")):
+    """Result of check_bases: ok = every point passed; first_bad = smallest index with a non-zero status (n if none);
+    not_reduced / off_curve / off_subgroup = number of points with status 1 / 2 / 3; status = the per-point bytes (numpy
+    array for a host input, CUDA uint8 tensor for a tensor) when asked for, else None."""
+    __slots__ = ()
+
+
+def check_bases(curve, points, subgroup=True, method=0, return_status=False, on_curve=True):
+    """Validate a base set where it lives (ark_hip_sw_check / ark_hip_sw_check_device): every coordinate a field element,
+    every point on the curve (Affine::is_on_curve, affine.rs:146-157) and, with subgroup=True, in the prime-order subgroup
+    (is_in_correct_subgroup_assuming_on_curve, short_weierstrass/mod.rs:82-90) -- the precondition of every MSM entry.
+    points: Affine points, numpy array or CUDA tensor (2*fe_words u64 per point); it is not modified.  method: 0 auto,
+    1 double-and-add over r, 2 the endomorphism test (BLS12-381 G1 only).  on_curve=False with subgroup=True is the
+    reference's "assuming on curve".  Nothing validates by default: this is the call that does."""
+    cid = cv.curve_id(curve)
+    checks = (1 if on_curve else 0) | (2 if subgroup else 0)
+    out = (C.c_uint64 * 4)()
+    if not _is_torch(points):
+        p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, cv.affine_words(cid))
+        n = p.shape[0]
+        status = np.zeros(n, dtype=np.uint8) if return_status else None
+        check(lib().ark_hip_sw_check(cid, p.ctypes.data_as(C.c_void_p), n, checks, method,
+                                     status.ctypes.data_as(C.c_void_p) if return_status else None, out), "ark_hip_sw_check")
+    else:
+        import torch
+        assert points.is_cuda and points.is_contiguous()
+        n = points.numel() * points.element_size() // (8 * cv.affine_words(cid))
+        status = torch.zeros(n, dtype=torch.uint8, device=points.device) if return_status else None
+        torch.cuda.current_stream().synchronize()
+        check(lib().ark_hip_sw_check_device(cid, points.data_ptr(), n, checks, method,
+                                            status.data_ptr() if return_status and n else None, out), "ark_hip_sw_check_device")
+    first, c1, c2, c3 = (int(v) for v in out)
+    return BaseCheck(c1 + c2 + c3 == 0, first, c1, c2, c3, status)

@@ -284,6 +284,30 @@ int ark_hip_sw_normalize_batch_device(int curve, const void* d_jac, void* d_out_
 /* the same from host memory: n Projective in, n Affine out (the Rust hook behind CurveGroup::normalize_batch) */
 int ark_hip_sw_normalize_batch(int curve, const uint64_t* jac_points, size_t n, uint64_t* out_xy);
 
+/* ---- base-set validation: what establishes the MSM entries' precondition on the device ----
+ * The reference runs two predicates when it deserialises a point: Affine::is_on_curve (ec/src/models/short_weierstrass/
+ * affine.rs:146-157) and SWCurveConfig::is_in_correct_subgroup_assuming_on_curve (short_weierstrass/mod.rs:82-90; overrides:
+ * curves/bn254/src/curves/g1.rs:59, bls12_381 g1.rs:69-85, g2.rs:75).  These entries run them over n Affine points (x | y,
+ * Montgomery form, identity = (0, 0)) where the points live.  Per point a status, the first stage that fails:
+ *   0  passed every requested stage
+ *   1  a coordinate is not a field element (an Fp component, read as an integer, is >= p).  Nothing can be computed for such
+ *      a point, so this stage runs under every mask.
+ *   2  not on the curve (y^2 != x^3 + b); the identity passes
+ *   3  on the curve (or assumed to be) but [r]P != O
+ * checks: bit 0 (1) = the curve equation, bit 1 (2) = the subgroup test; with both, the subgroup test runs only for points that
+ *   passed the equation; with bit 1 alone it is "assuming on curve", as in the reference.  BN254 G1 has cofactor one: its
+ *   subgroup test is the constant true.
+ * method: 1 = double-and-add over the bits of r on the exact mixed addition (the reference's default; every curve);
+ *   2 = phi(P) == -[x^2]P with phi(x, y) = (beta x, y) (Scott, eprint 2021/1130 section 6; bls12_381 g1.rs:69-85): BLS12-381 G1
+ *   only, ARK_HIP_ERR_ARG elsewhere; 0 = auto: method 2 on BLS12-381 G1 (the faster one there), method 1 elsewhere.  The
+ *   status does not depend on the method.
+ * d_status / status: n bytes, or NULL.  out[0] = smallest index with a non-zero status (n if none), out[1..3] = number of points
+ * with status 1, 2, 3.  n = 0 gives out = {0, 0, 0, 0}.  The input is not modified.  ARK_HIP_ERR_ARG for a bad curve / checks /
+ * method or a null pointer, before any device is touched.  Both entries synchronise before they return. */
+int ark_hip_sw_check_device(int curve, const void* d_bases_xy, size_t n, int checks, int method, void* d_status, uint64_t out[4]);
+/* the same for a host slice: staged upload in chunks, one launch per chunk */
+int ark_hip_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, int method, uint8_t* status, uint64_t out[4]);
+
 /* ---- Radix-2 evaluation domain ----
  * Mirror of Radix2EvaluationDomain<F>'s public fields (poly/src/domain/radix2/mod.rs:22-42). */
 typedef struct {
@@ -495,6 +519,9 @@ int ark_hip_test_basefield_op(int curve, int op, const uint64_t* a, const uint64
 /* the same ops (0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 dbl) through the HOST builds of the field arithmetic -- what the MSM's serial
  * tail runs on (64-bit limbs) -- on the calling thread: no GPU involved */
 int ark_hip_test_host_basefield_op(int curve, int op, const uint64_t* a, const uint64_t* b, uint64_t* r, size_t n);
+/* sw_check_point (csrc/pointcheck.cuh: the per-point function of ark_hip_sw_check_device) through its HOST build, on the calling
+ * thread: no GPU involved.  status: n bytes. */
+int ark_hip_test_host_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, int method, uint8_t* status);
 /* kind: 2 bucket += affine, 3 bucket -= affine, 4 bucket += bucket, 5 bucket double, 6 bucket -> jacobian,
  * 7 affine double_to_bucket.  acc/other/out are arrays of n elements. */
 int ark_hip_test_point_op(int curve, int kind, const uint64_t* acc, const uint64_t* other, uint64_t* out, size_t n);

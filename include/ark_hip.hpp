@@ -179,6 +179,48 @@ struct VariableBaseMSM {
   }
 };
 
+// ---- base-set validation (ark_hip_sw_check / ark_hip_sw_check_device) ------------------------------------------------
+// What establishes the precondition of every MSM entry above: coordinates are field elements, points are on the curve
+// (Affine::is_on_curve) and, with subgroup = true, in the prime-order subgroup
+// (SWCurveConfig::is_in_correct_subgroup_assuming_on_curve).  Nothing validates by default: these calls do.
+struct BaseCheck {
+  bool ok;               // every point passed
+  uint64_t first_bad;    // smallest index with a non-zero status (n if none)
+  uint64_t not_reduced, off_curve, off_subgroup;   // points with status 1, 2, 3
+  std::vector<uint8_t> status;                     // per point, when asked for (host form)
+};
+enum class CheckMethod : int { Auto = 0, Ladder = 1, Endomorphism = 2 };
+template <class Curve>
+inline BaseCheck check_bases(const typename Curve::AffineT* bases, size_t n, bool subgroup = true,
+                             CheckMethod method = CheckMethod::Auto, bool return_status = false) {
+  BaseCheck r{};
+  if (return_status) r.status.assign(n, 0);
+  uint64_t out[4];
+  check(ark_hip_sw_check(Curve::ID, reinterpret_cast<const uint64_t*>(bases), n, subgroup ? 3 : 1, static_cast<int>(method),
+                         return_status ? r.status.data() : nullptr, out),
+        "ark_hip_sw_check");
+  r.first_bad = out[0], r.not_reduced = out[1], r.off_curve = out[2], r.off_subgroup = out[3];
+  r.ok = out[1] + out[2] + out[3] == 0;
+  return r;
+}
+template <class Curve>
+inline BaseCheck check_bases(const std::vector<typename Curve::AffineT>& bases, bool subgroup = true,
+                             CheckMethod method = CheckMethod::Auto, bool return_status = false) {
+  return check_bases<Curve>(bases.data(), bases.size(), subgroup, method, return_status);
+}
+// the same for n Affine points in device memory; d_status: n bytes of device memory, or nullptr
+template <class Curve>
+inline BaseCheck check_bases_device(const void* d_bases, size_t n, bool subgroup = true, CheckMethod method = CheckMethod::Auto,
+                                    void* d_status = nullptr) {
+  BaseCheck r{};
+  uint64_t out[4];
+  check(ark_hip_sw_check_device(Curve::ID, d_bases, n, subgroup ? 3 : 1, static_cast<int>(method), d_status, out),
+        "ark_hip_sw_check_device");
+  r.first_bad = out[0], r.not_reduced = out[1], r.off_curve = out[2], r.off_subgroup = out[3];
+  r.ok = out[1] + out[2] + out[3] == 0;
+  return r;
+}
+
 // ---- an MSM in flight (ark_hip_msm_job) -------------------------------------------------------------------------------
 template <class Curve>
 class MsmJob {

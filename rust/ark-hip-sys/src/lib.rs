@@ -121,6 +121,13 @@ extern "C" {
     pub fn ark_hip_sw_normalize_batch_device(curve: c_int, d_jac: *const c_void, d_out_xy: *mut c_void, n: usize) -> c_int;
     /// `CurveGroup::normalize_batch` from host memory: n Projective in, n Affine out.
     pub fn ark_hip_sw_normalize_batch(curve: c_int, jac_points: *const u64, n: usize, out_xy: *mut u64) -> c_int;
+    /// Base-set validation on the device: per point 0 ok / 1 not a field element / 2 off the curve / 3 outside the subgroup;
+    /// `out`: smallest bad index (n if none) and the three counts.  `checks`: bit 0 curve equation, bit 1 subgroup.
+    pub fn ark_hip_sw_check_device(curve: c_int, d_bases_xy: *const c_void, n: usize, checks: c_int, method: c_int,
+                                   d_status: *mut c_void, out: *mut u64) -> c_int;
+    /// The same for a host slice (staged upload in chunks).
+    pub fn ark_hip_sw_check(curve: c_int, bases_xy: *const u64, n: usize, checks: c_int, method: c_int, status: *mut u8,
+                            out: *mut u64) -> c_int;
     pub fn ark_hip_fft_in_place(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64) -> c_int;
     pub fn ark_hip_ifft_in_place(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64) -> c_int;
     pub fn ark_hip_fft_in_place_degree_aware(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64,

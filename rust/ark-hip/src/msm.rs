@@ -454,6 +454,41 @@ pub fn sw_normalize_batch<P: HipServed>(curve: c_int, v: &[Projective<P>]) -> Op
     Some(out)
 }
 
+/// What `check_bases` found: `first_bad` is the smallest index with a non-zero status (`len` if none), the three counts are
+/// the points whose coordinates are not field elements, that are off the curve, and that are outside the subgroup.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct BaseCheck {
+    pub first_bad: usize,
+    pub not_reduced: u64,
+    pub off_curve: u64,
+    pub off_subgroup: u64,
+}
+impl BaseCheck {
+    pub fn ok(&self) -> bool {
+        self.not_reduced + self.off_curve + self.off_subgroup == 0
+    }
+}
+
+/// `Affine::is_on_curve` (ec/src/models/short_weierstrass/affine.rs:146-157) and, with `subgroup`,
+/// `SWCurveConfig::is_in_correct_subgroup_assuming_on_curve` (short_weierstrass/mod.rs:82-90) over a whole base slice on the
+/// device: what establishes the precondition of every MSM entry for points built with `new_unchecked` or read with
+/// `Validate::No`.  Nothing validates by default; `None` on a layout mismatch or a device error.
+pub fn check_bases<P: HipServed>(curve: c_int, bases: &[Affine<P>], subgroup: bool) -> Option<BaseCheck> {
+    let curve = served_id::<P>(curve);
+    if !layout_ok::<P, P::ScalarField>(curve) {
+        return None;
+    }
+    let mut out = [0u64; 4];
+    let checks = if subgroup { 3 } else { 1 };
+    let rc = unsafe {
+        sys::ark_hip_sw_check(curve, bases.as_ptr() as *const u64, bases.len(), checks, 0, core::ptr::null_mut(), out.as_mut_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(BaseCheck { first_bad: out[0] as usize, not_reduced: out[1], off_curve: out[2], off_subgroup: out[3] })
+}
+
 /// `ScalarMul::batch_mul` (ec/src/scalar_mul/mod.rs:106-109: `BatchMulPreprocessing::new(self, v.len())` +
 /// `batch_mul_with_preprocessing`) on the device: the table of multiples is built in GPU memory (sized from `v.len()` by the
 /// device's own cost rule), the batch is one mixed addition per table row and scalar, the affine results come back once.

@@ -13,6 +13,8 @@ ff-macros/src/montgomery/mod.rs:40-52 (TWO_ADIC_ROOT_OF_UNITY = generator^((p-1)
 
 Outputs:  oracle/constants.h  (64-bit limbs, C)      algebra_amd/csrc/params.hpp (32-bit limbs, C++)
           algebra_amd/csrc/curve_consts.hpp (subgroup generators, host side)
+          algebra_amd/csrc/check_consts.hpp (what the base-set check needs: COEFF_B, the subgroup order r and, for
+          BLS12-381 G1, the endomorphism constant beta and x^2 -- csrc/pointcheck.cuh)
 This script is the single place the decimal literals live; tests/test_constants.py re-derives
 them independently and checks both headers.
 """
@@ -72,6 +74,87 @@ def limbs(x, n, w):
 def c_arr(x, n, w):
     fmt = "0x%016xULL" if w == 64 else ("0x%08xu" if w == 32 else "0x%07xu")
     return "{" + ", ".join(fmt % v for v in limbs(x, n, w)) + "}"
+
+
+# ---- the base-set check (csrc/pointcheck.cuh) ----
+BLS12_381_X = -0xd201000000010000          # curves/bls12_381/src/curves/mod.rs: X = 0xd201000000010000, X_IS_NEGATIVE
+BN254_U = 4965661367192848881              # curves/bn254/src/curves/mod.rs: X
+
+
+def _aff_add(P, Q, p):
+    """textbook affine addition on y^2 = x^3 + b over Fp (None: the identity)"""
+    if P is None:
+        return Q
+    if Q is None:
+        return P
+    (x1, y1), (x2, y2) = P, Q
+    if x1 == x2:
+        if (y1 + y2) % p == 0:
+            return None
+        lam = 3 * x1 * x1 * pow(2 * y1, -1, p) % p
+    else:
+        lam = (y2 - y1) * pow(x2 - x1, -1, p) % p
+    x3 = (lam * lam - x1 - x2) % p
+    return (x3, (lam * (x1 - x3) - y1) % p)
+
+
+def _aff_mul(P, k, p):
+    acc = None
+    for bit in bin(k)[2:]:
+        acc = _aff_add(acc, acc, p)
+        if bit == "1":
+            acc = _aff_add(acc, P, p)
+    return acc
+
+
+def endo_beta_bls12_381():
+    """The cube root of unity beta in Fq with (beta x, y) = -[x^2](x, y) on the subgroup of BLS12-381 G1 (Scott, eprint
+    2021/1130 section 6; curves/bls12_381/src/curves/g1.rs:69-85), derived and ASSERTED on the generator."""
+    p = dict((n, q) for n, q, _ in FIELDS)["BLS12_381_FQ"]
+    r = dict((n, q) for n, q, _ in FIELDS)["BLS12_381_FR"]
+    x = BLS12_381_X
+    assert r == x ** 4 - x ** 2 + 1
+    G = [(c[6][0][0], c[6][1][0]) for c in CURVES if c[0] == "BLS12_381_G1"][0]
+    assert (G[1] * G[1] - G[0] ** 3 - 4) % p == 0 and _aff_mul(G, r, p) is None
+    w = pow(2, (p - 1) // 3, p)
+    assert w != 1 and pow(w, 3, p) == 1
+    T = _aff_mul(G, x * x, p)
+    want = (T[0], (-T[1]) % p)
+    hits = [b for b in (w, w * w % p) if (b * G[0] % p, G[1]) == want]
+    assert len(hits) == 1, "exactly one non-trivial cube root of unity satisfies phi(G) = -[x^2]G"
+    return hits[0], x * x
+
+
+def check_consts_header(fc):
+    fp = dict((n, q) for n, q, _ in FIELDS)
+    beta, x2 = endo_beta_bls12_381()
+    assert x2.bit_length() == 128
+    # BN254 G1 has cofactor one: #E(Fq) = q + 1 - t with t = 6u^2 + 1 is r itself (curves/bn254/src/curves/g1.rs:59)
+    assert fp["BN254_FQ"] + 1 - (6 * BN254_U ** 2 + 1) == fp["BN254_FR"]
+    h = []
+    h.append("// GENERATED by tools/gen_constants.py -- do not edit.")
+    h.append("// Per curve, what the base-set check (pointcheck.cuh) needs: COEFF_B (Montgomery form, one row per Fp component), the")
+    h.append("// subgroup order r as a plain integer (32-bit limbs) and whether the cofactor is one; for BLS12-381 G1 also x^2 and the")
+    h.append("// cube root of unity beta with (beta x, y) = -[x^2](x, y) on the subgroup (asserted on the generator at generation time).")
+    h.append("#pragma once\n#include <stdint.h>\nnamespace arkhip {")
+    for name, bf, sf, deg, _, b, _ in CURVES:
+        f = fc[bf]
+        p, n = f["p"], f["n64"] * 2
+        r = fp[sf]
+        endo = name == "BLS12_381_G1"
+        h.append("struct CHECK_%s {" % name)
+        h.append("  static constexpr bool COFACTOR_ONE = %s;" % ("true" if name == "BN254_G1" else "false"))
+        h.append("  static constexpr int R_BITS = %d;           // popcount %d" % (r.bit_length(), bin(r).count("1")))
+        h.append("  static constexpr uint32_t R[8] = %s;" % c_arr(r, 8, 32))
+        h.append("  static constexpr uint32_t B[%d][%d] = {%s};" % (deg, n, ", ".join(c_arr(c * f["R"] % p, n, 32) for c in b)))
+        h.append("  static constexpr bool HAS_ENDO = %s;" % ("true" if endo else "false"))
+        if endo:
+            h.append("  static constexpr int X2_BITS = %d;          // popcount %d" % (x2.bit_length(), bin(x2).count("1")))
+            h.append("  static constexpr uint32_t X2[8] = %s;" % c_arr(x2, 8, 32))
+            h.append("  static constexpr uint32_t ENDO_BETA[%d] = %s;" % (n, c_arr(beta * f["R"] % p, n, 32)))
+        h.append("};")
+    h.append("} // namespace arkhip")
+    return "\n".join(h) + "\n"
 
 
 def main():
@@ -168,7 +251,8 @@ def main():
         h.append("static const uint64_t GEN_%s[%d] = {%s};" % (name, len(words), ", ".join("0x%016xULL" % v for v in words)))
     h.append("} // namespace arkhip")
     open(os.path.join(root, "algebra_amd", "csrc", "curve_consts.hpp"), "w").write("\n".join(h) + "\n")
-    print("wrote oracle/constants.h, algebra_amd/csrc/params.hpp and curve_consts.hpp")
+    open(os.path.join(root, "algebra_amd", "csrc", "check_consts.hpp"), "w").write(check_consts_header(fc))
+    print("wrote oracle/constants.h, algebra_amd/csrc/params.hpp, curve_consts.hpp and check_consts.hpp")
 
 
 if __name__ == "__main__":
