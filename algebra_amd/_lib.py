@@ -98,6 +98,12 @@ SYMBOLS = {
     "ark_hip_sw_normalize_batch_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_sw_check_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_hip_sw_check": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_hip_sw_compressed_size": (C.c_int, [C.c_int]),
+    "ark_hip_sw_decompress_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_uint64)]),
+    "ark_hip_sw_decompress": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_hip_sw_compress_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ark_hip_sw_compress": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ark_hip_radix2_domain_new": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(Radix2DomainStruct)]),
     "ark_hip_radix2_domain_get_coset": (C.c_int, [C.c_int, C.POINTER(Radix2DomainStruct), C.c_void_p,
                                                   C.POINTER(Radix2DomainStruct)]),
@@ -154,6 +160,10 @@ TEST_SYMBOLS = {
     "ark_hip_test_basefield_op": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_host_basefield_op": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_host_sw_check": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+    "ark_hip_test_host_sw_decompress": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ark_hip_test_host_sw_compress": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ark_hip_test_coord_sqrt": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_test_host_coord_sqrt": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_point_op": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_msm_sharded_emulated": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                     C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.POINTER(C.c_int)]),

@@ -223,7 +223,7 @@ struct Context {
   FftWorkspace fft;
   DevBuf stage_a, stage_b, stage_c;    // host-pointer entry points: device copies
   DevBuf gfft_work, gfft_scal;         // transform over group elements: XYZZ scratch, per-position scalars
-  DevBuf check_work;                   // base-set check: the four summary words
+  DevBuf check_work;                   // base-set check / decompression: the summary words
   DevBuf poly_work;                    // polynomial ops: result slot, tile values / carries of every scan level, partial sums
   DevBuf ring_s[2], ring_b[2];         // double-buffered scalar / base uploads of the streaming entry points
   hipEvent_t ring_free[2] = {nullptr, nullptr}, ring_up[2] = {nullptr, nullptr};
@@ -423,6 +423,17 @@ inline int normalize_dispatch(int curve, const void* in, void* out, size_t n, hi
 inline int sw_check_dispatch(int curve, const void* in, size_t n, size_t base, int checks, int method, void* d_status, void* d_out,
                              hipStream_t st) {
 #define X(NAME) sw_check_##NAME(in, n, base, checks, method, d_status, d_out, st)
+  ARK_CURVE_SWITCH(curve, X);
+#undef X
+}
+inline int sw_decompress_dispatch(int curve, const void* d_bytes, size_t n, size_t base, int validate, int method, void* d_points,
+                                  void* d_status, void* d_out, hipStream_t st) {
+#define X(NAME) sw_decompress_##NAME(d_bytes, n, base, validate, method, d_points, d_status, d_out, st)
+  ARK_CURVE_SWITCH(curve, X);
+#undef X
+}
+inline int sw_compress_dispatch(int curve, const void* d_points, size_t n, void* d_bytes, hipStream_t st) {
+#define X(NAME) sw_compress_##NAME(d_points, n, d_bytes, st)
   ARK_CURVE_SWITCH(curve, X);
 #undef X
 }

@@ -226,6 +226,16 @@ int ark_hip_sw_normalize_batch(int curve, const uint64_t* jac_points, size_t n, 
 }
 
 // ---- base-set validation (pointcheck.cuh): coordinates are field elements, on the curve, in the prime-order subgroup ----
+// points per staged chunk of a host-slice entry: 64 MiB of points (ab bytes each) unless the environment variable `env` holds a
+// positive count (the tests cross chunk seams at small sizes with it); never more than n
+static size_t stage_chunk_points(const char* env, size_t ab, size_t n) {
+  size_t chunk = ((size_t)64 << 20) / ab;
+  if (const char* e = getenv(env)) {
+    const long long v = atoll(e);
+    if (v > 0) chunk = (size_t)v;
+  }
+  return chunk > n ? n : chunk;
+}
 static int sw_check_args(int curve, int checks, int method) {
   if (curve < 0 || curve > 4 || checks < 1 || checks > 3 || method < 0 || method > 2) return ARK_HIP_ERR_ARG;
   if (method == 2 && curve != ARK_HIP_BLS12_381_G1) return ARK_HIP_ERR_ARG;   // the endomorphism test is proven for this curve only
@@ -272,12 +282,7 @@ int ark_hip_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, 
   ARK_SCOPE(sc);
   Context* c = sc.c;
   const size_t ab = (size_t)CURVES[curve].fe_words * 16;
-  size_t chunk = ((size_t)64 << 20) / ab;
-  if (const char* e = getenv("ARK_HIP_CHECK_CHUNK_POINTS")) {
-    const long long v = atoll(e);
-    if (v > 0) chunk = (size_t)v;
-  }
-  if (chunk > n) chunk = n;
+  const size_t chunk = stage_chunk_points("ARK_HIP_CHECK_CHUNK_POINTS", ab, n);
   if (c->stage_a.cap < chunk * ab || (status && c->stage_b.cap < chunk)) {
     if (int rc = sync_compute(c)) return rc;
     if (c->stage_a.ensure(chunk * ab) || (status && c->stage_b.ensure(chunk))) return ARK_HIP_ERR_NOMEM;
@@ -292,6 +297,113 @@ int ark_hip_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, 
     if (status) ARK_HIP_TRY(hipMemcpyAsync(status + off, c->stage_b.p, m, hipMemcpyDeviceToHost, c->stream));
   }
   return sw_check_end(c, n, out);
+}
+
+// ---- compressed points (pointcodec.cuh): decompress (+ validate) and compress where the points live ----
+static const int SW_COMPRESSED_BYTES[5] = {32, 48, 48, 96, 96};
+int ark_hip_sw_compressed_size(int curve) { return curve < 0 || curve > 4 ? ARK_HIP_ERR_ARG : SW_COMPRESSED_BYTES[curve]; }
+
+static int sw_decompress_args(int curve, int validate, int method) {
+  if (curve < 0 || curve > 4 || validate < 0 || validate > 1 || method < 0 || method > 2) return ARK_HIP_ERR_ARG;
+  if (method == 2 && curve != ARK_HIP_BLS12_381_G1) return ARK_HIP_ERR_ARG;
+  return 0;
+}
+// device pointers: the bytes are read and written as 32-bit words, the points as 16-byte vectors like every point array here
+static bool sw_codec_ptrs_ok(int curve, const void* d_bytes, const void* d_points, size_t n) {
+  const uintptr_t b = (uintptr_t)d_bytes, p = (uintptr_t)d_points;
+  if ((b & 3) || (p & 3)) return false;
+  const size_t bl = n * (size_t)SW_COMPRESSED_BYTES[curve], pl = n * (size_t)CURVES[curve].fe_words * 16;
+  return b + bl <= p || p + pl <= b;   // no overlap
+}
+// the five summary words in context scratch: {all ones, 0, 0, 0, 0}, as for the base-set check
+static int sw_decompress_begin(Context* c) {
+  if (c->check_work.ensure(5 * sizeof(uint64_t))) return ARK_HIP_ERR_NOMEM;
+  ARK_HIP_TRY(hipMemsetAsync(c->check_work.p, 0xff, sizeof(uint64_t), c->stream));
+  ARK_HIP_TRY(hipMemsetAsync((char*)c->check_work.p + sizeof(uint64_t), 0, 4 * sizeof(uint64_t), c->stream));
+  return 0;
+}
+static int sw_decompress_end(Context* c, size_t n, uint64_t out[5]) {
+  ARK_HIP_TRY(hipMemcpyAsync(out, c->check_work.p, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  if (out[0] > (uint64_t)n) out[0] = (uint64_t)n;
+  return 0;
+}
+
+int ark_hip_sw_decompress_device(int curve, const void* d_bytes, size_t n, int validate, int method, void* d_points_xy, void* d_status,
+                                 uint64_t out[5]) {
+  if (int rc = sw_decompress_args(curve, validate, method)) return rc;
+  if (!out || (n && (!d_bytes || !d_points_xy))) return ARK_HIP_ERR_ARG;
+  if (n == 0) {
+    out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+    return 0;
+  }
+  if (!sw_codec_ptrs_ok(curve, d_bytes, d_points_xy, n)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (int rc = sw_decompress_begin(c)) return rc;
+  if (int rc = sw_decompress_dispatch(curve, d_bytes, n, 0, validate, method, d_points_xy, d_status, c->check_work.p, c->stream)) return rc;
+  return sw_decompress_end(c, n, out);
+}
+
+// The same for a HOST slice: the bytes go up in chunks (ARK_HIP_DECOMPRESS_CHUNK_POINTS points each; default: 64 MiB of points),
+// one launch per chunk into the same summary words with the chunk's base index; points and status bytes come down behind it.
+int ark_hip_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validate, int method, uint64_t* points_xy, uint8_t* status,
+                          uint64_t out[5]) {
+  if (int rc = sw_decompress_args(curve, validate, method)) return rc;
+  if (!out || (n && (!bytes || !points_xy))) return ARK_HIP_ERR_ARG;
+  if (n == 0) {
+    out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+    return 0;
+  }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  const size_t ab = (size_t)CURVES[curve].fe_words * 16, eb = (size_t)SW_COMPRESSED_BYTES[curve];
+  const size_t chunk = stage_chunk_points("ARK_HIP_DECOMPRESS_CHUNK_POINTS", ab, n);
+  if (c->stage_a.cap < chunk * eb || c->stage_c.cap < chunk * ab || (status && c->stage_b.cap < chunk)) {
+    if (int rc = sync_compute(c)) return rc;
+    if (c->stage_a.ensure(chunk * eb) || c->stage_c.ensure(chunk * ab) || (status && c->stage_b.ensure(chunk))) return ARK_HIP_ERR_NOMEM;
+  }
+  if (int rc = sw_decompress_begin(c)) return rc;
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = n - off < chunk ? n - off : chunk;
+    if (int rc = c->stager.upload(c->stage_a.p, (const char*)bytes + off * eb, m * eb, c->stream)) return rc;
+    if (int rc = sw_decompress_dispatch(curve, c->stage_a.p, m, off, validate, method, c->stage_c.p, status ? c->stage_b.p : nullptr,
+                                        c->check_work.p, c->stream))
+      return rc;
+    ARK_HIP_TRY(hipMemcpyAsync((char*)points_xy + off * ab, c->stage_c.p, m * ab, hipMemcpyDeviceToHost, c->stream));
+    if (status) ARK_HIP_TRY(hipMemcpyAsync(status + off, c->stage_b.p, m, hipMemcpyDeviceToHost, c->stream));
+  }
+  return sw_decompress_end(c, n, out);
+}
+
+// asynchronous on the context stream
+int ark_hip_sw_compress_device(int curve, const void* d_points_xy, size_t n, void* d_bytes) {
+  if (curve < 0 || curve > 4 || (n && (!d_points_xy || !d_bytes))) return ARK_HIP_ERR_ARG;
+  if (n == 0) return 0;
+  if (!sw_codec_ptrs_ok(curve, d_bytes, d_points_xy, n)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  return sw_compress_dispatch(curve, d_points_xy, n, d_bytes, sc.c->stream);
+}
+
+int ark_hip_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t* bytes) {
+  if (curve < 0 || curve > 4 || (n && (!points_xy || !bytes))) return ARK_HIP_ERR_ARG;
+  if (n == 0) return 0;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  const size_t ab = (size_t)CURVES[curve].fe_words * 16, eb = (size_t)SW_COMPRESSED_BYTES[curve];
+  const size_t chunk = stage_chunk_points("ARK_HIP_DECOMPRESS_CHUNK_POINTS", ab, n);
+  if (c->stage_a.cap < chunk * ab || c->stage_c.cap < chunk * eb) {
+    if (int rc = sync_compute(c)) return rc;
+    if (c->stage_a.ensure(chunk * ab) || c->stage_c.ensure(chunk * eb)) return ARK_HIP_ERR_NOMEM;
+  }
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = n - off < chunk ? n - off : chunk;
+    if (int rc = c->stager.upload(c->stage_a.p, (const char*)points_xy + off * ab, m * ab, c->stream)) return rc;
+    if (int rc = sw_compress_dispatch(curve, c->stage_a.p, m, c->stage_c.p, c->stream)) return rc;
+    ARK_HIP_TRY(hipMemcpyAsync(bytes + off * eb, c->stage_c.p, m * eb, hipMemcpyDeviceToHost, c->stream));
+  }
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 }  // extern "C"

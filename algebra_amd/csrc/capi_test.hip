@@ -7,6 +7,7 @@
 #include "capi_hostmath.hpp"
 #include "capi_cache.hpp"
 #include "pointcheck.cuh"
+#include "pointcodec.cuh"
 #include "lazytest_api.hpp"
 #include "relaxtest_api.hpp"
 using namespace arkhip;
@@ -123,6 +124,19 @@ elementwise_fn basefield_op_fn(int curve) {
   }
   return nullptr;
 }
+typedef int (*coord_sqrt_fn)(const void*, void*, void*, size_t, hipStream_t);
+coord_sqrt_fn coord_sqrt_fn_of(int curve) {
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case 0: return test_coord_sqrt_BN254_G1;
+    case 2: return test_coord_sqrt_BLS12_377_G1;
+    case 3: return test_coord_sqrt_BLS12_377_G2;
+    case 4: return test_coord_sqrt_BLS12_381_G2;
+#endif
+    case 1: return test_coord_sqrt_BLS12_381_G1;
+  }
+  return nullptr;
+}
 elementwise_fn point_op_fn(int curve) {
   switch (curve) {
 #ifndef ARK_HIP_DEV
@@ -200,6 +214,70 @@ int ark_hip_test_host_sw_check(int curve, const uint64_t* bases_xy, size_t n, in
     case ARK_HIP_BLS12_381_G1: sw_check_host<BLS12_381_G1>(bases_xy, n, checks, method, status); return 0;
   }
   return ARK_HIP_ERR_ARG;
+}
+
+// sw_decompress_point / sw_compress_point (pointcodec.cuh) on the calling thread: the HOST builds of the functions the codec kernels
+// run, no GPU involved
+int ark_hip_test_host_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validate, int method, uint64_t* points_xy,
+                                    uint8_t* status) {
+  if (curve < 0 || curve > 4 || validate < 0 || validate > 1 || method < 0 || method > 2 || (n && (!bytes || !points_xy))) return ARK_HIP_ERR_ARG;
+  if (method == 2 && curve != ARK_HIP_BLS12_381_G1) return ARK_HIP_ERR_ARG;
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_G1: sw_decompress_host<BN254_G1>(bytes, n, validate, method, points_xy, status); return 0;
+    case ARK_HIP_BLS12_377_G1: sw_decompress_host<BLS12_377_G1>(bytes, n, validate, method, points_xy, status); return 0;
+    case ARK_HIP_BLS12_377_G2: sw_decompress_host<BLS12_377_G2>(bytes, n, validate, method, points_xy, status); return 0;
+    case ARK_HIP_BLS12_381_G2: sw_decompress_host<BLS12_381_G2>(bytes, n, validate, method, points_xy, status); return 0;
+#endif
+    case ARK_HIP_BLS12_381_G1: sw_decompress_host<BLS12_381_G1>(bytes, n, validate, method, points_xy, status); return 0;
+  }
+  return ARK_HIP_ERR_ARG;
+}
+int ark_hip_test_host_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t* bytes) {
+  if (curve < 0 || curve > 4 || (n && (!points_xy || !bytes))) return ARK_HIP_ERR_ARG;
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_G1: sw_compress_host<BN254_G1>(points_xy, n, bytes); return 0;
+    case ARK_HIP_BLS12_377_G1: sw_compress_host<BLS12_377_G1>(points_xy, n, bytes); return 0;
+    case ARK_HIP_BLS12_377_G2: sw_compress_host<BLS12_377_G2>(points_xy, n, bytes); return 0;
+    case ARK_HIP_BLS12_381_G2: sw_compress_host<BLS12_381_G2>(points_xy, n, bytes); return 0;
+#endif
+    case ARK_HIP_BLS12_381_G1: sw_compress_host<BLS12_381_G1>(points_xy, n, bytes); return 0;
+  }
+  return ARK_HIP_ERR_ARG;
+}
+// the square root in the curve's coordinate field (Fp or Fp2): out = the root r with r <= -r, or zero with ok = 0
+int ark_hip_test_host_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n) {
+  if (curve < 0 || curve > 4 || (n && (!in || !out || !ok))) return ARK_HIP_ERR_ARG;
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_G1: coord_sqrt_host<BN254_G1>(in, out, ok, n); return 0;
+    case ARK_HIP_BLS12_377_G1: coord_sqrt_host<BLS12_377_G1>(in, out, ok, n); return 0;
+    case ARK_HIP_BLS12_377_G2: coord_sqrt_host<BLS12_377_G2>(in, out, ok, n); return 0;
+    case ARK_HIP_BLS12_381_G2: coord_sqrt_host<BLS12_381_G2>(in, out, ok, n); return 0;
+#endif
+    case ARK_HIP_BLS12_381_G1: coord_sqrt_host<BLS12_381_G1>(in, out, ok, n); return 0;
+  }
+  return ARK_HIP_ERR_ARG;
+}
+int ark_hip_test_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n) {
+  if (curve < 0 || curve > 4 || (n && (!in || !out || !ok))) return ARK_HIP_ERR_ARG;
+  coord_sqrt_fn fn = coord_sqrt_fn_of(curve);
+  if (!fn) return ARK_HIP_ERR_ARG;
+  if (n == 0) return 0;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  const size_t fb = (size_t)CURVES[curve].fe_words * 8;
+  if (c->stage_a.cap < n * fb || c->stage_b.cap < n || c->stage_c.cap < n * fb) {
+    if (int rc = sync_compute(c)) return rc;
+    if (c->stage_a.ensure(n * fb) || c->stage_b.ensure(n) || c->stage_c.ensure(n * fb)) return ARK_HIP_ERR_NOMEM;
+  }
+  ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, n * fb, hipMemcpyHostToDevice, c->stream));
+  if (int rc = fn(c->stage_a.p, c->stage_c.p, c->stage_b.p, n, c->stream)) return rc;
+  ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, n * fb, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipMemcpyAsync(ok, c->stage_b.p, n, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 int ark_hip_test_point_op(int curve, int kind, const uint64_t* acc, const uint64_t* other, uint64_t* out, size_t n) {

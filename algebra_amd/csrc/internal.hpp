@@ -34,6 +34,10 @@ struct MlePoint;
   int sw_add_affine_##NAME(const void* d_in, void* d_out, size_t n, const void* d_delta, hipStream_t s);        \
   int sw_normalize_batch_##NAME(const void* d_in, void* d_out, size_t n, hipStream_t s);                          \
   int sw_check_##NAME(const void* d_in, size_t n, size_t base, int checks, int method, void* d_status, void* d_out, hipStream_t s); \
+  int sw_decompress_##NAME(const void* d_bytes, size_t n, size_t base, int validate, int method, void* d_points, void* d_status, \
+                           void* d_out, hipStream_t s);                                                            \
+  int sw_compress_##NAME(const void* d_points, size_t n, void* d_bytes, hipStream_t s);                           \
+  int test_coord_sqrt_##NAME(const void* d_in, void* d_out, void* d_ok, size_t n, hipStream_t s);                 \
   int gfft_run_##NAME(void* d_jac, int k, const uint32_t* d_roots, const uint32_t* d_pre, const uint32_t* d_post, \
                       void* d_work, hipStream_t s);                                                                 \
   size_t gfft_work_bytes_##NAME(int k);

@@ -5,6 +5,7 @@
 #include "devops.cuh"
 #include "gfft.cuh"
 #include "pointcheck.cuh"
+#include "pointcodec.cuh"
 #include "internal.hpp"
 namespace arkhip {
 int msm_enqueue_BN254_G1(MsmWorkspace& ws, const void* d_points, size_t wstride, const MsmPlan* prepared, const void* d_scalars,
@@ -40,6 +41,11 @@ int sw_normalize_batch_BN254_G1(const void* in, void* out, size_t n, hipStream_t
 int sw_check_BN254_G1(const void* in, size_t n, size_t base, int checks, int method, void* d_status, void* d_out, hipStream_t s) {
   return sw_check_launch<BN254_G1>(in, n, base, checks, method, d_status, d_out, s);
 }
+int sw_decompress_BN254_G1(const void* d_bytes, size_t n, size_t base, int validate, int method, void* d_points, void* d_status, void* d_out,
+                     hipStream_t s) {
+  return sw_decompress_launch<BN254_G1>(d_bytes, n, base, validate, method, d_points, d_status, d_out, s);
+}
+int sw_compress_BN254_G1(const void* d_points, size_t n, void* d_bytes, hipStream_t s) { return sw_compress_launch<BN254_G1>(d_points, n, d_bytes, s); }
 int gfft_run_BN254_G1(void* d_jac, int k, const uint32_t* d_roots, const uint32_t* d_pre, const uint32_t* d_post, void* d_work, hipStream_t s) {
   return gfft_run<BN254_G1>(d_jac, k, d_roots, d_pre, d_post, d_work, s);
 }

@@ -4,6 +4,7 @@
 #include "testops.cuh"
 #include "lazytest.cuh"
 #include "relaxtest.cuh"
+#include "pointcodec.cuh"
 #include "internal.hpp"
 #ifndef ARK_TEST_CURVE
 #error "compile with -DARK_TEST_CURVE=BLS12_381_G1 (or another curve of curves.cuh)"
@@ -16,6 +17,10 @@ int ARK_CAT(test_basefield_op_, ARK_TEST_CURVE)(int op, const void* a, const voi
 }
 int ARK_CAT(test_point_op_, ARK_TEST_CURVE)(int kind, const void* acc, const void* other, void* out, size_t n, hipStream_t s) {
   return test_point_op_launch<ARK_TEST_CURVE>(kind, acc, other, out, n, s);
+}
+// the square root in the coordinate field (pointcodec.cuh), reachable with inputs that no curve point gives
+int ARK_CAT(test_coord_sqrt_, ARK_TEST_CURVE)(const void* in, void* out, void* ok, size_t n, hipStream_t s) {
+  return coord_sqrt_launch<ARK_TEST_CURVE>(in, out, ok, n, s);
 }
 // raw-limb hooks (lazytest.cuh): a G1 unit serves the FpL ops of its base field, a G2 unit the Fp2L ops over it
 int ARK_CAT(test_lazy_raw_op_, ARK_TEST_CURVE)(int op, int k, int h, const void* in, void* out, size_t n, hipStream_t s) {

@@ -594,3 +594,74 @@ def check_bases(curve, points, subgroup=True, method=0, return_status=False, on_
                                             status.data_ptr() if return_status and n else None, out), "ark_hip_sw_check_device")
     first, c1, c2, c3 = (int(v) for v in out)
     return BaseCheck(c1 + c2 + c3 == 0, first, c1, c2, c3, status)
+
+
+class BaseDecode(collections.namedtuple("BaseDecode", "ok first_bad bad_flags not_reduced no_root off_subgroup status")):
+    """Result of decompress_bases: ok = every encoding was accepted; first_bad = smallest index with a non-zero status (n if none);
+    bad_flags / not_reduced / no_root / off_subgroup = number of encodings with status 1 / 2 / 3 / 4; status = the per-point bytes
+    (numpy array for a host input, CUDA uint8 tensor for a tensor) when asked for, else None."""
+    __slots__ = ()
+
+
+def compressed_size(curve):
+    """bytes of one compressed point: 32 (BN254 G1), 48 (BLS12-381 / BLS12-377 G1), 96 (the G2 curves)"""
+    v = lib().ark_hip_sw_compressed_size(cv.curve_id(curve))
+    check(min(v, 0), "ark_hip_sw_compressed_size")
+    return v
+
+
+def decompress_bases(curve, data, validate=True, method=0, return_status=False):
+    """Compressed points -> Affine points where they live (ark_hip_sw_decompress / ark_hip_sw_decompress_device): what
+    Affine::deserialize_with_mode(.., Compress::Yes, Validate::Yes / No) does per point -- one square root in the base field
+    (affine.rs:129-143) and, with validate=True, the subgroup test of check_bases.  data: n encodings of compressed_size(curve)
+    bytes each (arkworks form on BN254 / BLS12-377, zcash form on BLS12-381), as bytes / a numpy uint8 array (-> numpy points,
+    through the host entry) or a CUDA uint8 tensor (-> CUDA tensor, through the device entry).  Returns (points [n, 2*fe_words],
+    BaseDecode); an encoding with a non-zero status gives the identity (0, 0)."""
+    cid = cv.curve_id(curve)
+    e = compressed_size(cid)
+    out = (C.c_uint64 * 5)()
+    words = cv.affine_words(cid)
+    if not _is_torch(data):
+        b = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data,
+                                 dtype=np.uint8).reshape(-1, e)
+        n = b.shape[0]
+        points = np.zeros((n, words), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint8) if return_status else None
+        check(lib().ark_hip_sw_decompress(cid, b.ctypes.data_as(C.c_void_p), n, 1 if validate else 0, method,
+                                          points.ctypes.data_as(C.c_void_p),
+                                          status.ctypes.data_as(C.c_void_p) if return_status else None, out), "ark_hip_sw_decompress")
+    else:
+        import torch
+        assert data.is_cuda and data.is_contiguous() and data.dtype == torch.uint8 and data.numel() % e == 0
+        n = data.numel() // e
+        points = torch.zeros((n, words), dtype=torch.int64, device=data.device)
+        status = torch.zeros(n, dtype=torch.uint8, device=data.device) if return_status else None
+        torch.cuda.current_stream().synchronize()
+        check(lib().ark_hip_sw_decompress_device(cid, data.data_ptr() if n else None, n, 1 if validate else 0, method,
+                                                 points.data_ptr() if n else None, status.data_ptr() if return_status and n else None,
+                                                 out), "ark_hip_sw_decompress_device")
+    first, c1, c2, c3, c4 = (int(v) for v in out)
+    return points, BaseDecode(c1 + c2 + c3 + c4 == 0, first, c1, c2, c3, c4, status)
+
+
+def compress_bases(curve, points):
+    """Affine points -> their canonical compressed encodings (ark_hip_sw_compress / ark_hip_sw_compress_device), [n, E] uint8:
+    numpy in, numpy out; CUDA tensor in, CUDA tensor out.  Precondition: reduced coordinates (what check_bases establishes)."""
+    cid = cv.curve_id(curve)
+    e = compressed_size(cid)
+    words = cv.affine_words(cid)
+    if not _is_torch(points):
+        p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, words)
+        out = np.zeros((p.shape[0], e), dtype=np.uint8)
+        check(lib().ark_hip_sw_compress(cid, p.ctypes.data_as(C.c_void_p), p.shape[0], out.ctypes.data_as(C.c_void_p)),
+              "ark_hip_sw_compress")
+        return out
+    import torch
+    assert points.is_cuda and points.is_contiguous()
+    n = points.numel() * points.element_size() // (8 * words)
+    out = torch.zeros((n, e), dtype=torch.uint8, device=points.device)
+    torch.cuda.current_stream().synchronize()
+    check(lib().ark_hip_sw_compress_device(cid, points.data_ptr() if n else None, n, out.data_ptr() if n else None),
+          "ark_hip_sw_compress_device")
+    check(lib().ark_hip_synchronize(), "ark_hip_synchronize")
+    return out

@@ -308,6 +308,37 @@ int ark_hip_sw_check_device(int curve, const void* d_bases_xy, size_t n, int che
 /* the same for a host slice: staged upload in chunks, one launch per chunk */
 int ark_hip_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, int method, uint8_t* status, uint64_t out[4]);
 
+/* ---- compressed points: decompress (+ validate) and compress where the points live ----
+ * The reference reads a point with Compress::Yes by taking one square root in the base field per point
+ * (Affine::get_ys_from_x_unchecked, ec/src/models/short_weierstrass/affine.rs:129-143) and, with Validate::Yes, the subgroup test
+ * above.  These entries do both over n encodings of E = ark_hip_sw_compressed_size(curve) bytes each:
+ *   BN254 G1 32, BLS12-377 G1 48, BLS12-377 G2 96: the arkworks form (short_weierstrass/mod.rs:125-193): x little-endian (Fp2:
+ *     c0 then c1), bit 7 of the last byte = "take the larger y", bit 6 = infinity.  Both bits: refused.  Every Fp component must be
+ *     < p once the two bits are cleared, also with the infinity bit; with it the result is the identity whatever x is.
+ *   BLS12-381 G1 48, G2 96: the zcash form (curves/bls12_381/src/curves/util.rs, g1.rs:97-147, g2.rs:124-140): x big-endian (Fp2:
+ *     c1 then c0), byte 0: bit 7 = compressed (required), bit 6 = infinity (then every other bit must be zero), bit 5 = larger y.
+ *   "Larger": y > -y on canonical residues; over Fp2 c1 decides, c0 if c1 = 0 (quadratic_extension.rs:443-453).
+ * Per point a status, the first stage that fails; 0 iff the reference returns Ok, and then the point is the reference's:
+ *   1  flags refused or malformed   2  a component is not a field element   3  x^3 + b has no square root
+ *   4  [r]P != O (only with validate = 1)
+ * A point with a non-zero status is written as the identity (0, 0).  Which SerializationError the reference picks is not mirrored.
+ * validate: 0 = Validate::No, 1 = Validate::Yes.  method: as for ark_hip_sw_check (0 auto, 1 ladder over r, 2 endomorphism test,
+ *   BLS12-381 G1 only); checked even when validate = 0.
+ * d_points_xy / points_xy: n Affine points out (x | y, Montgomery form).  d_status / status: n bytes, or NULL.
+ * out[0] = smallest index with a non-zero status (n if none), out[1..4] = number of points with status 1..4; n = 0 gives zeros.
+ * ARK_HIP_ERR_ARG before any device is touched: bad curve / validate / method, a null pointer with n > 0, a device pointer that is
+ * not 4-byte aligned, d_bytes and d_points_xy overlapping.  Device point arrays are 16-byte aligned, as everywhere in this library.
+ * Both decompress entries and ark_hip_sw_compress synchronise before they return; ark_hip_sw_compress_device is asynchronous on
+ * the context stream.  The host-slice entries, ark_hip_sw_decompress AND ark_hip_sw_compress, stage in chunks of 64 MiB of points
+ * (ARK_HIP_DECOMPRESS_CHUNK_POINTS overrides the chunk length of both, in points).
+ * Compress writes the canonical encoding; its precondition is reduced coordinates (what ark_hip_sw_check establishes).
+ * The uncompressed form (Compress::No) needs no square root and is not served. */
+int ark_hip_sw_compressed_size(int curve);                         /* 32 / 48 / 96; host only, ARK_HIP_ERR_ARG for a bad curve */
+int ark_hip_sw_decompress_device(int curve, const void* d_bytes, size_t n, int validate, int method, void* d_points_xy, void* d_status, uint64_t out[5]);
+int ark_hip_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validate, int method, uint64_t* points_xy, uint8_t* status, uint64_t out[5]);
+int ark_hip_sw_compress_device(int curve, const void* d_points_xy, size_t n, void* d_bytes);
+int ark_hip_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t* bytes);
+
 /* ---- Radix-2 evaluation domain ----
  * Mirror of Radix2EvaluationDomain<F>'s public fields (poly/src/domain/radix2/mod.rs:22-42). */
 typedef struct {
@@ -522,6 +553,14 @@ int ark_hip_test_host_basefield_op(int curve, int op, const uint64_t* a, const u
 /* sw_check_point (csrc/pointcheck.cuh: the per-point function of ark_hip_sw_check_device) through its HOST build, on the calling
  * thread: no GPU involved.  status: n bytes. */
 int ark_hip_test_host_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, int method, uint8_t* status);
+/* sw_decompress_point / sw_compress_point (csrc/pointcodec.cuh: the per-point functions of the codec kernels) through their HOST
+ * builds, on the calling thread: no GPU involved.  status may be NULL. */
+int ark_hip_test_host_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validate, int method, uint64_t* points_xy, uint8_t* status);
+int ark_hip_test_host_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t* bytes);
+/* the square root in the curve's coordinate field (Fp or Fp2, Montgomery form) on the device / through its host build:
+ * out = the root r with r <= -r, or zero with ok = 0 */
+int ark_hip_test_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n);
+int ark_hip_test_host_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n);
 /* kind: 2 bucket += affine, 3 bucket -= affine, 4 bucket += bucket, 5 bucket double, 6 bucket -> jacobian,
  * 7 affine double_to_bucket.  acc/other/out are arrays of n elements. */
 int ark_hip_test_point_op(int curve, int kind, const uint64_t* acc, const uint64_t* other, uint64_t* out, size_t n);

@@ -221,6 +221,65 @@ inline BaseCheck check_bases_device(const void* d_bases, size_t n, bool subgroup
   return r;
 }
 
+// ---- compressed points (ark_hip_sw_decompress* / ark_hip_sw_compress*) ------------------------------------------------
+// Affine::deserialize_with_mode(.., Compress::Yes, ..) over n encodings of compressed_size<Curve>() bytes each, and its inverse.
+struct BaseDecode {
+  bool ok;               // every encoding was accepted
+  uint64_t first_bad;    // smallest index with a non-zero status (n if none)
+  uint64_t bad_flags, not_reduced, no_root, off_subgroup;   // encodings with status 1, 2, 3, 4
+  std::vector<uint8_t> status;                               // per encoding, when asked for (host form)
+};
+template <class Curve>
+inline size_t compressed_size() {
+  return static_cast<size_t>(ark_hip_sw_compressed_size(Curve::ID));
+}
+namespace detail {
+inline BaseDecode base_decode(const uint64_t out[5], std::vector<uint8_t> status = {}) {
+  BaseDecode r{};
+  r.first_bad = out[0], r.bad_flags = out[1], r.not_reduced = out[2], r.no_root = out[3], r.off_subgroup = out[4];
+  r.ok = out[1] + out[2] + out[3] + out[4] == 0;
+  r.status = std::move(status);
+  return r;
+}
+}  // namespace detail
+// n encodings in host memory -> n Affine points in `points` (a refused encoding gives the identity)
+template <class Curve>
+inline BaseDecode decompress_bases(const uint8_t* bytes, size_t n, std::vector<typename Curve::AffineT>& points, bool validate = true,
+                                   CheckMethod method = CheckMethod::Auto, bool return_status = false) {
+  points.resize(n);
+  std::vector<uint8_t> status(return_status ? n : 0);
+  uint64_t out[5];
+  check(ark_hip_sw_decompress(Curve::ID, bytes, n, validate ? 1 : 0, static_cast<int>(method), reinterpret_cast<uint64_t*>(points.data()),
+                              return_status ? status.data() : nullptr, out),
+        "ark_hip_sw_decompress");
+  return detail::base_decode(out, std::move(status));
+}
+// the same in device memory; d_status: n bytes of device memory, or nullptr
+template <class Curve>
+inline BaseDecode decompress_bases_device(const void* d_bytes, size_t n, void* d_points, bool validate = true,
+                                          CheckMethod method = CheckMethod::Auto, void* d_status = nullptr) {
+  uint64_t out[5];
+  check(ark_hip_sw_decompress_device(Curve::ID, d_bytes, n, validate ? 1 : 0, static_cast<int>(method), d_points, d_status, out),
+        "ark_hip_sw_decompress_device");
+  return detail::base_decode(out);
+}
+// the canonical encodings of n points whose coordinates are reduced (what check_bases establishes)
+template <class Curve>
+inline std::vector<uint8_t> compress_bases(const typename Curve::AffineT* bases, size_t n) {
+  std::vector<uint8_t> bytes(n * compressed_size<Curve>());
+  check(ark_hip_sw_compress(Curve::ID, reinterpret_cast<const uint64_t*>(bases), n, bytes.data()), "ark_hip_sw_compress");
+  return bytes;
+}
+template <class Curve>
+inline std::vector<uint8_t> compress_bases(const std::vector<typename Curve::AffineT>& bases) {
+  return compress_bases<Curve>(bases.data(), bases.size());
+}
+// device memory to device memory, asynchronous on the context stream
+template <class Curve>
+inline void compress_bases_device(const void* d_bases, size_t n, void* d_bytes) {
+  check(ark_hip_sw_compress_device(Curve::ID, d_bases, n, d_bytes), "ark_hip_sw_compress_device");
+}
+
 // ---- an MSM in flight (ark_hip_msm_job) -------------------------------------------------------------------------------
 template <class Curve>
 class MsmJob {

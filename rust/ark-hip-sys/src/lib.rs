@@ -128,6 +128,20 @@ extern "C" {
     /// The same for a host slice (staged upload in chunks).
     pub fn ark_hip_sw_check(curve: c_int, bases_xy: *const u64, n: usize, checks: c_int, method: c_int, status: *mut u8,
                             out: *mut u64) -> c_int;
+    /// Bytes of one compressed point: 32 / 48 / 96 (host only).
+    pub fn ark_hip_sw_compressed_size(curve: c_int) -> c_int;
+    /// Compressed points -> Affine points on the device (one square root per point, optional subgroup test): per point 0 ok /
+    /// 1 flags refused / 2 not a field element / 3 no square root / 4 outside the subgroup; `out`: smallest bad index (n if none)
+    /// and the four counts.  arkworks form on BN254 / BLS12-377, zcash form on BLS12-381.
+    pub fn ark_hip_sw_decompress_device(curve: c_int, d_bytes: *const c_void, n: usize, validate: c_int, method: c_int,
+                                        d_points_xy: *mut c_void, d_status: *mut c_void, out: *mut u64) -> c_int;
+    /// The same for a host slice (staged in chunks).
+    pub fn ark_hip_sw_decompress(curve: c_int, bytes: *const u8, n: usize, validate: c_int, method: c_int, points_xy: *mut u64,
+                                 status: *mut u8, out: *mut u64) -> c_int;
+    /// Affine points -> their canonical compressed encodings; asynchronous on the context stream.
+    pub fn ark_hip_sw_compress_device(curve: c_int, d_points_xy: *const c_void, n: usize, d_bytes: *mut c_void) -> c_int;
+    /// The same for a host slice.
+    pub fn ark_hip_sw_compress(curve: c_int, points_xy: *const u64, n: usize, bytes: *mut u8) -> c_int;
     pub fn ark_hip_fft_in_place(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64) -> c_int;
     pub fn ark_hip_ifft_in_place(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64) -> c_int;
     pub fn ark_hip_fft_in_place_degree_aware(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64,

@@ -489,6 +489,57 @@ pub fn check_bases<P: HipServed>(curve: c_int, bases: &[Affine<P>], subgroup: bo
     Some(BaseCheck { first_bad: out[0] as usize, not_reduced: out[1], off_curve: out[2], off_subgroup: out[3] })
 }
 
+/// `Affine::deserialize_with_mode(.., Compress::Yes, ..)` over a whole slice of encodings on the device: one square root per point
+/// (`Affine::get_ys_from_x_unchecked`, ec/src/models/short_weierstrass/affine.rs:129-143) and, with `validate`, the subgroup test
+/// of `check_bases`.  `bytes`: `len / E` encodings of `E = ark_hip_sw_compressed_size(curve)` bytes each, back to back -- the
+/// serialisation of a `Vec<Affine>` carries a u64 length prefix in front of them, which the caller strips.
+/// `None`: no device, a layout mismatch or a length that is no multiple of `E`; `Some(Err(i))`: the reference would refuse
+/// encoding `i` (the first such); `Some(Ok(points))` otherwise.
+pub fn decompress_bases<P: HipServed>(curve: c_int, bytes: &[u8], validate: bool) -> Option<Result<Vec<Affine<P>>, usize>> {
+    let curve = served_id::<P>(curve);
+    if !layout_ok::<P, P::ScalarField>(curve) {
+        return None;
+    }
+    let e = unsafe { sys::ark_hip_sw_compressed_size(curve) };
+    if e <= 0 || bytes.len() % e as usize != 0 {
+        return None;
+    }
+    let n = bytes.len() / e as usize;
+    let mut out: Vec<Affine<P>> = Vec::with_capacity(n);
+    let mut summary = [0u64; 5];
+    let rc = unsafe {
+        sys::ark_hip_sw_decompress(curve, bytes.as_ptr(), n, validate as c_int, 0, out.as_mut_ptr() as *mut u64, core::ptr::null_mut(),
+                                   summary.as_mut_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    if summary[1] + summary[2] + summary[3] + summary[4] != 0 {
+        return Some(Err(summary[0] as usize));
+    }
+    unsafe { out.set_len(n) }; // every element written by the library
+    Some(Ok(out))
+}
+
+/// The canonical compressed encodings of a base slice (`serialize_with_mode(.., Compress::Yes)` of each point, back to back, without
+/// a length prefix), computed on the device.  `None`: no device or a layout mismatch.
+pub fn compress_bases<P: HipServed>(curve: c_int, bases: &[Affine<P>]) -> Option<Vec<u8>> {
+    let curve = served_id::<P>(curve);
+    if !layout_ok::<P, P::ScalarField>(curve) {
+        return None;
+    }
+    let e = unsafe { sys::ark_hip_sw_compressed_size(curve) };
+    if e <= 0 {
+        return None;
+    }
+    let mut out = vec![0u8; bases.len() * e as usize];
+    let rc = unsafe { sys::ark_hip_sw_compress(curve, bases.as_ptr() as *const u64, bases.len(), out.as_mut_ptr()) };
+    if rc != 0 {
+        return None;
+    }
+    Some(out)
+}
+
 /// `ScalarMul::batch_mul` (ec/src/scalar_mul/mod.rs:106-109: `BatchMulPreprocessing::new(self, v.len())` +
 /// `batch_mul_with_preprocessing`) on the device: the table of multiples is built in GPU memory (sized from `v.len()` by the
 /// device's own cost rule), the batch is one mixed addition per table row and scalar, the affine results come back once.

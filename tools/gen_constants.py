@@ -15,6 +15,8 @@ Outputs:  oracle/constants.h  (64-bit limbs, C)      algebra_amd/csrc/params.hpp
           algebra_amd/csrc/curve_consts.hpp (subgroup generators, host side)
           algebra_amd/csrc/check_consts.hpp (what the base-set check needs: COEFF_B, the subgroup order r and, for
           BLS12-381 G1, the endomorphism constant beta and x^2 -- csrc/pointcheck.cuh)
+          algebra_amd/csrc/codec_consts.hpp (what the compressed-point codec needs: square-root exponents, (p-1)/2,
+          1/2, the 2^46-th root of unity of BLS12-377 Fq, 1/beta of the two Fp2 -- csrc/pointcodec.cuh)
 This script is the single place the decimal literals live; tests/test_constants.py re-derives
 them independently and checks both headers.
 """
@@ -156,6 +158,73 @@ def check_consts_header(fc):
     h.append("} // namespace arkhip")
     return "\n".join(h) + "\n"
 
+# ---- the compressed-point codec (csrc/pointcodec.cuh) ----
+# curve -> (bytes per point, zcash form?)   arkworks: short_weierstrass/mod.rs:125-193; zcash: bls12_381/src/curves/util.rs
+CODEC_FORMS = {"BN254_G1": (32, False), "BLS12_381_G1": (48, True), "BLS12_377_G1": (48, False), "BLS12_377_G2": (96, False),
+               "BLS12_381_G2": (96, True)}
+
+
+def sqrt_plan(p, g):
+    """How csrc/pointcodec.cuh takes a square root in Fp, and what it costs in Fp products.
+    p = 3 mod 4: w = a^((p-3)/4), root = w a, accepted iff root^2 = a (then 1/root = w).
+    otherwise (BLS12-377 Fq, p - 1 = 2^s q): Tonelli-Shanks with fixed trip counts (RFC 9380 appendix I.4):
+    z = a^((q-1)/2), then s - 1 rounds of (i - 2 squarings, 3 products), i = s .. 2, accepted iff root^2 = a."""
+    if p % 4 == 3:
+        e = (p - 3) // 4
+        count = (e.bit_length() - 1) + (bin(e).count("1") - 1) + 2
+        return dict(p3mod4=True, e=e, s=1, products=count)
+    s, q = 0, p - 1
+    while q % 2 == 0:
+        q //= 2
+        s += 1
+    e = (q - 1) // 2
+    count = (e.bit_length() - 1) + (bin(e).count("1") - 1) + 3 + sum(i - 2 for i in range(2, s + 1)) + 3 * (s - 1) + 1
+    root = pow(g, q, p)
+    assert pow(root, 1 << (s - 1), p) == p - 1
+    return dict(p3mod4=False, e=e, s=s, products=count, root=root)
+
+
+def codec_consts_header(fc):
+    h = []
+    h.append("// GENERATED by tools/gen_constants.py -- do not edit.")
+    h.append("// What the compressed-point codec (pointcodec.cuh) needs.  Per base field: the square-root exponent E as a plain integer")
+    h.append("// ((p-3)/4 where p = 3 mod 4; (q-1)/2 with p - 1 = 2^S q otherwise), (p-1)/2 as a plain integer (y > -y iff the deciding")
+    h.append("// component is above it), p - 2 as a plain integer (the inversion exponent), 1/2 and the 2^S-th root of unity in Montgomery")
+    h.append("// form (-1 where S = 1), and the Fp products of one square root.")
+    h.append("// Per curve: bytes per point, which form, and for BLS12-377 G2 1/beta of the quadratic extension (Montgomery form).")
+    h.append("#pragma once\n#include <stdint.h>\nnamespace arkhip {")
+    for name in ("BN254_FQ", "BLS12_381_FQ", "BLS12_377_FQ"):
+        f = fc[name]
+        p, n = f["p"], f["n64"] * 2
+        plan = sqrt_plan(p, f["gen"])
+        m = lambda x: x * f["R"] % p
+        h.append("struct SQRT_%s {" % name)
+        h.append("  static constexpr bool P3MOD4 = %s;" % ("true" if plan["p3mod4"] else "false"))
+        h.append("  static constexpr int S = %d;                // two-adicity used by the root (1: none needed)" % plan["s"])
+        h.append("  static constexpr int E_BITS = %d;           // popcount %d" % (plan["e"].bit_length(), bin(plan["e"]).count("1")))
+        h.append("  static constexpr int PRODUCTS = %d;        // Fp products of one square root, acceptance test included" % plan["products"])
+        h.append("  static constexpr uint32_t E[%d] = %s;" % (n, c_arr(plan["e"], n, 32)))
+        h.append("  static constexpr uint32_t HALF_P[%d] = %s;" % (n, c_arr((p - 1) // 2, n, 32)))
+        h.append("  static constexpr uint32_t PM2[%d] = %s;" % (n, c_arr(p - 2, n, 32)))
+        h.append("  static constexpr uint32_t TWO_INV[%d] = %s;" % (n, c_arr(m(pow(2, -1, p)), n, 32)))
+        h.append("  static constexpr uint32_t ROOT[%d] = %s;" % (n, c_arr(m(plan.get("root", p - 1)), n, 32)))
+        h.append("};")
+    for name, bf, sf, deg, beta, b, _ in CURVES:
+        f = fc[bf]
+        p, n = f["p"], f["n64"] * 2
+        e, zc = CODEC_FORMS[name]
+        assert e == deg * f["n64"] * 8 and 8 * f["n64"] * 8 - f["bits"] >= (3 if zc else 2)
+        h.append("struct CODEC_%s {" % name)
+        h.append("  static constexpr int E = %d;" % e)
+        h.append("  static constexpr bool ZCASH = %s;" % ("true" if zc else "false"))
+        if deg == 2:
+            assert pow(beta % p, (p - 1) // 2, p) == p - 1
+        if deg == 2 and not (p % 4 == 3 and beta == -1):     # beta = -1 with p = 3 mod 4: the root of -a comes for free
+            h.append("  static constexpr uint32_t INV_BETA[%d] = %s;" % (n, c_arr(pow(beta, -1, p) * f["R"] % p, n, 32)))
+        h.append("};")
+    h.append("} // namespace arkhip")
+    return "\n".join(h) + "\n"
+
 
 def main():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -252,7 +321,8 @@ def main():
     h.append("} // namespace arkhip")
     open(os.path.join(root, "algebra_amd", "csrc", "curve_consts.hpp"), "w").write("\n".join(h) + "\n")
     open(os.path.join(root, "algebra_amd", "csrc", "check_consts.hpp"), "w").write(check_consts_header(fc))
-    print("wrote oracle/constants.h, algebra_amd/csrc/params.hpp, curve_consts.hpp and check_consts.hpp")
+    open(os.path.join(root, "algebra_amd", "csrc", "codec_consts.hpp"), "w").write(codec_consts_header(fc))
+    print("wrote oracle/constants.h, algebra_amd/csrc/params.hpp, curve_consts.hpp, check_consts.hpp and codec_consts.hpp")
 
 
 if __name__ == "__main__":
