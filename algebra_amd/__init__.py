@@ -19,4 +19,5 @@ from .msm import (BatchMulPreprocessing, batch_mul, ChunkedPippenger, HashMapPip
                   BaseCheck, check_bases, BaseDecode, compressed_size, decompress_bases, compress_bases)
 from .domain import Radix2EvaluationDomain  # noqa: F401
 from .poly import DeviceVec, poly_mul, poly_mul_host  # noqa: F401
+from .points import DevicePoints  # noqa: F401
 from .mle import DenseMultilinearExtension, mle_fold_plan, mle_fold_tiles  # noqa: F401

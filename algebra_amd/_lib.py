@@ -104,6 +104,11 @@ SYMBOLS = {
     "ark_hip_sw_decompress": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_hip_sw_compress_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ark_hip_sw_compress": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ark_hip_sw_mul_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p]),
+    "ark_hip_sw_mul": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p]),
+    "ark_hip_sw_add_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "ark_hip_sw_fold_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t,
+                                         C.c_void_p]),
     "ark_hip_radix2_domain_new": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(Radix2DomainStruct)]),
     "ark_hip_radix2_domain_get_coset": (C.c_int, [C.c_int, C.POINTER(Radix2DomainStruct), C.c_void_p,
                                                   C.POINTER(Radix2DomainStruct)]),
@@ -162,6 +167,10 @@ TEST_SYMBOLS = {
     "ark_hip_test_host_sw_check": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
     "ark_hip_test_host_sw_decompress": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ark_hip_test_host_sw_compress": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ark_hip_test_host_sw_mul": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_void_p]),
+    "ark_hip_test_host_sw_add": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "ark_hip_test_host_sw_fold": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t,
+                                            C.c_void_p]),
     "ark_hip_test_coord_sqrt": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_host_coord_sqrt": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_point_op": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -224,6 +224,7 @@ struct Context {
   DevBuf stage_a, stage_b, stage_c;    // host-pointer entry points: device copies
   DevBuf gfft_work, gfft_scal;         // transform over group elements: XYZZ scratch, per-position scalars
   DevBuf check_work;                   // base-set check / decompression: the summary words
+  DevBuf pointvec_work;                // point vectors: the window tables of one launch (pointvec.cuh)
   DevBuf poly_work;                    // polynomial ops: result slot, tile values / carries of every scan level, partial sums
   DevBuf ring_s[2], ring_b[2];         // double-buffered scalar / base uploads of the streaming entry points
   hipEvent_t ring_free[2] = {nullptr, nullptr}, ring_up[2] = {nullptr, nullptr};
@@ -436,6 +437,33 @@ inline int sw_compress_dispatch(int curve, const void* d_points, size_t n, void*
 #define X(NAME) sw_compress_##NAME(d_points, n, d_bytes, st)
   ARK_CURVE_SWITCH(curve, X);
 #undef X
+}
+inline int sw_vec_mul_dispatch(int curve, const void* d_points, int form, const void* d_scalars, size_t kstride, int mont, size_t n,
+                               void* d_out, void* d_tab, size_t slab, hipStream_t st) {
+#define X(NAME) sw_vec_mul_##NAME(d_points, form, d_scalars, kstride, mont, n, d_out, d_tab, slab, st)
+  ARK_CURVE_SWITCH(curve, X);
+#undef X
+}
+inline int sw_vec_fold_dispatch(int curve, const void* d_lo, const void* d_hi, int form, const uint64_t* a4, const uint64_t* b4, int mont,
+                                size_t n, void* d_out, void* d_tab, size_t slab, hipStream_t st) {
+#define X(NAME) sw_vec_fold_##NAME(d_lo, d_hi, form, a4, b4, mont, n, d_out, d_tab, slab, st)
+  ARK_CURVE_SWITCH(curve, X);
+#undef X
+}
+inline int sw_vec_add_dispatch(int curve, const void* d_a, const void* d_b, int negate_b, size_t n, void* d_out, hipStream_t st) {
+#define X(NAME) sw_vec_add_##NAME(d_a, d_b, negate_b, n, d_out, st)
+  ARK_CURVE_SWITCH(curve, X);
+#undef X
+}
+// points per staged chunk of a host-slice entry: 64 MiB of points (ab bytes each) unless the environment variable `env` holds a
+// positive count (the tests cross chunk seams at small sizes with it); never more than n
+inline size_t stage_chunk_points(const char* env, size_t ab, size_t n) {
+  size_t chunk = ((size_t)64 << 20) / ab;
+  if (const char* e = getenv(env)) {
+    const long long v = atoll(e);
+    if (v > 0) chunk = (size_t)v;
+  }
+  return chunk > n ? n : chunk;
 }
 inline int fr_mul_dispatch(int field, const void* a, const void* b, void* r, size_t n, hipStream_t st) {
 #define X(NAME) field_op_##NAME(2, a, b, r, n, st)

@@ -49,6 +49,7 @@ void ark_hip_shutdown(void) {
       c->stage_c.release();
       c->poly_work.release();
       c->check_work.release();
+      c->pointvec_work.release();
       for (int j = 0; j < 2; j++) {
         c->ring_s[j].release();
         c->ring_b[j].release();
@@ -226,16 +227,6 @@ int ark_hip_sw_normalize_batch(int curve, const uint64_t* jac_points, size_t n, 
 }
 
 // ---- base-set validation (pointcheck.cuh): coordinates are field elements, on the curve, in the prime-order subgroup ----
-// points per staged chunk of a host-slice entry: 64 MiB of points (ab bytes each) unless the environment variable `env` holds a
-// positive count (the tests cross chunk seams at small sizes with it); never more than n
-static size_t stage_chunk_points(const char* env, size_t ab, size_t n) {
-  size_t chunk = ((size_t)64 << 20) / ab;
-  if (const char* e = getenv(env)) {
-    const long long v = atoll(e);
-    if (v > 0) chunk = (size_t)v;
-  }
-  return chunk > n ? n : chunk;
-}
 static int sw_check_args(int curve, int checks, int method) {
   if (curve < 0 || curve > 4 || checks < 1 || checks > 3 || method < 0 || method > 2) return ARK_HIP_ERR_ARG;
   if (method == 2 && curve != ARK_HIP_BLS12_381_G1) return ARK_HIP_ERR_ARG;   // the endomorphism test is proven for this curve only

@@ -8,6 +8,7 @@
 #include "capi_cache.hpp"
 #include "pointcheck.cuh"
 #include "pointcodec.cuh"
+#include "pointvec.cuh"
 #include "lazytest_api.hpp"
 #include "relaxtest_api.hpp"
 using namespace arkhip;
@@ -245,6 +246,58 @@ int ark_hip_test_host_sw_compress(int curve, const uint64_t* points_xy, size_t n
     case ARK_HIP_BLS12_381_G1: sw_compress_host<BLS12_381_G1>(points_xy, n, bytes); return 0;
   }
   return ARK_HIP_ERR_ARG;
+}
+// pv_chain_point / pv_add_point (pointvec.cuh) on the calling thread: the HOST builds of the functions the point-vector kernels run,
+// no GPU involved.  impl: 0 = the form the device entry runs by default (carry-free limbs for G1, saturated for G2), 1 = saturated.
+int ark_hip_test_host_sw_mul(int curve, const uint64_t* points, int form, const uint64_t* scalars, size_t n_scalars,
+                             int scalars_are_montgomery, int impl, size_t n, uint64_t* out_xyz) {
+  if (curve < 0 || curve > 4 || form < 0 || form > 1 || impl < 0 || impl > 1 || (n_scalars != 1 && n_scalars != n) ||
+      (n && (!points || !scalars || !out_xyz)))
+    return ARK_HIP_ERR_ARG;
+  const size_t ks = n_scalars == 1 ? 0 : 8;
+#define CALL(C) pv_chain_host<C, 1>(points, nullptr, form, scalars, ks, nullptr, nullptr, scalars_are_montgomery, impl, n, out_xyz)
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_G1: CALL(BN254_G1); return 0;
+    case ARK_HIP_BLS12_377_G1: CALL(BLS12_377_G1); return 0;
+    case ARK_HIP_BLS12_377_G2: CALL(BLS12_377_G2); return 0;
+    case ARK_HIP_BLS12_381_G2: CALL(BLS12_381_G2); return 0;
+#endif
+    case ARK_HIP_BLS12_381_G1: CALL(BLS12_381_G1); return 0;
+  }
+  return ARK_HIP_ERR_ARG;
+#undef CALL
+}
+int ark_hip_test_host_sw_fold(int curve, const uint64_t* lo, const uint64_t* hi, int form, const uint64_t a[4], const uint64_t b[4],
+                              int scalars_are_montgomery, int impl, size_t n, uint64_t* out_xyz) {
+  if (curve < 0 || curve > 4 || form < 0 || form > 1 || impl < 0 || impl > 1 || !a || !b || (n && (!lo || !hi || !out_xyz))) return ARK_HIP_ERR_ARG;
+#define CALL(C) pv_chain_host<C, 2>(lo, hi, form, nullptr, 0, a, b, scalars_are_montgomery, impl, n, out_xyz)
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_G1: CALL(BN254_G1); return 0;
+    case ARK_HIP_BLS12_377_G1: CALL(BLS12_377_G1); return 0;
+    case ARK_HIP_BLS12_377_G2: CALL(BLS12_377_G2); return 0;
+    case ARK_HIP_BLS12_381_G2: CALL(BLS12_381_G2); return 0;
+#endif
+    case ARK_HIP_BLS12_381_G1: CALL(BLS12_381_G1); return 0;
+  }
+  return ARK_HIP_ERR_ARG;
+#undef CALL
+}
+int ark_hip_test_host_sw_add(int curve, const uint64_t* a_xyz, const uint64_t* b_xyz, int negate_b, size_t n, uint64_t* out_xyz) {
+  if (curve < 0 || curve > 4 || (n && (!a_xyz || !b_xyz || !out_xyz))) return ARK_HIP_ERR_ARG;
+#define CALL(C) pv_add_host<C>(a_xyz, b_xyz, negate_b, n, out_xyz)
+  switch (curve) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_G1: CALL(BN254_G1); return 0;
+    case ARK_HIP_BLS12_377_G1: CALL(BLS12_377_G1); return 0;
+    case ARK_HIP_BLS12_377_G2: CALL(BLS12_377_G2); return 0;
+    case ARK_HIP_BLS12_381_G2: CALL(BLS12_381_G2); return 0;
+#endif
+    case ARK_HIP_BLS12_381_G1: CALL(BLS12_381_G1); return 0;
+  }
+  return ARK_HIP_ERR_ARG;
+#undef CALL
 }
 // the square root in the curve's coordinate field (Fp or Fp2): out = the root r with r <= -r, or zero with ok = 0
 int ark_hip_test_host_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n) {

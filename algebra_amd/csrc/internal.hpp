@@ -37,6 +37,11 @@ struct MlePoint;
   int sw_decompress_##NAME(const void* d_bytes, size_t n, size_t base, int validate, int method, void* d_points, void* d_status, \
                            void* d_out, hipStream_t s);                                                            \
   int sw_compress_##NAME(const void* d_points, size_t n, void* d_bytes, hipStream_t s);                           \
+  int sw_vec_mul_##NAME(const void* d_points, int form, const void* d_scalars, size_t kstride, int mont, size_t n, void* d_out, \
+                        void* d_tab, size_t slab, hipStream_t s);                                                  \
+  int sw_vec_fold_##NAME(const void* d_lo, const void* d_hi, int form, const uint64_t* a4, const uint64_t* b4, int mont, size_t n, \
+                         void* d_out, void* d_tab, size_t slab, hipStream_t s);                                     \
+  int sw_vec_add_##NAME(const void* d_a, const void* d_b, int negate_b, size_t n, void* d_out, hipStream_t s);     \
   int test_coord_sqrt_##NAME(const void* d_in, void* d_out, void* d_ok, size_t n, hipStream_t s);                 \
   int gfft_run_##NAME(void* d_jac, int k, const uint32_t* d_roots, const uint32_t* d_pre, const uint32_t* d_post, \
                       void* d_work, hipStream_t s);                                                                 \

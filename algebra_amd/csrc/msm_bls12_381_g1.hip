@@ -1,4 +1,4 @@
-// Instantiation of the MSM pipeline, the fixed-base batch multiplication and the point-array kernels for BLS12_381_G1 (one TU per curve so
+// Instantiation of the MSM pipeline, the fixed-base batch multiplication, the point-array and point-vector kernels for BLS12_381_G1 (one TU per curve so
 // the five heavy template expansions compile in parallel).
 #include "msm.cuh"
 #include "batchmul.cuh"
@@ -6,6 +6,7 @@
 #include "gfft.cuh"
 #include "pointcheck.cuh"
 #include "pointcodec.cuh"
+#include "pointvec.cuh"
 #include "internal.hpp"
 namespace arkhip {
 int msm_enqueue_BLS12_381_G1(MsmWorkspace& ws, const void* d_points, size_t wstride, const MsmPlan* prepared, const void* d_scalars,
@@ -46,6 +47,18 @@ int sw_decompress_BLS12_381_G1(const void* d_bytes, size_t n, size_t base, int v
   return sw_decompress_launch<BLS12_381_G1>(d_bytes, n, base, validate, method, d_points, d_status, d_out, s);
 }
 int sw_compress_BLS12_381_G1(const void* d_points, size_t n, void* d_bytes, hipStream_t s) { return sw_compress_launch<BLS12_381_G1>(d_points, n, d_bytes, s); }
+int sw_vec_mul_BLS12_381_G1(const void* d_points, int form, const void* d_scalars, size_t kstride, int mont, size_t n, void* d_out, void* d_tab,
+                    size_t slab, hipStream_t s) {
+  return pv_chain_launch<BLS12_381_G1, 1>(d_points, nullptr, form, d_scalars, kstride, PvImm<1>{}, mont, n, d_out, d_tab, slab, s);
+}
+int sw_vec_fold_BLS12_381_G1(const void* d_lo, const void* d_hi, int form, const uint64_t* a4, const uint64_t* b4, int mont, size_t n, void* d_out,
+                     void* d_tab, size_t slab, hipStream_t s) {
+  const PvImm<2> imm = pv_imm2(a4, b4);
+  return pv_chain_launch<BLS12_381_G1, 2>(d_lo, d_hi, form, nullptr, 0, imm, mont, n, d_out, d_tab, slab, s);
+}
+int sw_vec_add_BLS12_381_G1(const void* d_a, const void* d_b, int negate_b, size_t n, void* d_out, hipStream_t s) {
+  return pv_add_launch<BLS12_381_G1>(d_a, d_b, negate_b, n, d_out, s);
+}
 int gfft_run_BLS12_381_G1(void* d_jac, int k, const uint32_t* d_roots, const uint32_t* d_pre, const uint32_t* d_post, void* d_work, hipStream_t s) {
   return gfft_run<BLS12_381_G1>(d_jac, k, d_roots, d_pre, d_post, d_work, s);
 }

@@ -339,6 +339,41 @@ int ark_hip_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validat
 int ark_hip_sw_compress_device(int curve, const void* d_points_xy, size_t n, void* d_bytes);
 int ark_hip_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t* bytes);
 
+/* ---- point vectors: elementwise scalar multiplication, elementwise sum, two-scalar fold, where the points live ----
+ * The reference has no batch form of these: `Projective *= ScalarField` (ec/src/models/short_weierstrass/group.rs:556-570) goes
+ * through mul_bigint to SWCurveConfig::mul_projective / mul_affine (short_weierstrass/mod.rs:101-109) and double_and_add(_affine)
+ * (ec/src/scalar_mul/mod.rs:29-60), `Projective += / -= Projective` is group.rs:450-538, and callers map them over a vector with
+ * rayon.  These entries do that over n points where they live -- one lane per point:
+ *   mul   out[i] = [k_i] P_i, with n scalars or ONE scalar shared by every point (n_scalars = 1)
+ *   add   out[i] = A_i + B_i, or A_i - B_i with negate_b = 1: the full addition (either side the identity, A = B, A = -B)
+ *   fold  out[i] = [a] Lo_i + [b] Hi_i with two shared scalars on ONE joint doubling chain (a round of an inner-product
+ *         argument: G' = [u^-1] G_lo + [u] G_hi)
+ * form: of the INPUT points.  ARK_HIP_FORM_AFFINE: x | y, identity (0, 0); ARK_HIP_FORM_PROJECTIVE: Jacobian x | y | z, identity
+ *   z = 0.  add takes Projective only.  Coordinates are Montgomery residues below p.  The OUTPUT is always Projective; as a group
+ *   element it is the reference's, its representative is not (compare after into_affine / normalize_batch).
+ * scalars: 4 x u64 each; Montgomery Fr (scalars_are_montgomery = 1) or canonical BigInt<4> (0), and then EVERY 256-bit value is
+ *   multiplied exactly, as in ark_hip_batch_mul (mul_bigint semantics: nothing is reduced mod r, so a point outside the
+ *   prime-order subgroup gets the multiple asked for).
+ * The three G1 curves run on the carry-free limbs of the MSM's accumulate kernels (ARK_HIP_MSM_LAZY=0: on saturated limbs, as
+ * the G2 curves always do).  A vector is walked in slabs of at most 2^17 lanes per launch (a launch keeps 8 multiples of each
+ * point in context scratch; ARK_HIP_POINTVEC_SLAB_LOG = 6..17 lowers the slab).
+ * ARK_HIP_ERR_ARG before any device is looked for: a bad curve / form / flag; n_scalars not 1 or n; a null pointer with n > 0; a
+ *   device pointer that is not 16-byte aligned; out overlapping an input.  EXACT aliasing (out == the input pointer) is allowed
+ *   where the input is Projective -- a lane reads its element before it writes it; with Affine input the strides differ and any
+ *   overlap is refused; out never overlaps the scalars.  n = 0 succeeds and touches nothing.
+ * The three _device entries are ASYNCHRONOUS on the context stream (ark_hip_synchronize, or any synchronising entry such as
+ * ark_hip_memcpy_d2h, waits for them); a and b of the fold are read before the call returns.  ark_hip_sw_mul (host slices)
+ * stages points and scalars in chunks of 64 MiB of points (ARK_HIP_POINTVEC_CHUNK_POINTS overrides the chunk length, in
+ * points) and synchronises before it returns. */
+enum { ARK_HIP_FORM_AFFINE = 0, ARK_HIP_FORM_PROJECTIVE = 1 };
+int ark_hip_sw_mul_device(int curve, const void* d_points, int form, const void* d_scalars, size_t n_scalars /* 1 or n */,
+                          int scalars_are_montgomery, size_t n, void* d_out_xyz);
+int ark_hip_sw_mul(int curve, const uint64_t* points, int form, const uint64_t* scalars, size_t n_scalars, int scalars_are_montgomery,
+                   size_t n, uint64_t* out_xyz);
+int ark_hip_sw_add_device(int curve, const void* d_a_xyz, const void* d_b_xyz, int negate_b, size_t n, void* d_out_xyz);
+int ark_hip_sw_fold_device(int curve, const void* d_lo, const void* d_hi, int form, const uint64_t a[4], const uint64_t b[4],
+                           int scalars_are_montgomery, size_t n, void* d_out_xyz);
+
 /* ---- Radix-2 evaluation domain ----
  * Mirror of Radix2EvaluationDomain<F>'s public fields (poly/src/domain/radix2/mod.rs:22-42). */
 typedef struct {
@@ -557,6 +592,14 @@ int ark_hip_test_host_sw_check(int curve, const uint64_t* bases_xy, size_t n, in
  * builds, on the calling thread: no GPU involved.  status may be NULL. */
 int ark_hip_test_host_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validate, int method, uint64_t* points_xy, uint8_t* status);
 int ark_hip_test_host_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t* bytes);
+/* pv_chain_point / pv_add_point (csrc/pointvec.cuh: the per-lane functions of ark_hip_sw_mul_device / _fold_device / _add_device)
+ * through their HOST builds, on the calling thread: no GPU involved.  Arguments as for the device entries, host pointers.
+ * impl: 0 = the form the device entry runs by default (carry-free limbs for the G1 curves, saturated for G2), 1 = saturated. */
+int ark_hip_test_host_sw_mul(int curve, const uint64_t* points, int form, const uint64_t* scalars, size_t n_scalars,
+                             int scalars_are_montgomery, int impl, size_t n, uint64_t* out_xyz);
+int ark_hip_test_host_sw_add(int curve, const uint64_t* a_xyz, const uint64_t* b_xyz, int negate_b, size_t n, uint64_t* out_xyz);
+int ark_hip_test_host_sw_fold(int curve, const uint64_t* lo, const uint64_t* hi, int form, const uint64_t a[4], const uint64_t b[4],
+                              int scalars_are_montgomery, int impl, size_t n, uint64_t* out_xyz);
 /* the square root in the curve's coordinate field (Fp or Fp2, Montgomery form) on the device / through its host build:
  * out = the root r with r <= -r, or zero with ok = 0 */
 int ark_hip_test_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n);

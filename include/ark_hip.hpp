@@ -848,4 +848,131 @@ class DenseMultilinearExtension {
   }
 };
 
+// ---- point vectors kept on the device: elementwise scalar multiplication, elementwise sum, two-scalar fold ----
+// The reference maps `Projective *= ScalarField` (ec/src/models/short_weierstrass/group.rs:556-570 -> mul_bigint ->
+// SWCurveConfig::mul_projective, short_weierstrass/mod.rs:101-109 -> double_and_add, ec/src/scalar_mul/mod.rs:29-60) and
+// `Projective += Projective` (group.rs:450-538) over a vector with rayon.  DevicePoints<Curve> owns ark_hip_malloc memory
+// holding Projective points and runs them where the points live (ark_hip_sw_mul_device / ark_hip_sw_add_device /
+// ark_hip_sw_fold_device).  Asynchronous on the library's stream; to_vec() waits.  Results are group elements: compare
+// after into_affine / normalize.  Mirrors: ark_hip::DevicePoints in rust/ark-hip/src/points.rs, algebra_amd.DevicePoints.
+template <class Curve>
+class DevicePoints {
+ public:
+  using AffineT = typename Curve::AffineT;
+  using ProjectiveT = typename Curve::ProjectiveT;
+  using Scalars = DeviceVec<Curve::SCALAR_FIELD>;
+  DevicePoints() = default;
+  static DevicePoints from_projective(const std::vector<ProjectiveT>& x) {
+    DevicePoints v;
+    v.alloc(x.size());
+    if (!x.empty()) check(ark_hip_memcpy_h2d(v.p_, x.data(), x.size() * sizeof(ProjectiveT)), "ark_hip_memcpy_h2d");
+    return v;
+  }
+  // Affine points (an SRS as it is stored), converted on the device: [1] P_i with the shared canonical scalar one
+  static DevicePoints from_affine(const std::vector<AffineT>& x) {
+    DevicePoints v;
+    v.alloc(x.size());
+    if (x.empty()) return v;
+    const size_t bytes = x.size() * sizeof(AffineT);
+    void* tmp = nullptr;
+    check(ark_hip_malloc(bytes + 32, &tmp), "ark_hip_malloc");
+    const uint64_t one[4] = {1, 0, 0, 0};
+    void* d_one = static_cast<char*>(tmp) + bytes;
+    int rc = ark_hip_memcpy_h2d(tmp, x.data(), bytes);
+    if (!rc) rc = ark_hip_memcpy_h2d(d_one, one, 32);
+    if (!rc) rc = ark_hip_sw_mul_device(Curve::ID, tmp, ARK_HIP_FORM_AFFINE, d_one, 1, 0, x.size(), v.p_);
+    const int rf = ark_hip_free(tmp);   // waits for the stream
+    check(rc, "ark_hip_sw_mul_device");
+    check(rf, "ark_hip_free");
+    return v;
+  }
+  DevicePoints(DevicePoints&& o) noexcept : p_(o.p_), len_(o.len_) { o.p_ = nullptr; o.len_ = 0; }
+  DevicePoints& operator=(DevicePoints&& o) noexcept {
+    if (this != &o) { release(); p_ = o.p_; len_ = o.len_; o.p_ = nullptr; o.len_ = 0; }
+    return *this;
+  }
+  DevicePoints(const DevicePoints&) = delete;
+  DevicePoints& operator=(const DevicePoints&) = delete;
+  ~DevicePoints() { release(); }
+  DevicePoints clone() const {
+    DevicePoints v;
+    v.alloc(len_);
+    if (len_) check(ark_hip_memcpy_d2d(v.p_, p_, len_ * sizeof(ProjectiveT)), "ark_hip_memcpy_d2d");
+    return v;
+  }
+  std::vector<ProjectiveT> to_vec() const {
+    std::vector<ProjectiveT> out(len_);
+    if (len_) check(ark_hip_memcpy_d2h(out.data(), p_, len_ * sizeof(ProjectiveT)), "ark_hip_memcpy_d2h");
+    return out;
+  }
+  size_t len() const { return len_; }
+  void* device_ptr() { return p_; }
+  const void* device_ptr() const { return p_; }
+  // self[i] *= scalars[i], the scalars (Montgomery Fr) already on the device
+  DevicePoints& mul_assign(const Scalars& scalars) {
+    if (scalars.len() != len_) throw Error(ARK_HIP_ERR_ARG, "one scalar per point");
+    check(ark_hip_sw_mul_device(Curve::ID, p_, ARK_HIP_FORM_PROJECTIVE, scalars.device_ptr(), len_, 1, len_, p_), "ark_hip_sw_mul_device");
+    return *this;
+  }
+  // self[i] *= k for one scalar (Montgomery Fr) shared by every point
+  DevicePoints& mul_assign(const Fr& k) {
+    Scalars s = Scalars::from_slice(&k, 1);
+    check(ark_hip_sw_mul_device(Curve::ID, p_, ARK_HIP_FORM_PROJECTIVE, s.device_ptr(), 1, 1, len_, p_), "ark_hip_sw_mul_device");
+    return *this;   // s is freed here: ark_hip_free waits for the stream
+  }
+  DevicePoints& operator+=(const DevicePoints& o) { return add_signed(o, 0); }
+  DevicePoints& operator-=(const DevicePoints& o) { return add_signed(o, 1); }
+  // [a] self[i] + [b] hi[i] on one joint doubling chain (a, b: Montgomery Fr)
+  DevicePoints fold(const DevicePoints& hi, const Fr& a, const Fr& b) const {
+    if (hi.len_ != len_) throw Error(ARK_HIP_ERR_ARG, "vectors of unequal length");
+    DevicePoints out;
+    out.alloc(len_);
+    check(ark_hip_sw_fold_device(Curve::ID, p_, hi.p_, ARK_HIP_FORM_PROJECTIVE, a.limbs.data(), b.limbs.data(), 1, len_, out.p_),
+          "ark_hip_sw_fold_device");
+    return out;
+  }
+  // CurveGroup::normalize_batch on the device, one download
+  std::vector<AffineT> normalize_to_vec() const {
+    std::vector<AffineT> out(len_);
+    if (!len_) return out;
+    void* tmp = nullptr;
+    check(ark_hip_malloc(len_ * sizeof(AffineT), &tmp), "ark_hip_malloc");
+    int rc = ark_hip_sw_normalize_batch_device(Curve::ID, p_, tmp, len_);
+    if (!rc) rc = ark_hip_memcpy_d2h(out.data(), tmp, len_ * sizeof(AffineT));
+    const int rf = ark_hip_free(tmp);
+    check(rc, "ark_hip_sw_normalize_batch_device");
+    check(rf, "ark_hip_free");
+    return out;
+  }
+
+ private:
+  void* p_ = nullptr;
+  size_t len_ = 0;
+  void alloc(size_t len) {
+    len_ = len;
+    if (len) check(ark_hip_malloc(len * sizeof(ProjectiveT), &p_), "ark_hip_malloc");
+  }
+  void release() {
+    if (p_) (void)ark_hip_free(p_);
+    p_ = nullptr;
+    len_ = 0;
+  }
+  DevicePoints& add_signed(const DevicePoints& o, int negate) {
+    if (o.len_ != len_) throw Error(ARK_HIP_ERR_ARG, "vectors of unequal length");
+    check(ark_hip_sw_add_device(Curve::ID, p_, o.p_, negate, len_, p_), "ark_hip_sw_add_device");
+    return *this;
+  }
+};
+// host slices through the staged entry (ark_hip_sw_mul): out[i] = [k_i] P_i, Montgomery Fr scalars, one per point or one for all
+template <class Curve>
+inline std::vector<typename Curve::ProjectiveT> sw_mul(const std::vector<typename Curve::AffineT>& points, const std::vector<Fr>& scalars) {
+  std::vector<typename Curve::ProjectiveT> out(points.size());
+  check(ark_hip_sw_mul(Curve::ID, reinterpret_cast<const uint64_t*>(points.data()), ARK_HIP_FORM_AFFINE,
+                       reinterpret_cast<const uint64_t*>(scalars.data()), scalars.size(), 1, points.size(),
+                       reinterpret_cast<uint64_t*>(out.data())),
+        "ark_hip_sw_mul");
+  return out;
+}
+
+
 }  // namespace ark_hip

@@ -17,6 +17,9 @@ pub const BLS12_381_G1: c_int = 1;
 pub const BLS12_377_G1: c_int = 2;
 pub const BLS12_377_G2: c_int = 3;
 pub const BLS12_381_G2: c_int = 4;
+/// form of the input points of the point-vector entries (`ark_hip_sw_mul_device`, ..): x | y, or Jacobian x | y | z
+pub const ARK_HIP_FORM_AFFINE: c_int = 0;
+pub const ARK_HIP_FORM_PROJECTIVE: c_int = 1;
 pub const ERR_SCALAR_RANGE: c_int = -4;
 pub const ERR_BUSY: c_int = -6;
 
@@ -142,6 +145,17 @@ extern "C" {
     pub fn ark_hip_sw_compress_device(curve: c_int, d_points_xy: *const c_void, n: usize, d_bytes: *mut c_void) -> c_int;
     /// The same for a host slice.
     pub fn ark_hip_sw_compress(curve: c_int, points_xy: *const u64, n: usize, bytes: *mut u8) -> c_int;
+    /// out[i] = [k_i] P_i over n points in device memory (one lane per point); `form`: of the input points (`ARK_HIP_FORM_*`),
+    /// the output is Projective and may be the input pointer when that is Projective; `n_scalars`: n, or 1 for one scalar shared
+    /// by every point; Montgomery Fr or canonical BigInt<4> (every 256-bit value multiplied exactly).  Asynchronous on the
+    /// context stream.
+    pub fn ark_hip_sw_mul_device(curve: c_int, d_points: *const c_void, form: c_int, d_scalars: *const c_void, n_scalars: usize, scalars_are_montgomery: c_int, n: usize, d_out_xyz: *mut c_void) -> c_int;
+    /// The same for host slices, staged in chunks; synchronises before it returns.
+    pub fn ark_hip_sw_mul(curve: c_int, points: *const u64, form: c_int, scalars: *const u64, n_scalars: usize, scalars_are_montgomery: c_int, n: usize, out_xyz: *mut u64) -> c_int;
+    /// out[i] = A_i + B_i (or A_i - B_i), Projective in and out: the full addition.  Asynchronous on the context stream.
+    pub fn ark_hip_sw_add_device(curve: c_int, d_a_xyz: *const c_void, d_b_xyz: *const c_void, negate_b: c_int, n: usize, d_out_xyz: *mut c_void) -> c_int;
+    /// out[i] = [a] Lo_i + [b] Hi_i with two shared scalars on one joint doubling chain.  Asynchronous on the context stream.
+    pub fn ark_hip_sw_fold_device(curve: c_int, d_lo: *const c_void, d_hi: *const c_void, form: c_int, a: *const u64, b: *const u64, scalars_are_montgomery: c_int, n: usize, d_out_xyz: *mut c_void) -> c_int;
     pub fn ark_hip_fft_in_place(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64) -> c_int;
     pub fn ark_hip_ifft_in_place(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64) -> c_int;
     pub fn ark_hip_fft_in_place_degree_aware(field: c_int, dom: *const ark_hip_radix2_domain, data: *mut u64,

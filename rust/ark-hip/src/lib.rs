@@ -25,9 +25,11 @@ pub mod device;
 pub mod domain;
 pub mod mle;
 pub mod msm;
+pub mod points;
 pub use ark_hip_sys as sys;
 pub use ark_hip_sys::{BLS12_377_G1, BLS12_377_G2, BLS12_381_G1, BLS12_381_G2, BN254_G1};
 pub use device::{DeviceError, DeviceEvaluations, DeviceVec};
+pub use points::DevicePoints;
 pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension};
 pub use msm::{check_bases, compress_bases, decompress_bases, serve_group_coefficients, sw_msm, sw_msm_bigint, BaseCheck, HipServed};
 #[cfg(feature = "ec-hook")]
