@@ -447,6 +447,69 @@ int ark_hip_test_msm_reduce_geometry(int curve, int c, int W, int narrow, int sh
   for (int k = 0; k < 12; k++) out[k] = v[k];
   return 0;
 }
+// The explicit knob record of the two hooks below -> MsmKnobs: everything else stays at its default, and no environment
+// variable is read.  knobs[8] = c, hb, tile, heavy, groups, big_slices, compact, probe.
+static MsmKnobs knobs_of_record(const int32_t* r) {
+  MsmKnobs k;
+  k.c = r[0] >= 3 && r[0] <= 26 ? r[0] : 0;
+  k.hb = r[1];
+  k.tile = r[2];
+  k.heavy = r[3] >= 64 ? r[3] : 0;
+  k.groups = r[4];
+  k.big_slices = r[5] != 0;
+  k.compact = r[6] != 0;
+  k.probe = r[7] != 0;
+  return k;
+}
+// Test hook (host only, no device): the geometry of the partition sort, the order pass and the heavy-run arrays
+// (msm_plan.hpp: msm_sort_geometry, msm_heavy_geometry) for n carried scalars under the plan (c, W, narrow, shared); W = 0: the
+// window layout of the curve's full-width scalars for c.
+int ark_hip_test_msm_sort_geometry(int curve, size_t n, int c, int W, int narrow, int shared, const int32_t knobs[8], uint64_t out[32]) {
+  if (curve < 0 || curve > 4 || !out || !knobs || n == 0 || n >= (1ull << 31) || c < 3 || c > 26 || W < 0 || W > 256 || narrow < 0 ||
+      (W && narrow > W))
+    return ARK_HIP_ERR_ARG;
+  if (W == 0) msm_window_layout(c, msm_scalar_bits(curve), &W, &narrow);
+  const MsmKnobs k = knobs_of_record(knobs);
+  const MsmPlan pl{c, W, narrow, (size_t)W << (c - 1), shared != 0};
+  const MsmSortGeom g = msm_sort_geometry(n, pl, k);
+  const MsmHeavyGeom h = msm_heavy_geometry(n, pl, k);
+  const bool accepted = (size_t)n * (size_t)W < (1ull << 32) && g.lds_a <= PART_SCATTER_LDS_MAX;   // msm_setup's two size checks
+  const uint64_t v[32] = {(uint64_t)g.HB, (uint64_t)g.LB, g.nsuper, g.tile, g.ntiles, g.nthist, g.lds_a, g.lds_b, g.stage_cap,
+                          g.big_on ? 1u : 0u, g.big_region, g.noblk, g.nohist, g.nsums, h.mean_load, h.forced_thresh, h.max_heavy,
+                          h.max_items, (uint64_t)W, (uint64_t)narrow, accepted ? 1u : 0u, PART_LDS_WORDS, PART_SCATTER_LDS_MAX,
+                          PART_BIG, SCAN_SMALL_MAX, HEAVY_CHUNK, (uint64_t)SCAN_TILE, (uint64_t)ORDER_TILE, (uint64_t)ORDER_BINS,
+                          (uint64_t)msm_window_groups(n, pl, false, k), 0, 0};
+  for (int i = 0; i < 32; i++) out[i] = v[i];
+  return 0;
+}
+// Test hook: the integer stages of one plain MSM call, copied out (msm_stage_dump.cuh, which documents header, out and cap).
+// scalars: n scalars as the MSM entries take them -- 32-byte field elements, or sbytes-byte unsigned integers with sbits
+// significant bits (sbytes = 0: full width) -- in device memory (on_device) or host memory.  Runs on lane 0's workspace and
+// stream like a synchronous MSM entry, and returns with both idle.
+int ark_hip_test_msm_sort_stages(int curve, const void* scalars, int on_device, size_t n, int mont, int sbytes, int sbits,
+                                 const int32_t knobs[8], uint64_t header[32], void* const* out, const size_t* cap_words) {
+  if (curve < 0 || curve > 4 || !scalars || !knobs || !header || n == 0 || (out && !cap_words)) return ARK_HIP_ERR_ARG;
+  if (sbytes == 0 && sbits != 0) return ARK_HIP_ERR_ARG;
+  if (sbytes && sbits == 0) sbits = 8 * sbytes;
+  const MsmKnobs k = knobs_of_record(knobs);
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  hipStream_t st;
+  if (int rc = msm_lane_stream(c, 0, &st)) return rc;
+  const void* d_scalars = scalars;
+  if (!on_device) {
+    const size_t bytes = n * (size_t)(sbytes ? sbytes : 32);
+    if (c->stage_a.cap < bytes) {
+      if (int rc = sync_compute(c)) return rc;
+      if (c->stage_a.ensure(bytes)) return ARK_HIP_ERR_NOMEM;
+    }
+    ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, scalars, bytes, hipMemcpyHostToDevice, st));
+    d_scalars = c->stage_a.p;
+  }
+#define X(NAME) msm_sort_stages_##NAME(c->msm[0], d_scalars, n, mont, st, sbytes, sbits, k, header, out, cap_words)
+  ARK_CURVE_SWITCH(curve, X);
+#undef X
+}
 // Test hook (host only, no device): the verified cache's tag of `words` u64 words -- tests/test_capi_host.py checks that
 // edits the round-4 hash could not see (a two-word edit built from its published constants) change it.
 int ark_hip_test_base_hash(const uint64_t* p, size_t words, uint64_t out[2]) {

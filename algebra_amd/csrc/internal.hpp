@@ -8,6 +8,7 @@ namespace arkhip {
 struct MsmWorkspace;
 struct MsmTimings;
 struct MsmPlan;
+struct MsmKnobs;
 struct MsmPiece;
 struct MsmSumsHeader;
 struct MsmWidths;
@@ -22,6 +23,8 @@ struct MlePoint;
                          const void* d_scalars, size_t n, int mont, hipStream_t stream, bool timing, int sbytes,  \
                          int sbits, const MsmPiece* piece);                                                       \
   int msm_finish_##NAME(MsmWorkspace& ws, int slot, uint64_t* out_xyz, MsmTimings* tm);                          \
+  int msm_sort_stages_##NAME(MsmWorkspace& ws, const void* d_scalars, size_t n, int mont, hipStream_t stream, int sbytes, \
+                             int sbits, const MsmKnobs& knobs, uint64_t* header, void* const* out, const size_t* cap); \
   int msm_sum_ranks_##NAME(const void* d_blocks, int world, size_t block_bytes, uint32_t npairs, void* d_out, hipStream_t stream); \
   int msm_fold_sums_##NAME(const MsmSumsHeader& h, const void* h_sums, uint64_t* out_xyz);                         \
   void msm_sample_widths_##NAME(const void* h_scalars, size_t n, int mont, MsmWidths* out);                        \

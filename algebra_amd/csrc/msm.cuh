@@ -1683,13 +1683,37 @@ struct MsmCall {
     return 0;
   }
 
+  // Everything in front of the accumulation: the counters zeroed, K0c, K1, group 0's sort on `stream` and group 1's on the side
+  // stream, which starts where group 0's accumulate kernel will (ws.grp_ev[1] fires behind it)
+  int front(const void* d_scalars_all, size_t n_all, const MsmProbe& pr, int sbytes, int sbits) {
+    if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[0], stream));
+    ARK_HIP_TRY(hipMemsetAsync(ws.hctr.p, 0, 64, stream));  // per window group: [chunk items, heavy runs, threshold, -]; [3]: scalar-range error flag; [8 + g]: super-buckets of group g left to the sliced pass B
+    if (compacted) compact(d_scalars_all, n_all, pr);
+    digits(sbytes, sbits);
+    if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[1], stream));
+    if (int rc = sort_group(grp[0], stream, true)) return rc;
+    if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[3], stream));
+    if (ngroups == 2) {   // group 1's sort starts when group 0's accumulate kernel does
+      ARK_HIP_TRY(hipEventRecord(ws.grp_ev[0], stream));
+      ARK_HIP_TRY(hipStreamWaitEvent(ws.side, ws.grp_ev[0], 0));
+      if (int rc = sort_group(grp[1], ws.side, false)) return rc;
+      ARK_HIP_TRY(hipEventRecord(ws.grp_ev[1], ws.side));
+    }
+    return 0;
+  }
+
+  // K4h, first kernel: the list of the group's runs that are too long for one lane, cut into chunk items, and the threshold
+  void find_heavy(const Group& G, hipStream_t st) {
+    hipLaunchKernelGGL(msm_find_heavy_kernel, dim3((u32)((G.nslots + 255) / 256)), dim3(256), 0, st, G.offsets, (u32)G.nslots,
+                       hg.forced_thresh, G.hctr, G.hlist, G.hitems);
+  }
+
   // K4h, K4, K4s: heavy runs + the lane-per-bucket kernel of one group
   int accumulate_group(const Group& G, hipStream_t st) {   // (st is reassigned below)
     const int W = pl.W, Bbits = pl.c - 1, HB = sg.HB, LB = sg.LB;
     const size_t nbk = pl.nbuckets();
     // runs too long for one lane: chunk partials by one wave each, combined per run (empty for uniform scalars)
-    hipLaunchKernelGGL(msm_find_heavy_kernel, dim3((u32)((G.nslots + 255) / 256)), dim3(256), 0, st, G.offsets, (u32)G.nslots,
-                       hg.forced_thresh, G.hctr, G.hlist, G.hitems);
+    find_heavy(G, st);
     constexpr u32 LN = C::FA::LANES;                        // lanes per element of the accumulate field
     constexpr size_t ACCB = AccOps<C>::ACC_BYTES;           // one parked accumulator (the form the kernels sum in)
     const u32 hthreads = ACCB * (256 / LN) > 49152 ? 128 : 256;  // one LDS tree per wave, <= 48 KiB per workgroup
@@ -1800,17 +1824,85 @@ struct MsmCall {
   }
 };
 
+// What one call decides before its first pipeline launch: K0, the plan, whether K0c runs, every geometry.  Shared by msm_enqueue
+// and the stage dump of the test build (msm_sort_stages).  `prepared` and `wstride` are the caller's: the probe may reset them.
+template <class C>
+struct MsmSetup {
+  MsmProbe pr;
+  MsmPlan pl;
+  size_t n_all, n;          // the call's scalars, and those the pipeline carries (after K0c: the non-zero ones)
+  bool compacted;
+  MsmSortGeom sg;
+  MsmReduceGeom rg;
+  MsmHeavyGeom hg;
+  bool lazy;                // the accumulate kernels on carry-free limbs (fp28.cuh); ARK_HIP_MSM_LAZY=0: saturated
+  u32 run_parts;
+  int ngroups;
+  bool heavy_side;
+  int split_level;
+  // the call's stages over this set-up (make_groups done); d_scalars: the call's n_all scalars
+  MsmCall<C> call(MsmWorkspace& ws, MsmJob& job, hipStream_t stream, bool timing, const void* d_points, size_t wstride,
+                  const void* d_scalars, int scalars_mont, const MsmPiece* piece, char* d_buckets) const {
+    MsmCall<C> c{ws, job, stream, timing, d_points, wstride, compacted ? ws.cscal.p : d_scalars, n, scalars_mont, piece,
+                 pl, sg, rg, hg, ngroups, heavy_side, lazy, compacted, run_parts, split_level,
+                 d_buckets, (piece && !piece->first) ? 1 : 0};
+    c.make_groups();
+    return c;
+  }
+};
+template <class C>
+int msm_setup(MsmWorkspace& ws, const void* d_scalars, size_t n, int scalars_mont, hipStream_t stream, int sbytes, int sbits,
+              const MsmPlan*& prepared, size_t& wstride, const MsmPiece* piece, const MsmKnobs& knobs, MsmSetup<C>& su) {
+  MsmProbe& pr = su.pr;   // K0
+  if (!sbytes && !piece && n >= ((size_t)1 << 19))
+    if (int rc = msm_probe_widths<C>(ws, d_scalars, n, scalars_mont, stream, knobs, prepared, wstride, pr)) return rc;
+  const MsmPlan pl = prepared ? *prepared
+                     : piece  ? *piece->plan
+                     : pr.have_widths ? msm_plan_for_widths(C::ID, n, pr.widths, knobs)
+                                      : msm_default_plan(C::ID, n, sbytes ? sbits + 1 : C::S::BITS, false, nullptr, knobs);
+  // K0c: a quarter or more of the scalars zero (known exactly from the probe's class 0) -> they leave before the sort.
+  // From here on `n` is the number of scalars the pipeline carries; base indices come back through ws.cidx after the sort.
+  // What the compaction saves grows with zeros x windows (the keys that are never written, counted and scattered), what it
+  // costs with n (one more pass over the scalars): witness-like 2^24 (60 % zeros, 15 windows) 6.52 -> 5.90 ms, a bool vector
+  // (half zeros, ONE window) 3.22 -> 3.32 -- so: at least a quarter zeros and zeros x W >= 3 n (profiles/r5_zero_compaction.txt)
+  const size_t n_all = n, zeros = pr.widths.count[0];
+  const bool compacted = pr.measured_exact && knobs.compact && zeros * 4 >= n && zeros < n && zeros * (size_t)pl.W >= 3 * n;
+  if (compacted) n = n_all - zeros;
+  if ((size_t)n * (size_t)pl.W >= (1ull << 32)) return -2;  // sort positions are 32-bit
+  if (prepared && (wstride < n || (size_t)pl.W * wstride >= (1ull << 31))) return -2;
+
+  su.pl = pl;
+  su.n_all = n_all;
+  su.n = n;
+  su.compacted = compacted;
+  su.sg = msm_sort_geometry(n, pl, knobs);
+  if (su.sg.lds_a > PART_SCATTER_LDS_MAX) return -2;   // 2^14 super-buckets and more: beyond the n W < 2^32 the sort serves anyway
+  su.rg = msm_reduce_geometry(pl, C::FA::LANES, C::S::BITS, C::FA::LANES == 1 ? msm_resident_lanes<C>() : 0, knobs);
+  su.hg = msm_heavy_geometry(n, pl, knobs);
+  su.lazy = knobs.lazy;
+  su.run_parts = (su.lazy && !piece && !pl.shared) ? msm_run_parts(n, pl, pr.have_widths ? &pr.widths : nullptr, knobs) : 1u;
+  su.ngroups = msm_window_groups(n, pl, piece != nullptr, knobs);
+  // Heavy runs (skewed scalars) and the lane-per-bucket kernel touch disjoint buckets: with one window group and a call
+  // long enough to pay two event hops, the chunk / combine kernels -- chains of dependent additions on a few hundred
+  // waves -- run on the side stream UNDER the accumulate kernel (witness-like 2^24: 1.7 ms of heavy kernels in front of
+  // 2.1 ms of accumulation; profiles/r4_skewed_sort_ab.txt).  ARK_HIP_MSM_HEAVY_SIDE=0 keeps them in line.
+  su.heavy_side = knobs.heavy_side && su.ngroups == 1 && !piece && n >= ((size_t)1 << 20);
+  su.split_level = knobs.split_level;
+  return 0;
+}
+
 // Enqueue one single-GPU MSM with device-resident inputs on `stream`; returns the job slot (>= 0) or a negative code.
 //   points / wstride / prepared:  plain call: points = the n bases, wstride = 0, prepared = nullptr;
 //                                 prepared base set: points = the [W][wstride] table of per-window multiples and
 //                                 `prepared` = the plan it was built for (msm_prepare_table).
 //   sbytes != 0: narrow unsigned scalars of sbytes bytes with at most sbits significant bits (K1n); never with `prepared`
 //   piece != nullptr: see MsmPiece (never with `prepared`; n > 0)
+//   knobs_in: the knobs of this call (nullptr: msm_knobs(), the environment's -- what every entry point of the library passes)
 // The stages are those of DESIGN.md section 4; every size comes from msm_plan.hpp.
 template <class C>
 int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const MsmPlan* prepared, const void* d_scalars,
                 size_t n, int scalars_mont, hipStream_t stream, bool timing, int sbytes = 0, int sbits = 0,
-                const MsmPiece* piece = nullptr) {
+                const MsmPiece* piece = nullptr, const MsmKnobs* knobs_in = nullptr) {
   typedef XYZZ<typename C::F> Pt;
   std::lock_guard<std::mutex> lock(ws.mu);
   int slot = -1;
@@ -1829,60 +1921,19 @@ int msm_enqueue(MsmWorkspace& ws, const void* d_points, size_t wstride, const Ms
   if (n >= (1ull << 31)) return -2;
   if (sbytes && (prepared || (sbytes != 1 && sbytes != 2 && sbytes != 4 && sbytes != 8) || sbits < 1 || sbits > 8 * sbytes))
     return -1;
-  const MsmKnobs knobs = msm_knobs();
+  const MsmKnobs knobs = knobs_in ? *knobs_in : msm_knobs();
+  MsmSetup<C> su;
+  if (int rc = msm_setup<C>(ws, d_scalars, n, scalars_mont, stream, sbytes, sbits, prepared, wstride, piece, knobs, su)) return rc;
 
-  MsmProbe pr;   // K0
-  if (!sbytes && !piece && n >= ((size_t)1 << 19))
-    if (int rc = msm_probe_widths<C>(ws, d_scalars, n, scalars_mont, stream, knobs, prepared, wstride, pr)) return rc;
-  const MsmPlan pl = prepared ? *prepared
-                     : piece  ? *piece->plan
-                     : pr.have_widths ? msm_plan_for_widths(C::ID, n, pr.widths, knobs)
-                                      : msm_default_plan(C::ID, n, sbytes ? sbits + 1 : C::S::BITS, false, nullptr, knobs);
-  // K0c: a quarter or more of the scalars zero (known exactly from the probe's class 0) -> they leave before the sort.
-  // From here on `n` is the number of scalars the pipeline carries; base indices come back through ws.cidx after the sort.
-  // What the compaction saves grows with zeros x windows (the keys that are never written, counted and scattered), what it
-  // costs with n (one more pass over the scalars): witness-like 2^24 (60 % zeros, 15 windows) 6.52 -> 5.90 ms, a bool vector
-  // (half zeros, ONE window) 3.22 -> 3.32 -- so: at least a quarter zeros and zeros x W >= 3 n (profiles/r5_zero_compaction.txt)
-  const size_t n_all = n, zeros = pr.widths.count[0];
-  const bool compacted = pr.measured_exact && knobs.compact && zeros * 4 >= n && zeros < n && zeros * (size_t)pl.W >= 3 * n;
-  if (compacted) n = n_all - zeros;
-  if ((size_t)n * (size_t)pl.W >= (1ull << 32)) return -2;  // sort positions are 32-bit
-  if (prepared && (wstride < n || (size_t)pl.W * wstride >= (1ull << 31))) return -2;
+  if (ws.reserve(su.n, su.pl, su.sg, su.rg, su.hg, Pt::BYTES, su.compacted, !piece, su.run_parts)) return -3;
+  if (int rc = msm_job_resources(job, su.rg.npairs * Pt::BYTES + 64, timing)) return rc;
+  if (int rc = ws.launch_resources(su.ngroups == 2 || su.heavy_side)) return rc;
 
-  const MsmSortGeom sg = msm_sort_geometry(n, pl, knobs);
-  if (sg.lds_a > PART_SCATTER_LDS_MAX) return -2;   // 2^14 super-buckets and more: beyond the n W < 2^32 the sort serves anyway
-  const MsmReduceGeom rg = msm_reduce_geometry(pl, C::FA::LANES, C::S::BITS, C::FA::LANES == 1 ? msm_resident_lanes<C>() : 0, knobs);
-  const MsmHeavyGeom hg = msm_heavy_geometry(n, pl, knobs);
-  const bool lazy = knobs.lazy;  // the accumulate kernels on carry-free limbs (fp28.cuh); ARK_HIP_MSM_LAZY=0: saturated
-  const u32 run_parts = (lazy && !piece && !pl.shared) ? msm_run_parts(n, pl, pr.have_widths ? &pr.widths : nullptr, knobs) : 1u;
-  const int ngroups = msm_window_groups(n, pl, piece != nullptr, knobs);
-  // Heavy runs (skewed scalars) and the lane-per-bucket kernel touch disjoint buckets: with one window group and a call
-  // long enough to pay two event hops, the chunk / combine kernels -- chains of dependent additions on a few hundred
-  // waves -- run on the side stream UNDER the accumulate kernel (witness-like 2^24: 1.7 ms of heavy kernels in front of
-  // 2.1 ms of accumulation; profiles/r4_skewed_sort_ab.txt).  ARK_HIP_MSM_HEAVY_SIDE=0 keeps them in line.
-  const bool heavy_side = knobs.heavy_side && ngroups == 1 && !piece && n >= ((size_t)1 << 20);
-
-  if (ws.reserve(n, pl, sg, rg, hg, Pt::BYTES, compacted, !piece, run_parts)) return -3;
-  if (int rc = msm_job_resources(job, rg.npairs * Pt::BYTES + 64, timing)) return rc;
-  if (int rc = ws.launch_resources(ngroups == 2 || heavy_side)) return rc;
-
-  MsmCall<C> call{ws, job, stream, timing, d_points, wstride, compacted ? ws.cscal.p : d_scalars, n, scalars_mont, piece,
-                  pl, sg, rg, hg, ngroups, heavy_side, lazy, compacted, run_parts, knobs.split_level,
-                  piece ? (char*)piece->buckets : (char*)ws.buckets.p, (piece && !piece->first) ? 1 : 0};
-  call.make_groups();
-  if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[0], stream));
-  ARK_HIP_TRY(hipMemsetAsync(ws.hctr.p, 0, 64, stream));  // per window group: [chunk items, heavy runs, threshold, -]; [3]: scalar-range error flag; [8 + g]: super-buckets of group g left to the sliced pass B
-  if (compacted) call.compact(d_scalars, n_all, pr);
-  call.digits(sbytes, sbits);
-  if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[1], stream));
-  if (int rc = call.sort_group(call.grp[0], stream, true)) return rc;
-  if (timing) ARK_HIP_TRY(hipEventRecord(job.ev[3], stream));
-  if (ngroups == 2) {   // group 1's sort starts when group 0's accumulate kernel does
-    ARK_HIP_TRY(hipEventRecord(ws.grp_ev[0], stream));
-    ARK_HIP_TRY(hipStreamWaitEvent(ws.side, ws.grp_ev[0], 0));
-    if (int rc = call.sort_group(call.grp[1], ws.side, false)) return rc;
-    ARK_HIP_TRY(hipEventRecord(ws.grp_ev[1], ws.side));
-  }
+  MsmCall<C> call = su.call(ws, job, stream, timing, d_points, wstride, d_scalars, scalars_mont, piece,
+                            piece ? (char*)piece->buckets : (char*)ws.buckets.p);
+  const MsmReduceGeom& rg = su.rg;
+  const int ngroups = su.ngroups;
+  if (int rc = call.front(d_scalars, su.n_all, su.pr, sbytes, sbits)) return rc;
   if (piece && piece->after_prev) ARK_HIP_TRY(hipStreamWaitEvent(stream, piece->after_prev, 0));  // the buckets' previous writer
   if (int rc = call.accumulate_group(call.grp[0], stream)) return rc;
   if (ngroups == 2) {

@@ -1,6 +1,7 @@
 // Instantiation of the MSM pipeline, the fixed-base batch multiplication, the point-array and point-vector kernels for BN254_G1 (one TU per curve so
 // the five heavy template expansions compile in parallel).
 #include "msm.cuh"
+#include "msm_stage_dump.cuh"
 #include "batchmul.cuh"
 #include "devops.cuh"
 #include "gfft.cuh"
@@ -12,6 +13,10 @@ namespace arkhip {
 int msm_enqueue_BN254_G1(MsmWorkspace& ws, const void* d_points, size_t wstride, const MsmPlan* prepared, const void* d_scalars,
                    size_t n, int mont, hipStream_t stream, bool timing, int sbytes, int sbits, const MsmPiece* piece) {
   return msm_enqueue<BN254_G1>(ws, d_points, wstride, prepared, d_scalars, n, mont, stream, timing, sbytes, sbits, piece);
+}
+int msm_sort_stages_BN254_G1(MsmWorkspace& ws, const void* d_scalars, size_t n, int mont, hipStream_t stream, int sbytes, int sbits,
+                   const MsmKnobs& knobs, uint64_t* header, void* const* out, const size_t* cap) {
+  return msm_sort_stages<BN254_G1>(ws, d_scalars, n, mont, stream, sbytes, sbits, knobs, header, out, cap);
 }
 int msm_finish_BN254_G1(MsmWorkspace& ws, int slot, uint64_t* out_xyz, MsmTimings* tm) {
   return msm_finish<BN254_G1>(ws, slot, out_xyz, tm);

@@ -629,6 +629,28 @@ int ark_hip_test_msm_host_fold_l0(int curve, const uint64_t* parts, int windows,
  * resident_lanes: chunks the level-0 kernel keeps resident on the chip (0: unknown).
  * out = L0, m, mn, nbits, Q, two_digit, d2, rows2, nsum2, chunk, nchunks, npairs. */
 int ark_hip_test_msm_reduce_geometry(int curve, int c, int W, int narrow, int shared, size_t resident_lanes, uint32_t out[12]);
+/* HOST-ONLY test hook: the geometry of the MSM's partition sort, bucket order pass and heavy-run arrays (csrc/msm_plan.hpp,
+ * msm_sort_geometry and msm_heavy_geometry) for n carried scalars under the plan (c, W, narrow, shared); W = 0: the window layout
+ * of the curve's full-width scalars.  knobs[8] = c, hb, tile, heavy, groups, big_slices, compact, probe (MsmKnobs fields; the rest
+ * at their defaults; no environment variable is read).
+ * out = HB, LB, nsuper, tile, ntiles, nthist, lds_a, lds_b, stage_cap, big_on, big_region, noblk, nohist, nsums, mean_load,
+ * forced_thresh, max_heavy, max_items, W, narrow, accepted (the call passes msm_enqueue's size checks), PART_LDS_WORDS,
+ * PART_SCATTER_LDS_MAX, PART_BIG, SCAN_SMALL_MAX, HEAVY_CHUNK, SCAN_TILE, ORDER_TILE, ORDER_BINS, window groups, 0, 0. */
+int ark_hip_test_msm_sort_geometry(int curve, size_t n, int c, int W, int narrow, int shared, const int32_t knobs[8], uint64_t out[32]);
+/* The integer stages of one plain MSM call -- width probe, plan, zero-scalar compaction, digit recoding, the partition sort and
+ * order pass of every window group, the heavy-run list -- run through the stage functions msm_enqueue runs, synchronised and
+ * copied out.  No bases, no accumulation; no job slot stays busy.  scalars: 32-byte field elements (sbytes = 0, sbits = 0) or
+ * sbytes-byte unsigned integers with sbits significant bits (0: all), in device (on_device) or host memory.  knobs: as above.
+ * header[32] = c, W, narrow, n_carried, compacted, ngroups, HB, LB, tile, ntiles, nthist, stage_cap, big_on, shift, HEAVY_CHUNK,
+ * PART_BIG, max_heavy, max_items, noblk, nsums, lds_a, lds_b, SCAN_SMALL_MAX, n; from word 24, per window group: w0, Wg, nslots,
+ * nbk_g.  out = NULL: the header only.  Otherwise nine arrays of u32 words with their capacities in words (cap_words): keys
+ * [W][n_carried]; cidx [n_carried] and the compacted scalars [n_carried][8] (when compacted; else may be NULL); sorted
+ * [W][n_carried] (group g from word w0 n_carried; 0xffffffff where the sort wrote nothing); offsets (group g: nslots + 1 words
+ * from word (w0 << (c - 1)) + g); order (group g from word w0 << (c - 1)); hctr [16]; hlist (3 words per heavy run: bucket,
+ * first_item, items; group 0's, then group 1's); hitems (2 words per chunk item, likewise).  ARK_HIP_ERR_SIZE when a capacity is
+ * too small: nothing is ever written short. */
+int ark_hip_test_msm_sort_stages(int curve, const void* scalars, int on_device, size_t n, int mont, int sbytes, int sbits,
+                                 const int32_t knobs[8], uint64_t header[32], void* const* out, const size_t* cap_words);
 /* The carry-free limb arithmetic (csrc/fp28.cuh, fp28x2.cuh, fft.cuh Fft29) ONE OP AT A TIME ON RAW LIMBS: lane t reads `arity`
  * slots of L words (u32[L]: the W-bit limbs as the test chose them, not canonical words) at in[(t * arity + j) * L] and writes
  * L + 1 words at out[t * (L + 1)] (word L: the op's boolean result).  The Fp2L ops (op >= 40; field = BLS12-381 / BLS12-377 Fq)
