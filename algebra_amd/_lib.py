@@ -188,6 +188,9 @@ TEST_SYMBOLS = {
     "ark_hip_test_msm_sort_stages": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                                C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
                                                C.POINTER(C.c_size_t)]),
+    "ark_hip_test_msm_pieces": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_int,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
     "ark_hip_test_msm_host_fold_l0": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 TEST_LIB_PATH = os.path.join(_HERE, "libark_hip_test.so")

@@ -6,6 +6,7 @@
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "capi_cache.hpp"
+#include "msm_piece_dump.cuh"
 #include "pointcheck.cuh"
 #include "pointcodec.cuh"
 #include "pointvec.cuh"
@@ -507,6 +508,65 @@ int ark_hip_test_msm_sort_stages(int curve, const void* scalars, int on_device, 
     d_scalars = c->stage_a.p;
   }
 #define X(NAME) msm_sort_stages_##NAME(c->msm[0], d_scalars, n, mont, st, sbytes, sbits, k, header, out, cap_words)
+  ARK_CURVE_SWITCH(curve, X);
+#undef X
+}
+// Test hook: one MSM run as explicit pieces that share one plan and one bucket array, the buckets copied out behind every piece
+// (msm_piece_dump.cuh, which documents header, hctr_out and buckets_out).  bases / scalars: the n pairs in device memory
+// (on_device) or host memory; sizes[npieces] sum to n.  The plan is msm_stream's: msm_default_plan(.., streamed = true) under
+// the knobs of the record, and no environment variable is read:
+//   knobs[12] = c, heavy, hb, probe, compact, lazy, tile, big_slices, prepared, 0, 0, 0
+// (prepared != 0: the plan is handed to msm_enqueue as a prepared set's too, which a piece must refuse with ARK_HIP_ERR_ARG).
+// Runs on lane 0's workspace and stream, and returns with both idle and no job slot taken.
+int ark_hip_test_msm_pieces(int curve, const void* bases, const void* scalars, int on_device, size_t n, int mont, const size_t* sizes,
+                            int npieces, const int32_t knobs[12], uint64_t header[80], uint32_t* hctr_out, size_t hctr_cap_words,
+                            void* buckets_out, size_t buckets_cap_bytes, uint64_t* out_xyz) {
+  if (curve < 0 || curve > 4 || !bases || !scalars || !sizes || !knobs || !header || n == 0 || n >= (1ull << 31) || npieces < 1 ||
+      npieces > MPD_MAX_PIECES || knobs[9] || knobs[10] || knobs[11])
+    return ARK_HIP_ERR_ARG;
+  MsmKnobs k;
+  k.c = knobs[0] >= 3 && knobs[0] <= 26 ? knobs[0] : 0;
+  k.heavy = knobs[1] >= 64 ? knobs[1] : 0;
+  k.hb = knobs[2];
+  k.probe = knobs[3] != 0;
+  k.compact = knobs[4] != 0;
+  k.lazy = knobs[5] != 0;
+  k.tile = knobs[6];
+  k.big_slices = knobs[7] != 0;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  hipStream_t st;
+  if (int rc = msm_lane_stream(c, 0, &st)) return rc;
+  // the plan as msm_stream makes it: the window size from a sample of the host scalars where the probe is on and n is large
+  MsmWidths widths{};
+  bool skewed = false;
+  if (k.probe && !on_device && n >= ((size_t)1 << 19) && msm_sample_widths_dispatch(curve, scalars, n, mont, &widths) == 0)
+    skewed = msm_widths_skewed(widths);
+  const MsmPlan plan = msm_default_plan(curve, n, msm_scalar_bits(curve), false, skewed ? &widths : nullptr, k, /*streamed=*/true);
+  size_t step = 0;
+  for (int i = 0; i < npieces; i++) step = sizes[i] > step ? sizes[i] : step;
+  if ((size_t)step * (size_t)plan.W >= (1ull << 32)) return ARK_HIP_ERR_SIZE;
+  const size_t ab = (size_t)CURVES[curve].fe_words * 16;
+  const size_t need = plan.nbuckets() * (size_t)CURVES[curve].fe_words * 32;   // XYZZ: four field elements
+  const bool grow = c->piece_buckets.cap < need || (!on_device && (c->stage_a.cap < n * 32 || c->stage_b.cap < n * ab));
+  if (grow) {
+    if (int rc = sync_compute(c)) return rc;
+    if (c->piece_buckets.ensure(need) || (!on_device && (c->stage_a.ensure(n * 32) || c->stage_b.ensure(n * ab)))) return ARK_HIP_ERR_NOMEM;
+  }
+  for (int j = 0; j < 2; j++)
+    if (!c->piece_ev[j]) ARK_HIP_TRY(hipEventCreateWithFlags(&c->piece_ev[j], hipEventDisableTiming));
+  const void *d_bases = bases, *d_scalars = scalars;
+  if (!on_device && hctr_out) {
+    ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, scalars, n * 32, hipMemcpyHostToDevice, st));
+    ARK_HIP_TRY(hipMemcpyAsync(c->stage_b.p, bases, n * ab, hipMemcpyHostToDevice, st));
+  }
+  if (!on_device) {
+    d_scalars = c->stage_a.p;
+    d_bases = c->stage_b.p;
+  }
+#define X(NAME)                                                                                                                    \
+  msm_piece_dump_##NAME(c->msm[0], d_bases, d_scalars, n, mont, st, sizes, npieces, plan, k, knobs[8] != 0, c->piece_buckets.p, \
+                        c->piece_ev, header, hctr_out, hctr_cap_words, buckets_out, buckets_cap_bytes, out_xyz)
   ARK_CURVE_SWITCH(curve, X);
 #undef X
 }

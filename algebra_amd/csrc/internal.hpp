@@ -25,6 +25,10 @@ struct MlePoint;
   int msm_finish_##NAME(MsmWorkspace& ws, int slot, uint64_t* out_xyz, MsmTimings* tm);                          \
   int msm_sort_stages_##NAME(MsmWorkspace& ws, const void* d_scalars, size_t n, int mont, hipStream_t stream, int sbytes, \
                              int sbits, const MsmKnobs& knobs, uint64_t* header, void* const* out, const size_t* cap); \
+  int msm_piece_dump_##NAME(MsmWorkspace& ws, const void* d_bases, const void* d_scalars, size_t n, int mont, hipStream_t stream, \
+                            const size_t* sizes, int npieces, const MsmPlan& plan, const MsmKnobs& knobs, bool as_prepared, \
+                            void* d_buckets, hipEvent_t* ev, uint64_t* header, uint32_t* hctr_out, size_t hctr_cap, \
+                            void* buckets_out, size_t buckets_cap, uint64_t* out_xyz); \
   int msm_sum_ranks_##NAME(const void* d_blocks, int world, size_t block_bytes, uint32_t npairs, void* d_out, hipStream_t stream); \
   int msm_fold_sums_##NAME(const MsmSumsHeader& h, const void* h_sums, uint64_t* out_xyz);                         \
   void msm_sample_widths_##NAME(const void* h_scalars, size_t n, int mont, MsmWidths* out);                        \

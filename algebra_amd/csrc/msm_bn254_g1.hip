@@ -2,6 +2,7 @@
 // the five heavy template expansions compile in parallel).
 #include "msm.cuh"
 #include "msm_stage_dump.cuh"
+#include "msm_piece_dump.cuh"
 #include "batchmul.cuh"
 #include "devops.cuh"
 #include "gfft.cuh"
@@ -17,6 +18,13 @@ int msm_enqueue_BN254_G1(MsmWorkspace& ws, const void* d_points, size_t wstride,
 int msm_sort_stages_BN254_G1(MsmWorkspace& ws, const void* d_scalars, size_t n, int mont, hipStream_t stream, int sbytes, int sbits,
                    const MsmKnobs& knobs, uint64_t* header, void* const* out, const size_t* cap) {
   return msm_sort_stages<BN254_G1>(ws, d_scalars, n, mont, stream, sbytes, sbits, knobs, header, out, cap);
+}
+int msm_piece_dump_BN254_G1(MsmWorkspace& ws, const void* d_bases, const void* d_scalars, size_t n, int mont, hipStream_t stream,
+                   const size_t* sizes, int npieces, const MsmPlan& plan, const MsmKnobs& knobs, bool as_prepared, void* d_buckets,
+                   hipEvent_t* ev, uint64_t* header, uint32_t* hctr_out, size_t hctr_cap, void* buckets_out, size_t buckets_cap,
+                   uint64_t* out_xyz) {
+  return msm_piece_dump<BN254_G1>(ws, d_bases, d_scalars, n, mont, stream, sizes, npieces, plan, knobs, as_prepared, d_buckets, ev, header,
+                        hctr_out, hctr_cap, buckets_out, buckets_cap, out_xyz);
 }
 int msm_finish_BN254_G1(MsmWorkspace& ws, int slot, uint64_t* out_xyz, MsmTimings* tm) {
   return msm_finish<BN254_G1>(ws, slot, out_xyz, tm);

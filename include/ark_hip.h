@@ -651,6 +651,21 @@ int ark_hip_test_msm_sort_geometry(int curve, size_t n, int c, int W, int narrow
  * too small: nothing is ever written short. */
 int ark_hip_test_msm_sort_stages(int curve, const void* scalars, int on_device, size_t n, int mont, int sbytes, int sbits,
                                  const int32_t knobs[8], uint64_t header[32], void* const* out, const size_t* cap_words);
+/* One MSM run as explicit pieces that share one plan and one bucket array (csrc/msm_piece_dump.cuh), through the msm_enqueue /
+ * msm_finish the streamed host-pointer entry runs for each of its pieces; the bucket array is copied out behind every piece.
+ * bases (affine x|y) and scalars (32 bytes each): the n pairs, in device memory (on_device) or host memory; sizes[npieces],
+ * 1 <= npieces <= 16, none zero, summing to n (one piece: a first-and-last piece).  The plan is the streamed entry's under
+ * knobs[12] = c, heavy, hb, probe, compact, lazy, tile, big_slices, prepared, 0, 0, 0 -- no environment variable is read;
+ * prepared != 0 hands the plan to msm_enqueue as a prepared set's as well, which a piece refuses: ARK_HIP_ERR_ARG.
+ * header (u64 words): c, W, narrow, nbuckets, bytes of a stored XYZZ point, npieces, pieces run, the piece whose scalars were
+ * out of range (else ~0), the reduction's L0, m, mn, nbits, Q, two_digit, npairs, lazy; from word 16, four per piece: HB, LB, n,
+ * window groups.  hctr_out = NULL: the header only.  Otherwise piece k's 16 counter words (u32) go to hctr_out + 16 k and the
+ * nbuckets points behind piece k to buckets_out + k * nbuckets * point bytes; ARK_HIP_ERR_SIZE when a capacity (words / bytes)
+ * is too small, before anything is written.  out_xyz: the result, written behind the last piece.  ARK_HIP_ERR_SCALAR_RANGE
+ * names the piece in the header; no later piece is enqueued.  On return lane 0 is idle and no job slot is taken. */
+int ark_hip_test_msm_pieces(int curve, const void* bases, const void* scalars, int on_device, size_t n, int mont, const size_t* sizes,
+                            int npieces, const int32_t knobs[12], uint64_t header[80], uint32_t* hctr_out, size_t hctr_cap_words,
+                            void* buckets_out, size_t buckets_cap_bytes, uint64_t* out_xyz);
 /* The carry-free limb arithmetic (csrc/fp28.cuh, fp28x2.cuh, fft.cuh Fft29) ONE OP AT A TIME ON RAW LIMBS: lane t reads `arity`
  * slots of L words (u32[L]: the W-bit limbs as the test chose them, not canonical words) at in[(t * arity + j) * L] and writes
  * L + 1 words at out[t * (L + 1)] (word L: the op's boolean result).  The Fp2L ops (op >= 40; field = BLS12-381 / BLS12-377 Fq)
