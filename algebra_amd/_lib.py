@@ -193,6 +193,19 @@ TEST_SYMBOLS = {
                                           C.c_void_p]),
     "ark_hip_test_msm_host_fold_l0": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
+
+
+class ScratchRow(C.Structure):
+    """``ark_hip_scratch_row``: one scratch buffer in ark_hip_test_scratch_report's answer."""
+    _fields_ = [("name", C.c_char * 40), ("cap", C.c_uint64), ("asked", C.c_uint64), ("regrown", C.c_uint64),
+                ("dirty_beyond", C.c_uint64), ("first_dirty_offset", C.c_uint64)]
+
+
+TEST_SYMBOLS.update({
+    "ark_hip_test_scratch_poison": (C.c_int, [C.c_uint32]),
+    "ark_hip_test_scratch_report": (C.c_int, [C.c_uint32, C.POINTER(ScratchRow), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ark_hip_test_scratch_selfcheck": (C.c_int, []),
+})
 TEST_LIB_PATH = os.path.join(_HERE, "libark_hip_test.so")
 
 _lib = None

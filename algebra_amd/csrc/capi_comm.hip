@@ -16,10 +16,9 @@ constexpr uint32_t SUMS_MAX_PARTS = 1024;
 size_t sums_block_bytes(int curve) { return sizeof(MsmSumsHeader) + (size_t)SUMS_MAX_PARTS * CURVES[curve].fe_words * 32; }
 int sums_buffers(Context* c, int curve, int world) {
   const size_t bb = sums_block_bytes(curve);
-  if (c->comm_sums.cap < bb * (size_t)(world + 2)) {
+  if (c->comm_sums.cap < bb * (size_t)(world + 2))
     if (int rc = sync_compute(c)) return rc;
-    if (c->comm_sums.ensure(bb * (size_t)(world + 2))) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->comm_sums.ensure(bb * (size_t)(world + 2))) return ARK_HIP_ERR_NOMEM;
   // pinned: [MAX_DEV staging headers | MAX_DEV gathered headers | summed parts]
   if (!c->comm_sums_pinned) ARK_HIP_TRY(hipHostMalloc(&c->comm_sums_pinned, sizeof(MsmSumsHeader) * 2 * MAX_DEV + (size_t)SUMS_MAX_PARTS * 12 * 32));
   return 0;
@@ -487,8 +486,8 @@ int ark_hip_fft_sharded_device(int field, const ark_hip_radix2_domain* dom, void
   if (c->comm_tmp.cap < k.m * 32) {
     if (int rc = sync_compute(c)) return rc;
     ARK_HIP_TRY(hipStreamSynchronize(c->comm_stream));
-    if (c->comm_tmp.ensure(k.m * 32)) return ARK_HIP_ERR_NOMEM;
   }
+  if (c->comm_tmp.ensure(k.m * 32)) return ARK_HIP_ERR_NOMEM;
   char* loc = (char*)d_local;
   char* tmp = (char*)c->comm_tmp.p;
   const int S = comm_slices(k.sub);

@@ -146,10 +146,9 @@ int ark_hip_poly_mul(int field, const uint64_t* a, size_t na, const uint64_t* b,
   const size_t n = (size_t)dom.size;
   ARK_SCOPE(sc);
   Context* c = sc.c;
-  if (c->stage_a.cap < n * 32 || c->stage_b.cap < n * 32) {
+  if (c->stage_a.cap < n * 32 || c->stage_b.cap < n * 32)
     if (int rc = sync_compute(c)) return rc;
-    if (c->stage_a.ensure(n * 32) || c->stage_b.ensure(n * 32)) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->stage_a.ensure(n * 32) || c->stage_b.ensure(n * 32)) return ARK_HIP_ERR_NOMEM;
   if (int rc = c->stager.upload(c->stage_a.p, a, na * 32, c->stream)) return rc;
   if (int rc = c->stager.upload(c->stage_b.p, b, nb * 32, c->stream)) return rc;
   // forward transforms: short inputs take the degree-aware path (their padding is never read beyond the next power of
@@ -224,10 +223,9 @@ static int gfft_entry(Context* c, int curve, const ark_hip_radix2_domain* dom, v
     if (int rc = fft_roots_dispatch(field, c->fft, k, inverse ? dom->group_gen_inv : dom->group_gen, c->stream, &roots)) return rc;
   const size_t wb = gfft_work_bytes_any(curve, k);
   if (wb == 0) return ARK_HIP_ERR_ARG;
-  if (c->gfft_work.cap < wb || c->gfft_scal.cap < n * 32) {
+  if (c->gfft_work.cap < wb || c->gfft_scal.cap < n * 32)
     if (int rc = sync_compute(c)) return rc;
-    if (c->gfft_work.ensure(wb) || c->gfft_scal.ensure(n * 32)) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->gfft_work.ensure(wb) || c->gfft_scal.ensure(n * 32)) return ARK_HIP_ERR_NOMEM;
   const uint32_t *pre = nullptr, *post = nullptr;
   if (!inverse && coset) {        // distribute_powers(coeffs, offset)                                   fft.rs:74-79
     if (int rc = fft_scalars_dispatch(field, c->fft, dom->offset, nullptr, n, c->gfft_scal.p, c->stream)) return rc;
@@ -250,10 +248,9 @@ int ark_hip_fft_group_in_place(int curve, const ark_hip_radix2_domain* dom, uint
   ARK_SCOPE(sc);
   Context* c = sc.c;
   const size_t bytes = (size_t)dom->size * CURVES[curve].fe_words * 3 * 8;
-  if (c->stage_a.cap < bytes) {
+  if (c->stage_a.cap < bytes)
     if (int rc = sync_compute(c)) return rc;
-    if (c->stage_a.ensure(bytes)) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->stage_a.ensure(bytes)) return ARK_HIP_ERR_NOMEM;
   if (int rc = c->stager.upload(c->stage_a.p, jac_points, bytes, c->stream)) return rc;
   if (int rc = gfft_entry(c, curve, dom, c->stage_a.p, inverse)) {
     (void)hipStreamSynchronize(c->stream);

@@ -194,18 +194,16 @@ static int msm_sw_small_once(int curve, const uint64_t* bases, const void* scala
   return msm_with_bases(c, curve, bases, n, [&](const void* d_res, bool fill, BaseCacheEntry*) -> int {
     const void* d_bases = d_res;
     if (!d_bases) {
-      if (c->stage_a.cap < bb) {
+      if (c->stage_a.cap < bb)
         if (int rc = sync_compute(c)) return rc;
-        if (c->stage_a.ensure(bb)) return ARK_HIP_ERR_NOMEM;
-      }
+      if (c->stage_a.ensure(bb)) return ARK_HIP_ERR_NOMEM;
       d_bases = c->stage_a.p;
     }
     if (!d_res || fill)
       if (int rc = c->stager.upload((void*)d_bases, bases, bb, c->copy_stream)) return rc;
-    if (c->stage_b.cap < sb) {
+    if (c->stage_b.cap < sb)
       if (int rc = sync_compute(c)) return rc;
-      if (c->stage_b.ensure(sb)) return ARK_HIP_ERR_NOMEM;
-    }
+    if (c->stage_b.ensure(sb)) return ARK_HIP_ERR_NOMEM;
     if (int rc = c->stager.upload(c->stage_b.p, scalars, sb, c->copy_stream)) return rc;
     ARK_HIP_TRY(hipStreamSynchronize(c->copy_stream));   // staged uploads leave their last slices in flight
     return msm_sw_small_device_once(curve, d_bases, c->stage_b.p, n, scalar_bytes, max_bits, out_xyz);
@@ -422,10 +420,9 @@ static int msm_prepared_host_enqueue(const ark_hip_msm_bases* bases, const uint6
   int k = 0;
   if (int rc = ring_acquire(c, &k)) return rc;
   if (n) {
-    if (c->ring_s[k].cap < n * 32) {
+    if (c->ring_s[k].cap < n * 32)
       if (int rc = sync_compute(c)) return rc;  // growing frees memory an enqueued MSM may still read
-      if (c->ring_s[k].ensure(n * 32)) return ARK_HIP_ERR_NOMEM;
-    }
+    if (c->ring_s[k].ensure(n * 32)) return ARK_HIP_ERR_NOMEM;
     // page-locked scalars (ark_hip_host_alloc) are read in place by the DMA engine -- the caller keeps them valid until
     // the wait returns; ordinary memory goes through the pinned staging ring and has been read when this returns
     if (int rc = c->stager.upload(c->ring_s[k].p, scalars, n * 32, c->copy_stream, true)) {

@@ -28,8 +28,8 @@ int tables(Context* c, int curve, int nt, size_t n, size_t* slab) {
   if (c->pointvec_work.cap < bytes) {
     if (int rc = sync_compute(c)) return rc;   // the buffer it replaces may still be read by a launch in flight
     ARK_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->pointvec_work.ensure(bytes)) return ARK_HIP_ERR_NOMEM;
   }
+  if (c->pointvec_work.ensure(bytes)) return ARK_HIP_ERR_NOMEM;
   *slab = lanes;
   return 0;
 }
@@ -74,10 +74,9 @@ int ark_hip_sw_mul(int curve, const uint64_t* points, int form, const uint64_t* 
   const size_t chunk = stage_chunk_points("ARK_HIP_POINTVEC_CHUNK_POINTS", ob, n);
   const bool shared = n_scalars == 1 && n != 1;
   const size_t sb = shared ? 32 : chunk * 32;
-  if (c->stage_a.cap < chunk * pb || c->stage_b.cap < sb || c->stage_c.cap < chunk * ob) {
+  if (c->stage_a.cap < chunk * pb || c->stage_b.cap < sb || c->stage_c.cap < chunk * ob)
     if (int rc = sync_compute(c)) return rc;
-    if (c->stage_a.ensure(chunk * pb) || c->stage_b.ensure(sb) || c->stage_c.ensure(chunk * ob)) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->stage_a.ensure(chunk * pb) || c->stage_b.ensure(sb) || c->stage_c.ensure(chunk * ob)) return ARK_HIP_ERR_NOMEM;
   size_t slab = 0;
   if (int rc = tables(c, curve, 1, chunk, &slab)) return rc;
   if (shared)

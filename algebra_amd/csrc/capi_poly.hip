@@ -63,8 +63,8 @@ inline PolyLevels poly_levels(size_t n) {
 }
 // grows only with every stream idle: earlier asynchronous calls may still be using the buffer
 inline int poly_scratch(Context* c, size_t elems) {
-  if (c->poly_work.cap >= elems * 32) return 0;
-  if (int rc = sync_compute(c)) return rc;
+  if (c->poly_work.cap < elems * 32)
+    if (int rc = sync_compute(c)) return rc;
   return c->poly_work.ensure(elems * 32) ? ARK_HIP_ERR_NOMEM : 0;
 }
 inline int result_to_host(Context* c, uint64_t* out) {

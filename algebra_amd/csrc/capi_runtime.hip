@@ -215,10 +215,9 @@ int ark_hip_sw_normalize_batch(int curve, const uint64_t* jac_points, size_t n, 
   ARK_SCOPE(sc);
   Context* c = sc.c;
   const size_t fb = (size_t)CURVES[curve].fe_words * 8;
-  if (c->stage_a.cap < n * 3 * fb || c->stage_b.cap < n * 2 * fb) {
+  if (c->stage_a.cap < n * 3 * fb || c->stage_b.cap < n * 2 * fb)
     if (int rc = sync_compute(c)) return rc;
-    if (c->stage_a.ensure(n * 3 * fb) || c->stage_b.ensure(n * 2 * fb)) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->stage_a.ensure(n * 3 * fb) || c->stage_b.ensure(n * 2 * fb)) return ARK_HIP_ERR_NOMEM;
   if (int rc = c->stager.upload(c->stage_a.p, jac_points, n * 3 * fb, c->stream)) return rc;
   if (int rc = normalize_dispatch(curve, c->stage_a.p, c->stage_b.p, n, c->stream)) return rc;
   ARK_HIP_TRY(hipMemcpyAsync(out_xy, c->stage_b.p, n * 2 * fb, hipMemcpyDeviceToHost, c->stream));
@@ -274,10 +273,9 @@ int ark_hip_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, 
   Context* c = sc.c;
   const size_t ab = (size_t)CURVES[curve].fe_words * 16;
   const size_t chunk = stage_chunk_points("ARK_HIP_CHECK_CHUNK_POINTS", ab, n);
-  if (c->stage_a.cap < chunk * ab || (status && c->stage_b.cap < chunk)) {
+  if (c->stage_a.cap < chunk * ab || (status && c->stage_b.cap < chunk))
     if (int rc = sync_compute(c)) return rc;
-    if (c->stage_a.ensure(chunk * ab) || (status && c->stage_b.ensure(chunk))) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->stage_a.ensure(chunk * ab) || (status && c->stage_b.ensure(chunk))) return ARK_HIP_ERR_NOMEM;
   if (int rc = sw_check_begin(c)) return rc;
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = n - off < chunk ? n - off : chunk;
@@ -350,10 +348,9 @@ int ark_hip_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validat
   Context* c = sc.c;
   const size_t ab = (size_t)CURVES[curve].fe_words * 16, eb = (size_t)SW_COMPRESSED_BYTES[curve];
   const size_t chunk = stage_chunk_points("ARK_HIP_DECOMPRESS_CHUNK_POINTS", ab, n);
-  if (c->stage_a.cap < chunk * eb || c->stage_c.cap < chunk * ab || (status && c->stage_b.cap < chunk)) {
+  if (c->stage_a.cap < chunk * eb || c->stage_c.cap < chunk * ab || (status && c->stage_b.cap < chunk))
     if (int rc = sync_compute(c)) return rc;
-    if (c->stage_a.ensure(chunk * eb) || c->stage_c.ensure(chunk * ab) || (status && c->stage_b.ensure(chunk))) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->stage_a.ensure(chunk * eb) || c->stage_c.ensure(chunk * ab) || (status && c->stage_b.ensure(chunk))) return ARK_HIP_ERR_NOMEM;
   if (int rc = sw_decompress_begin(c)) return rc;
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = n - off < chunk ? n - off : chunk;
@@ -383,10 +380,9 @@ int ark_hip_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t*
   Context* c = sc.c;
   const size_t ab = (size_t)CURVES[curve].fe_words * 16, eb = (size_t)SW_COMPRESSED_BYTES[curve];
   const size_t chunk = stage_chunk_points("ARK_HIP_DECOMPRESS_CHUNK_POINTS", ab, n);
-  if (c->stage_a.cap < chunk * ab || c->stage_c.cap < chunk * eb) {
+  if (c->stage_a.cap < chunk * ab || c->stage_c.cap < chunk * eb)
     if (int rc = sync_compute(c)) return rc;
-    if (c->stage_a.ensure(chunk * ab) || c->stage_c.ensure(chunk * eb)) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->stage_a.ensure(chunk * ab) || c->stage_c.ensure(chunk * eb)) return ARK_HIP_ERR_NOMEM;
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = n - off < chunk ? n - off : chunk;
     if (int rc = c->stager.upload(c->stage_a.p, (const char*)points_xy + off * ab, m * ab, c->stream)) return rc;

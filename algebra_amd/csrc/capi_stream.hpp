@@ -112,10 +112,9 @@ inline int msm_stream(Context* c, int curve, const void* d_bases, const uint64_t
     plan = msm_default_plan(curve, n, msm_scalar_bits(curve), false, skewed ? &widths : nullptr, knobs, /*streamed=*/true);
     if ((size_t)step * (size_t)plan.W >= (1ull << 32)) return ARK_HIP_ERR_SIZE;
     const size_t need = plan.nbuckets() * (size_t)CURVES[curve].fe_words * 32;  // XYZZ: four field elements
-    if (c->piece_buckets.cap < need) {
+    if (c->piece_buckets.cap < need)
       if (int rc = sync_compute(c)) return rc;
-      if (c->piece_buckets.ensure(need)) return ARK_HIP_ERR_NOMEM;
-    }
+    if (c->piece_buckets.ensure(need)) return ARK_HIP_ERR_NOMEM;
     for (int j = 0; j < 2; j++)
       if (!c->piece_ev[j]) ARK_HIP_TRY(hipEventCreateWithFlags(&c->piece_ev[j], hipEventDisableTiming));
   }
@@ -181,6 +180,7 @@ inline int msm_stream(Context* c, int curve, const void* d_bases, const uint64_t
       if (int rc = sync_compute(c)) return fail(rc);  // growing frees memory an enqueued MSM may still read
       if (c->ring_s[k].ensure(step * 32) || (ring_bases && c->ring_b[k].ensure(step * ab))) return fail(ARK_HIP_ERR_NOMEM);
     }
+    if (c->ring_s[k].ensure(cnt * 32) || (ring_bases && c->ring_b[k].ensure(cnt * ab))) return fail(ARK_HIP_ERR_NOMEM);  // (recorded)
     const void* pts = ring_bases ? (const void*)c->ring_b[k].p : (const void*)((const char*)d_bases + off * ab);
     if (host_bases)
       if (int rc = c->stager.upload((void*)pts, host_bases + off * (ab / 8), cnt * ab, c->copy_stream)) return fail(rc);

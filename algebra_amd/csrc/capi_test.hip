@@ -12,6 +12,9 @@
 #include "pointvec.cuh"
 #include "lazytest_api.hpp"
 #include "relaxtest_api.hpp"
+#include "scratch_list.hpp"
+#include <map>
+#include <string>
 using namespace arkhip;
 using namespace arkhip::capi;
 
@@ -150,6 +153,128 @@ elementwise_fn point_op_fn(int curve) {
     case 1: return test_point_op_BLS12_381_G1;
   }
   return nullptr;
+}
+
+// ---- scratch poisoning (scratch_list.hpp) ---------------------------------------------------------------------------------
+// fill [0, bytes) with the bytes of `word`, repeated (plain vector stores; the last word may be cut)
+__global__ void __launch_bounds__(256) scratch_fill_kernel(unsigned char* p, size_t bytes, u32 word) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w * 4 < bytes; w += stride) {
+    if (w * 4 + 4 <= bytes) {
+      ((u32*)p)[w] = word;
+    } else {
+      for (size_t o = w * 4; o < bytes; o++) p[o] = (unsigned char)(word >> (8 * (o & 3)));
+    }
+  }
+}
+// out[0] += the bytes of [lo, hi) that differ from the poison pattern, out[1] = min(out[1], offset of the first one)
+__global__ void __launch_bounds__(256) scratch_scan_kernel(const unsigned char* p, size_t lo, size_t hi, u32 word,
+                                                            unsigned long long* out) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  unsigned long long cnt = 0, first = ~0ull;
+  for (size_t w = lo / 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; w * 4 < hi; w += stride) {
+    const size_t b0 = w * 4;
+    if (b0 >= lo && b0 + 4 <= hi && ((const u32*)p)[w] == word) continue;
+    for (size_t o = b0 < lo ? lo : b0; o < b0 + 4 && o < hi; o++)
+      if (p[o] != (unsigned char)(word >> (8 * (o & 3)))) {
+        cnt++;
+        if (o < first) first = o;
+      }
+  }
+  if (cnt) {
+    atomicAdd(&out[0], cnt);
+    atomicMin(&out[1], first);
+  }
+}
+unsigned scratch_blocks(size_t bytes) {
+  const size_t b = (bytes / 4 + 256) / 256;
+  return (unsigned)(b < 4096 ? b : 4096);
+}
+// where every scratch buffer stood when it was last poisoned (per context: the hooks serve the calling thread's device)
+std::map<std::string, const void*> g_poisoned[MAX_DEV];
+std::mutex g_poisoned_mu;
+
+bool scratch_jobs_busy(Context* c) {
+  for (int l = 0; l < 2; l++) {
+    std::lock_guard<std::mutex> lock(c->msm[l].mu);
+    for (const auto& j : c->msm[l].jobs)
+      if (j.busy) return true;
+  }
+  return false;
+}
+int scratch_poison(Context* c, u32 word) {
+  if (scratch_jobs_busy(c)) return ARK_HIP_ERR_ARG;
+  ARK_HIP_TRY(hipDeviceSynchronize());   // every stream of the context (and any other of this device) has drained
+  std::lock_guard<std::mutex> lock(g_poisoned_mu);
+  auto& seen = g_poisoned[c->logical];
+  seen.clear();
+  for_each_scratch(*c, [&](const char* name, DevBuf& b) {
+    if (b.p && b.cap)
+      hipLaunchKernelGGL(scratch_fill_kernel, dim3(scratch_blocks(b.cap)), dim3(256), 0, c->stream, (unsigned char*)b.p, b.cap, word);
+    b.asked = 0;
+    seen[name] = b.p;
+  });
+  for_each_pinned_scratch(*c, [&](const char* name, void* p, size_t cap, size_t) {
+    for (size_t o = 0; p && o < cap; o++) ((unsigned char*)p)[o] = (unsigned char)(word >> (8 * (o & 3)));
+    seen[name] = p;
+  });
+  for (int l = 0; l < 2; l++)
+    for (auto& j : c->msm[l].jobs) j.pinned_asked = 0;
+  ARK_HIP_TRY(hipGetLastError());
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+int scratch_report(Context* c, u32 word, ark_hip_scratch_row* rows, size_t cap_rows, size_t* n_rows) {
+  ARK_HIP_TRY(hipDeviceSynchronize());
+  std::lock_guard<std::mutex> lock(g_poisoned_mu);
+  auto& seen = g_poisoned[c->logical];
+  size_t n = 0;
+  for_each_scratch(*c, [&](const char*, DevBuf&) { n++; });
+  const size_t ndev = n;
+  for_each_pinned_scratch(*c, [&](const char*, void*, size_t, size_t) { n++; });
+  *n_rows = n;
+  if (n > cap_rows) return ARK_HIP_ERR_SIZE;
+  unsigned long long* d_out = nullptr;
+  std::vector<unsigned long long> h_out(2 * ndev);
+  for (size_t i = 0; i < ndev; i++) h_out[2 * i] = 0, h_out[2 * i + 1] = ~0ull;
+  ARK_HIP_TRY(hipMalloc((void**)&d_out, h_out.size() * 8));
+  hipError_t e = hipMemcpy(d_out, h_out.data(), h_out.size() * 8, hipMemcpyHostToDevice);
+  auto fill_row = [&](ark_hip_scratch_row& r, const char* name, const void* p, size_t cap, size_t asked) {
+    memset(&r, 0, sizeof r);
+    snprintf(r.name, sizeof r.name, "%s", name);
+    r.cap = cap;
+    r.asked = asked;
+    auto it = seen.find(name);
+    r.regrown = (it == seen.end() || it->second != p) ? 1 : 0;
+    r.first_dirty_offset = ~0ull;
+  };
+  size_t i = 0;
+  for_each_scratch(*c, [&](const char* name, DevBuf& b) {
+    fill_row(rows[i], name, b.p, b.cap, b.asked);
+    if (e == hipSuccess && b.p && b.asked < b.cap)
+      hipLaunchKernelGGL(scratch_scan_kernel, dim3(scratch_blocks(b.cap - b.asked)), dim3(256), 0, c->stream, (const unsigned char*)b.p,
+                         b.asked, b.cap, word, d_out + 2 * i);
+    i++;
+  });
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out, h_out.size() * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d_out);
+  ARK_HIP_TRY(e);
+  for (size_t k = 0; k < ndev; k++) {
+    rows[k].dirty_beyond = h_out[2 * k];
+    rows[k].first_dirty_offset = h_out[2 * k + 1];
+  }
+  for_each_pinned_scratch(*c, [&](const char* name, void* p, size_t cap, size_t asked) {
+    fill_row(rows[i], name, p, cap, asked);
+    for (size_t o = asked; p && o < cap; o++)
+      if (((const unsigned char*)p)[o] != (unsigned char)(word >> (8 * (o & 3)))) {
+        if (!rows[i].dirty_beyond) rows[i].first_dirty_offset = o;
+        rows[i].dirty_beyond++;
+      }
+    i++;
+  });
+  return 0;
 }
 }  // namespace
 
@@ -322,10 +447,9 @@ int ark_hip_test_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_
   ARK_SCOPE(sc);
   Context* c = sc.c;
   const size_t fb = (size_t)CURVES[curve].fe_words * 8;
-  if (c->stage_a.cap < n * fb || c->stage_b.cap < n || c->stage_c.cap < n * fb) {
+  if (c->stage_a.cap < n * fb || c->stage_b.cap < n || c->stage_c.cap < n * fb)
     if (int rc = sync_compute(c)) return rc;
-    if (c->stage_a.ensure(n * fb) || c->stage_b.ensure(n) || c->stage_c.ensure(n * fb)) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->stage_a.ensure(n * fb) || c->stage_b.ensure(n) || c->stage_c.ensure(n * fb)) return ARK_HIP_ERR_NOMEM;
   ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, n * fb, hipMemcpyHostToDevice, c->stream));
   if (int rc = fn(c->stage_a.p, c->stage_c.p, c->stage_b.p, n, c->stream)) return rc;
   ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, n * fb, hipMemcpyDeviceToHost, c->stream));
@@ -500,10 +624,9 @@ int ark_hip_test_msm_sort_stages(int curve, const void* scalars, int on_device, 
   const void* d_scalars = scalars;
   if (!on_device) {
     const size_t bytes = n * (size_t)(sbytes ? sbytes : 32);
-    if (c->stage_a.cap < bytes) {
+    if (c->stage_a.cap < bytes)
       if (int rc = sync_compute(c)) return rc;
-      if (c->stage_a.ensure(bytes)) return ARK_HIP_ERR_NOMEM;
-    }
+    if (c->stage_a.ensure(bytes)) return ARK_HIP_ERR_NOMEM;
     ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, scalars, bytes, hipMemcpyHostToDevice, st));
     d_scalars = c->stage_a.p;
   }
@@ -549,10 +672,9 @@ int ark_hip_test_msm_pieces(int curve, const void* bases, const void* scalars, i
   const size_t ab = (size_t)CURVES[curve].fe_words * 16;
   const size_t need = plan.nbuckets() * (size_t)CURVES[curve].fe_words * 32;   // XYZZ: four field elements
   const bool grow = c->piece_buckets.cap < need || (!on_device && (c->stage_a.cap < n * 32 || c->stage_b.cap < n * ab));
-  if (grow) {
+  if (grow)
     if (int rc = sync_compute(c)) return rc;
-    if (c->piece_buckets.ensure(need) || (!on_device && (c->stage_a.ensure(n * 32) || c->stage_b.ensure(n * ab)))) return ARK_HIP_ERR_NOMEM;
-  }
+  if (c->piece_buckets.ensure(need) || (!on_device && (c->stage_a.ensure(n * 32) || c->stage_b.ensure(n * ab)))) return ARK_HIP_ERR_NOMEM;
   for (int j = 0; j < 2; j++)
     if (!c->piece_ev[j]) ARK_HIP_TRY(hipEventCreateWithFlags(&c->piece_ev[j], hipEventDisableTiming));
   const void *d_bases = bases, *d_scalars = scalars;
@@ -583,5 +705,53 @@ int ark_hip_test_base_hash(const uint64_t* p, size_t words, uint64_t out[2]) {
 int ark_hip_test_msm_sharded_emulated(int curve, int world, const void* const* d_bases, const void* const* d_scalars,
                                       const size_t* n_local, int scalars_are_montgomery, uint64_t* out_xyz, int* path) {
   return arkhip::capi::msm_sharded_emulated(curve, world, d_bases, d_scalars, n_local, scalars_are_montgomery, out_xyz, path);
+}
+// ---- scratch poisoning: what survives between calls (scratch_list.hpp names the buffers) ----
+// Fill the whole capacity of every scratch buffer of the calling thread's context, and the pinned staging areas, with `word`;
+// remember where each buffer stands; reset the high-water marks (DevBuf::asked, MsmJob::pinned_asked).  ARK_HIP_ERR_ARG while an
+// MSM job slot is busy: its result would be read out of a poisoned staging area.
+int ark_hip_test_scratch_poison(uint32_t word) {
+  ARK_SCOPE(sc);
+  return scratch_poison(sc.c, word);
+}
+// One row per scratch buffer (device buffers first, then the pinned areas): what was asked of it since the poison, whether it
+// moved, and how many bytes of its slack [asked, cap) no longer hold the poison.  Only the slack is looked at, on the device.
+int ark_hip_test_scratch_report(uint32_t word, ark_hip_scratch_row* rows, size_t cap_rows, size_t* n_rows) {
+  if (!n_rows || (cap_rows && !rows)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  return scratch_report(sc.c, word, rows, cap_rows, n_rows);
+}
+// The harness checking itself, with no product kernel involved: 0 when (a) a poisoned cell that nothing wrote reads back as the
+// poison and (b) four bytes planted in a buffer's slack -- inside its capacity -- come back as exactly that buffer's
+// dirty_beyond == 4 at the planted offset, every other row clean and none regrown.  A positive value names the step that failed.
+int ark_hip_test_scratch_selfcheck(void) {
+  const uint32_t word = 0x00000001u;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (c->stage_c.ensure(1024)) return ARK_HIP_ERR_NOMEM;
+  if (int rc = scratch_poison(c, word)) return rc;
+  uint32_t got = 0;
+  ARK_HIP_TRY(hipMemcpy(&got, c->stage_c.p, 4, hipMemcpyDeviceToHost));
+  if (got != word) return 1;
+  if (c->stage_c.ensure(1024)) return ARK_HIP_ERR_NOMEM;   // no growth: the request is only recorded
+  const size_t off = c->stage_c.asked + 8;
+  if (c->stage_c.asked != 1024 || off + 4 > c->stage_c.cap) return 2;
+  const uint32_t planted = ~word;
+  ARK_HIP_TRY(hipMemcpy((char*)c->stage_c.p + off, &planted, 4, hipMemcpyHostToDevice));
+  size_t n = 0;
+  (void)scratch_report(c, word, nullptr, 0, &n);
+  std::vector<ark_hip_scratch_row> rows(n);
+  if (int rc = scratch_report(c, word, rows.data(), n, &n)) return rc;
+  int hits = 0;
+  for (const auto& r : rows) {
+    if (r.regrown) return 3;
+    if (!strcmp(r.name, "stage_c")) {
+      if (r.dirty_beyond != 4 || r.first_dirty_offset != off || r.asked != 1024) return 4;
+      hits++;
+    } else if (r.dirty_beyond) {
+      return 5;
+    }
+  }
+  return hits == 1 ? 0 : 6;
 }
 }  // extern "C"

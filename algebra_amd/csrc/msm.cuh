@@ -1308,7 +1308,9 @@ static inline bool msm_lazy_enabled() { static const bool on = msm_knobs().lazy;
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  size_t asked = 0;  // the largest request since the last release(): the test hooks' line between requested bytes and slack
   int ensure(size_t bytes) {
+    if (bytes > asked) asked = bytes;
     if (bytes <= cap) return 0;
     if (p) (void)hipFree(p);
     p = nullptr;
@@ -1327,6 +1329,7 @@ struct DevBuf {
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
+    asked = 0;
   }
 };
 
@@ -1341,6 +1344,7 @@ struct MsmTimings {  // filled when requested (HIP events on the MSM stream), mi
 struct MsmJob {
   void* pinned = nullptr;
   size_t pinned_cap = 0;
+  size_t pinned_asked = 0;   // the largest request (DevBuf::asked's twin)
   hipEvent_t done = nullptr;
   hipEvent_t acc_done = nullptr;   // recorded in front of the bucket reduction: when the host tail's helpers are called in (msm_finish)
   bool busy = false;
@@ -1422,6 +1426,7 @@ struct MsmWorkspace {
       if (j.pinned) (void)hipHostFree(j.pinned);
       j.pinned = nullptr;
       j.pinned_cap = 0;
+      j.pinned_asked = 0;
       if (j.done) (void)hipEventDestroy(j.done);
       if (j.acc_done) (void)hipEventDestroy(j.acc_done);
       j.done = nullptr;
@@ -1432,6 +1437,7 @@ struct MsmWorkspace {
 };
 
 static inline int msm_job_pinned(MsmJob& j, size_t bytes) {
+  if (bytes > j.pinned_asked) j.pinned_asked = bytes;
   if (j.pinned_cap >= bytes) return 0;
   if (j.pinned) (void)hipHostFree(j.pinned);
   j.pinned = nullptr;

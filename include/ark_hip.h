@@ -687,6 +687,22 @@ int ark_hip_test_relaxed_raw_op(int field, int op, const uint32_t* in, uint32_t*
  * point), the accumulator in and out as raw limbs (x | y | zz | zzz).  kind (csrc/relaxtest_api.hpp AccKind): 0 xyzz_madd_relaxed
  * (other: x2 | y2, y2 as given), 1 xyzz_add_relaxed (other: XYZZ), 2 xyzz_canonical. */
 int ark_hip_test_relaxed_acc_op(int curve, int kind, const void* acc, const void* other, void* out, size_t n);
+/* ---- what survives between calls: poison for the scratch buffers, a canary in their slack (csrc/scratch_list.hpp) ----
+ * The device workspaces live as long as the process and only grow; no call may read a cell it did not write, and no kernel may
+ * write past what its enqueue asked for.  ark_hip_test_scratch_poison fills the WHOLE capacity of every scratch buffer of the
+ * calling thread's device, and the pinned staging areas, with `word`, remembers where each buffer stands and resets the
+ * high-water mark of the requests; ARK_HIP_ERR_ARG while an MSM job is in flight.  ark_hip_test_scratch_report gives one row per
+ * buffer: regrown (the buffer moved since the poison, or did not exist then), and the bytes of [asked, cap) that no longer
+ * hold the poison with the offset of the first (~0 if none).  *n_rows: the number of rows; ARK_HIP_ERR_SIZE (nothing written)
+ * when cap_rows is smaller.  ark_hip_test_scratch_selfcheck runs no product kernel: 0 when an unwritten poisoned cell reads
+ * back as the poison and four bytes it plants in stage_c's slack are reported as exactly that; else the failing step (> 0). */
+typedef struct ark_hip_scratch_row {
+  char name[40];
+  uint64_t cap, asked, regrown, dirty_beyond, first_dirty_offset;
+} ark_hip_scratch_row;
+int ark_hip_test_scratch_poison(uint32_t word);
+int ark_hip_test_scratch_report(uint32_t word, ark_hip_scratch_row* rows, size_t cap_rows, size_t* n_rows);
+int ark_hip_test_scratch_selfcheck(void);
 
 #endif /* ARK_HIP_TEST_HOOKS */
 
