@@ -179,6 +179,7 @@ TEST_SYMBOLS = {
     "ark_hip_test_base_hash": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "ark_hip_test_lazy_raw_op": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_lazy_acc_op": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_test_s30_op": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_relaxed_raw_op": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_relaxed_acc_op": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_test_msm_host_fold": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -12,6 +12,7 @@
 #include "pointvec.cuh"
 #include "lazytest_api.hpp"
 #include "relaxtest_api.hpp"
+#include "s30test_api.hpp"
 #include "scratch_list.hpp"
 #include <map>
 #include <string>
@@ -34,6 +35,7 @@ ARK_DECL_LAZYTEST_RAW(BLS12_377_G2) ARK_DECL_LAZYTEST_RAW(BLS12_381_G2)
 ARK_DECL_LAZYTEST_RAW(BN254_FR) ARK_DECL_LAZYTEST_RAW(BLS12_381_FR) ARK_DECL_LAZYTEST_RAW(BLS12_377_FR)
 ARK_DECL_LAZYTEST_ACC(BN254_G1) ARK_DECL_LAZYTEST_ACC(BLS12_381_G1) ARK_DECL_LAZYTEST_ACC(BLS12_377_G1)
 ARK_DECL_LAZYTEST_ACC(BLS12_377_G2) ARK_DECL_LAZYTEST_ACC(BLS12_381_G2)
+int test_s30_raw_op_BLS12_381_G1(int op, const void* d_in, void* d_out, size_t n, hipStream_t s);   // s30test.cuh
 #undef ARK_DECL_LAZYTEST_RAW
 #undef ARK_DECL_LAZYTEST_ACC
 #define ARK_DECL_RELAXTEST_RAW(NAME) int test_relaxed_raw_op_##NAME(int op, const void* d_in, void* d_out, size_t n, hipStream_t s);
@@ -505,6 +507,26 @@ int ark_hip_test_lazy_acc_op(int curve, int kind, const void* acc, const void* o
   const size_t rbytes = n * (kind == ACC_TO_BUCKET ? 4 * fb : slot);
   if (bbytes && !other) return ARK_HIP_ERR_ARG;
   return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, lazy_acc_fn_of(curve), kind, n);
+}
+
+int ark_hip_test_s30_op(int op, const void* in, void* out, size_t n) {
+  using namespace arkhip::s30test;
+  if (op < 0 || op >= OPS || !in || !out) return ARK_HIP_ERR_ARG;
+  const size_t ibytes = n * (size_t)in_words(op) * 4, obytes = n * (size_t)out_words(op) * 4;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) return 0;
+  if (c->stage_a.ensure(ibytes) || c->stage_c.ensure(obytes)) return ARK_HIP_ERR_NOMEM;
+  ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, ibytes, hipMemcpyHostToDevice, c->stream));
+#ifndef ARK_HIP_DEV
+  const int rc = test_s30_raw_op_BLS12_381_G1(op, c->stage_a.p, c->stage_c.p, n, c->stream);
+#else
+  const int rc = -1;
+#endif
+  if (rc) return rc == -1 ? ARK_HIP_ERR_ARG : rc;
+  ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, obytes, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 int ark_hip_test_relaxed_raw_op(int field, int op, const uint32_t* in, uint32_t* out, size_t n) {

@@ -1,0 +1,105 @@
+// The mixed addition of the bucket-accumulation kernel on 13 signed 30-bit digits (fp30s.cuh): the formulas and special
+// cases of xyzz_madd_lazy (ec28.cuh; bucket.rs:168-238, madd-2008-s), 3055 multiply-adds per addition instead of 3542.
+//
+// Bases and buckets live in HBM in the reference's canonical form (radix 2^384).  A gathered coordinate enters by repacking
+// only (FpS::from_canonical_shl: the residue itself in radix 2^390, in [0, 64 p)); buckets leave through FpS::to_canonical.
+//
+// Residues are SIGNED and unreduced: a difference is a digit-wise subtraction and one signed carry sweep, nothing adds a
+// multiple of p.  Every product operand is normalised (digits 0..11 in [-2^29, 2^29]), which is what the column bounds of
+// fp30s.cuh ask for.  Bounds in the comments are |value| in units of p, with R' / p > 629.9 and a product's
+// |a b| / R' + 0.5001;  the accumulator invariant is
+//     |x| < 2.02,  |y| < 0.61,  |zz|, |zzz| < 1          (all n)
+// re-derived exactly by tests/lazy30_model.py.
+//
+// "Is this difference zero mod p" is asked of the SQUARE that follows it, as in ec28.cuh: PP = P^2 is a product's output,
+// |PP| < p and its digits are the unique balanced ones, so PP = 0 mod p exactly when every digit is zero.
+#pragma once
+#include "ec28.cuh"
+#include "fp30s.cuh"
+
+namespace arkhip {
+
+template <class P>
+struct XYZZS {
+  FpS<P> x, y, zz, zzz;
+  bool inf;
+};
+
+// a gathered base (canonical limbs; the digit's sign already applied to y) as product operands: values in [0, 64), n
+template <class P>
+ARK_HD void s30_from_affine(const Fp<P>& x, const Fp<P>& y, FpS<P>& xs, FpS<P>& ys) {
+  xs = FpS<P>::from_canonical_shl(x.l);
+  ys = FpS<P>::from_canonical_shl(y.l);
+}
+// stored bucket -> accumulator: repack, then one product with the residue 1 per coordinate: < 64 / 629.9 + 0.5001 < 0.602
+template <class P>
+ARK_HD XYZZS<P> s30_from_bucket(const XYZZ<Fp<P>>& b) {
+  typedef FpS<P> F;
+  XYZZS<P> r;
+  r.inf = b.is_zero();
+  const F one = F::one();
+  r.x = F::mul(F::from_canonical_shl(b.x.l), one);
+  r.y = F::mul(F::from_canonical_shl(b.y.l), one);
+  r.zz = F::mul(F::from_canonical_shl(b.zz.l), one);
+  r.zzz = F::mul(F::from_canonical_shl(b.zzz.l), one);
+  return r;
+}
+// accumulator -> bucket in the reference's canonical form (|coordinate| < 2.02 < OUT_K = 4)
+template <class P>
+ARK_HD XYZZ<Fp<P>> s30_to_bucket(const XYZZS<P>& a) {
+  if (a.inf) return XYZZ<Fp<P>>::zero();
+  XYZZ<Fp<P>> r;
+  r.x = a.x.to_canonical();
+  r.y = a.y.to_canonical();
+  r.zz = a.zz.to_canonical();
+  r.zzz = a.zzz.to_canonical();
+  return r;
+}
+// acc = 2 (+-) base at `src`: rare (duplicate bases), so it goes through the 28-bit doubling and the canonical form, which
+// keeps the hot loop's registers free of it; expanded in place (ARK_COLD_HD), no call frame
+template <class P>
+ARK_COLD_HD void xyzz_mdbl_s(XYZZS<P>& acc, const char* src, bool neg) {
+  XYZZL<P> d;
+  xyzz_mdbl_lazy<P>(d, src, neg);
+  acc = s30_from_bucket<P>(lazy_to_bucket<P>(d));
+}
+
+// acc += (x2, y2): a non-identity base from s30_from_affine.  Returns true when the base EQUALS the accumulated point: the
+// caller then replaces the accumulator by the doubling of the base (xyzz_mdbl_s), as with xyzz_madd_lazy.
+template <class P>
+ARK_HD bool xyzz_madd_s(XYZZS<P>& acc, const FpS<P>& x2, const FpS<P>& y2) {
+  typedef FpS<P> F;
+  if (acc.inf) {
+    const F one = F::one();
+    acc.x = F::mul(x2, one);                          // < 64 * 1 / 629.9 + 0.5001 < 0.602 (n)
+    acc.y = F::mul(y2, one);                          // < 0.602 (n)
+    acc.zz = one;                                     // in [0, 1) (n)
+    acc.zzz = one;
+    acc.inf = false;
+    return false;
+  }
+  const F u2 = F::mul(x2, acc.zz);                    // < 64 * 1 / 629.9 + 0.5001 < 0.602 (n)
+  const F s2 = F::mul(y2, acc.zzz);                   // < 0.602 (n)
+  const F pd = F::sub(u2, acc.x);                     // P = U2 - X1: < 0.602 + 2.02 < 2.63 (n, swept)
+  const F rd = F::sub(s2, acc.y);                     // R = S2 - Y1: < 0.602 + 0.61 < 1.22 (n, swept)
+  const F pp = F::sqr(pd);                            // < 2.63^2 / 629.9 + 0.5001 < 0.5111 (n): |PP| < p, the zero test is exact
+  if (pp.is_zero_digits()) {                          // P = 0 mod p: same x -- doubling or infinity (bucket.rs:176-200)
+    if (F::sqr(rd).is_zero_digits()) return true;     // R = 0 mod p as well (|R^2 / R'| < 0.5025): the same point
+    acc.inf = true;
+    return false;
+  }
+  const F ppp = F::mul(pd, pp);                       // < 2.63 * 0.5111 / 629.9 + 0.5001 < 0.5023 (n)
+  const F q = F::mul(acc.x, pp);                      // < 2.02 * 0.5111 / 629.9 + 0.5001 < 0.5018 (n)
+  const F e = F::add_2b(ppp, q);                      // PPP + 2 Q: < 1.506 (n, swept; digits before the sweep <= 3 2^29)
+  const F x3 = F::sub(F::sqr(rd), e);                 // R^2 - PPP - 2 Q: < 0.5025 + 1.506 < 2.009 (n, swept)
+  const F t = F::sub(q, x3);                          // Q - X3: < 2.511 (n, swept)
+  // Y3 = R (Q - X3) - Y1 PPP as ONE sum of two products: (1.22 * 2.511 + 0.61 * 0.5023) / 629.9 + 0.5001 < 0.506.
+  // All four operands n with top digits below 2^23 (|value| < 2.63 p < 2^383): the 26-term column of fp30s.cuh.
+  acc.y = F::sop2(rd, t, F::neg(acc.y), ppp);
+  acc.zz = F::mul(acc.zz, pp);                        // < 1 * 0.5111 / 629.9 + 0.5001 < 0.501 (n)
+  acc.zzz = F::mul(acc.zzz, ppp);                     // < 0.501 (n)
+  acc.x = x3;
+  return false;
+}
+
+}  // namespace arkhip

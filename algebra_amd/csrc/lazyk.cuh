@@ -5,6 +5,14 @@
 #include "curves.cuh"
 #include "ec28.cuh"
 #include "ec28x2.cuh"
+#include "ec30s.cuh"
+#include <type_traits>
+
+// 1 (default): the plain accumulate kernel of the curves whose base field has the signed 30-bit form (fp30s.cuh: BLS12-381 G1)
+// runs on it; 0: on the 28-bit form, as every other kernel does (A/B builds)
+#ifndef ARK_LAZY_S30
+#define ARK_LAZY_S30 1
+#endif
 
 namespace arkhip {
 
@@ -64,6 +72,66 @@ struct LazyK<C, 1> {
     return a;
   }
 };
+
+// The same interface on 13 signed 30-bit digits (ec30s.cuh), for msm_accumulate_lazy_kernel alone: the reduction, heavy-run,
+// parts and prepared kernels keep LazyK.  Buckets enter and leave in the same canonical form, so the two forms mix freely.
+template <class C>
+struct LazySK {
+  typedef typename C::F FM;
+  typedef typename FM::P P;
+  typedef FpS<P> FL;
+  typedef XYZZS<P> Acc;
+  static constexpr u32 LANES = 1;
+  static constexpr int WORDS = 4 * FL::L + 1;   // one parked accumulator: four coordinates + the infinity flag
+  ARK_HD static Acc inf() {
+    Acc a;
+    a.inf = true;
+    a.x = a.y = a.zz = a.zzz = FL::zero();
+    return a;
+  }
+  ARK_HD static Acc from_bucket(const XYZZ<FM>& b) { return s30_from_bucket<P>(b); }
+  ARK_HD static XYZZ<FM> to_bucket(const Acc& a) { return s30_to_bucket<P>(a); }
+  ARK_HD static bool madd(Acc& acc, const Affine<FM>& p, bool neg) {
+    FL sx, sy;
+    s30_from_affine<P>(p.x, FM::cond_neg(p.y, neg), sx, sy);
+    return xyzz_madd_s<P>(acc, sx, sy);
+  }
+  ARK_HD static void mdbl(Acc& out, const char* src, bool neg) { xyzz_mdbl_s<P>(out, src, neg); }
+  // the accumulator as 4 x 13 digits + the infinity flag: the layout of the raw-digit test hook (s30test.cuh) -- the accumulate
+  // kernel parks nothing, so no product kernel calls these two
+  ARK_HD static void park(const Acc& a, i32* w) {
+#pragma unroll
+    for (int i = 0; i < FL::L; i++) {
+      w[i] = a.x.l[i];
+      w[FL::L + i] = a.y.l[i];
+      w[2 * FL::L + i] = a.zz.l[i];
+      w[3 * FL::L + i] = a.zzz.l[i];
+    }
+    w[4 * FL::L] = a.inf ? 1 : 0;
+  }
+  ARK_HD static Acc unpark(const i32* w) {
+    Acc a;
+#pragma unroll
+    for (int i = 0; i < FL::L; i++) {
+      a.x.l[i] = w[i];
+      a.y.l[i] = w[FL::L + i];
+      a.zz.l[i] = w[2 * FL::L + i];
+      a.zzz.l[i] = w[3 * FL::L + i];
+    }
+    a.inf = w[4 * FL::L] != 0;
+    return a;
+  }
+};
+// does the base field of C have the signed 30-bit form?  (S30Of<P> is specialised for it)
+template <class P, class = void> struct HasS30 : std::false_type {};
+template <class P> struct HasS30<P, std::void_t<typename S30Of<P>::T>> : std::true_type {};
+// what msm_accumulate_lazy_kernel computes on
+template <class C, int LANES_ = C::FA::LANES, class = void>
+struct AccumK { typedef LazyK<C> T; };
+#if ARK_LAZY_S30
+template <class C>
+struct AccumK<C, 1, std::enable_if_t<HasS30<typename C::F::P>::value>> { typedef LazySK<C> T; };
+#endif
 
 // G2: a lane pair owns the bucket; every lane holds ONE component of each coordinate
 template <class C>

@@ -562,7 +562,7 @@ __global__ void __launch_bounds__(256, ARK_LAZY_MIN_WAVES) msm_accumulate_lazy_k
                                                                   const u32* __restrict__ order, u32 nbuckets,
                                                                   const u32* __restrict__ d_thresh, int HB, int LB,
                                                                   int accum, char* __restrict__ buckets) {
-  typedef LazyK<C> K;            // prime-field curves: one lane per bucket; G2: one lane PAIR (uniform control flow)
+  typedef typename AccumK<C>::T K;   // prime-field curves: one lane per bucket (BLS12-381 G1: signed 30-bit digits, ec30s.cuh); G2: one lane PAIR
   typedef typename K::FM F;
   u32 t = (blockIdx.x * blockDim.x + threadIdx.x) / K::LANES;
   if (t >= nbuckets) return;

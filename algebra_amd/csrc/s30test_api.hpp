@@ -1,0 +1,29 @@
+// TEST HOOKS ONLY: the ops and word counts of the raw-digit interface to the signed 30-bit arithmetic (csrc/s30test.cuh has the
+// layout and the dispatcher), beside lazytest_api.hpp's for the 28-bit forms.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace arkhip {
+namespace s30test {
+
+enum Op : int {
+  MUL = 0,        // 2 slots -> 1 slot
+  SQR = 1,        // 1 -> 1
+  SOP2 = 2,       // 4 -> 1: a b + c d
+  SUB = 3,        // 2 -> 1
+  ADD_2B = 4,     // 2 -> 1: a + 2 b
+  FROM_CANONICAL_SHL = 5,   // 1 (12 canonical words) -> 1
+  TO_CANONICAL = 6,         // 1 -> 1 (12 canonical words)
+  MADD = 7,       // parked accumulator (LazySK::park: 4 x 13 digits + the infinity flag) | base x | base y (canonical, 12 words of
+                  // a slot each; the sign already on y) -> parked accumulator | 1 when the base equals the accumulated point
+  OPS = 8
+};
+constexpr int SLOT = 13;
+constexpr int in_words(int op) {
+  return op == MADD ? 4 * SLOT + 1 + 2 * SLOT : SLOT * (op == MUL || op == SUB || op == ADD_2B ? 2 : (op == SOP2 ? 4 : 1));
+}
+constexpr int out_words(int op) { return op == MADD ? 4 * SLOT + 2 : SLOT; }
+
+}  // namespace s30test
+}  // namespace arkhip

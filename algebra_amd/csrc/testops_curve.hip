@@ -4,6 +4,7 @@
 #include "testops.cuh"
 #include "lazytest.cuh"
 #include "relaxtest.cuh"
+#include "s30test.cuh"
 #include "pointcodec.cuh"
 #include "internal.hpp"
 #ifndef ARK_TEST_CURVE
@@ -30,6 +31,10 @@ int ARK_CAT(test_lazy_raw_op_, ARK_TEST_CURVE)(int op, int k, int h, const void*
 }
 int ARK_CAT(test_lazy_acc_op_, ARK_TEST_CURVE)(int kind, const void* acc, const void* other, void* out, size_t n, hipStream_t s) {
   return lazytest::lazy_acc_op_launch<ARK_TEST_CURVE>(kind, acc, other, out, n, s);
+}
+// raw-digit hook of the signed 30-bit form (s30test.cuh): served by the G1 unit whose accumulate kernel runs on it, -1 elsewhere
+int ARK_CAT(test_s30_raw_op_, ARK_TEST_CURVE)(int op, const void* in, void* out, size_t n, hipStream_t s) {
+  return s30test::s30_raw_op_launch<ARK_TEST_CURVE>(op, in, out, n, s);
 }
 // raw-limb hooks of the relaxed saturated-limb arithmetic (relaxtest.cuh): a G1 unit serves the Fp ops of its base field, a G2
 // unit the Fp2 / Fp2Half ops over it

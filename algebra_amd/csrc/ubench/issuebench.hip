@@ -1,7 +1,7 @@
 // Issue rates of the candidate multiplier / accumulator instructions on gfx950, same loop shape for each: four
 // independent dependency chains per lane, 32 instructions per asm statement.  Answers "is there a faster primitive than
 // v_mad_u64_u32 for multi-limb products" (DESIGN.md 6): 24-bit multiplies, FP64 fused multiply-adds (the 52-bit-limb
-// technique), 64-bit adds, against the plain 32-bit add as the full-rate yardstick.
+// technique), the signed multiply-add of fp30s.cuh's 30-bit digits, 64-bit adds, against the plain 32-bit add as the full-rate yardstick.
 //   hipcc -O3 --offload-arch=gfx950 issuebench.hip -o issuebench.bin
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +36,7 @@ KERNEL32(k_mullo32, "v_mul_lo_u32 %0, %4, %0", "v_mul_lo_u32 %1, %4, %1", "v_mul
 KERNEL32(k_mulhi32, "v_mul_hi_u32 %0, %4, %0", "v_mul_hi_u32 %1, %4, %1", "v_mul_hi_u32 %2, %4, %2", "v_mul_hi_u32 %3, %4, %3")
 KERNEL32(k_addc, "v_add_co_u32 %0, vcc, %4, %0", "v_addc_co_u32 %1, vcc, %5, %1, vcc", "v_add_co_u32 %2, vcc, %4, %2", "v_addc_co_u32 %3, vcc, %5, %3, vcc")
 KERNEL64(k_mad64, u64, u32, "v_mad_u64_u32 %0, vcc, %4, %5, %0", "v_mad_u64_u32 %1, vcc, %4, %5, %1", "v_mad_u64_u32 %2, vcc, %4, %5, %2", "v_mad_u64_u32 %3, vcc, %4, %5, %3")
+KERNEL64(k_madi64, int64_t, int32_t, "v_mad_i64_i32 %0, vcc, %4, %5, %0", "v_mad_i64_i32 %1, vcc, %4, %5, %1", "v_mad_i64_i32 %2, vcc, %4, %5, %2", "v_mad_i64_i32 %3, vcc, %4, %5, %3")
 KERNEL64(k_add64, u64, u64, "v_lshl_add_u64 %0, %4, 0, %0", "v_lshl_add_u64 %1, %4, 0, %1", "v_lshl_add_u64 %2, %4, 0, %2", "v_lshl_add_u64 %3, %4, 0, %3")
 KERNEL64(k_fma64, double, double, "v_fma_f64 %0, %4, %5, %0", "v_fma_f64 %1, %4, %5, %1", "v_fma_f64 %2, %4, %5, %2", "v_fma_f64 %3, %4, %5, %3")
 KERNEL64(k_mul64f, double, double, "v_mul_f64 %0, %4, %0", "v_mul_f64 %1, %4, %1", "v_mul_f64 %2, %4, %2", "v_mul_f64 %3, %4, %3")
@@ -50,7 +51,7 @@ int main() {
   struct { const char* name; kern_t k; } ks[] = {
       {"v_add_u32            ", k_add32},  {"v_mad_u32_u24        ", k_mad24},   {"v_mul_hi_u32_u24     ", k_mulhi24},
       {"v_mul_lo_u32         ", k_mullo32}, {"v_mul_hi_u32         ", k_mulhi32}, {"v_add_co + v_addc_co ", k_addc},
-      {"v_mad_u64_u32        ", k_mad64},  {"v_lshl_add_u64       ", k_add64},   {"v_fma_f64            ", k_fma64},
+      {"v_mad_u64_u32        ", k_mad64},  {"v_mad_i64_i32        ", k_madi64}, {"v_lshl_add_u64       ", k_add64},   {"v_fma_f64            ", k_fma64},
       {"v_mul_f64            ", k_mul64f}};
   for (auto& e : ks) {
     for (int w : {2, 8}) {

@@ -677,6 +677,12 @@ int ark_hip_test_lazy_raw_op(int field, int op, int k, int h, const uint32_t* in
  * acc = +/- 2 base, 4 acc += stored bucket (other: canonical XYZZ), 5 acc += parked accumulator, 6 acc = 2 acc,
  * 7 from_bucket (acc: canonical XYZZ), 8 to_bucket (out: canonical XYZZ). */
 int ark_hip_test_lazy_acc_op(int curve, int kind, const void* acc, const void* other, void* out, size_t n);
+/* The signed 13 x 30-bit arithmetic of the plain accumulate kernel of BLS12-381 G1 (csrc/fp30s.cuh, ec30s.cuh) ONE OP AT A TIME
+ * ON RAW DIGITS: lane t reads in_words(op) int32 words and writes out_words(op) (csrc/s30test_api.hpp: a field element is a slot of
+ * 13 signed digits as the test chose them, a canonical element the first 12 words of a slot).  op: 0 mul, 1 sqr, 2 sop2, 3 sub,
+ * 4 add_2b, 5 from_canonical_shl, 6 to_canonical, 7 the mixed addition on a parked accumulator (4 x 13 digits + the infinity
+ * flag | base x | base y -> accumulator | "equal points"); anything else is ARK_HIP_ERR_ARG. */
+int ark_hip_test_s30_op(int op, const void* in, void* out, size_t n);
 /* The RELAXED arithmetic on saturated 32-bit limbs (csrc/fp.cuh: residues in [0, 2p), Fp, Fp2, Fp2Half) ONE OP AT A TIME ON RAW
  * LIMBS: lane t reads `arity` slots of N words (N = 8 or 12: whatever representative the test chose) at in[(t * arity + j) * N]
  * and writes N + 1 words at out[t * (N + 1)]: the limbs as the function returns them, then its boolean result.  The Fp2 and

@@ -12,7 +12,7 @@ Derivations follow ff/src/fields/models/fp/montgomery_backend.rs:21-60 (R, R2, I
 ff-macros/src/montgomery/mod.rs:40-52 (TWO_ADIC_ROOT_OF_UNITY = generator^((p-1)/2^s)).
 
 Outputs:  oracle/constants.h  (64-bit limbs, C)      algebra_amd/csrc/params.hpp (32-bit limbs, C++)
-          algebra_amd/csrc/curve_consts.hpp (subgroup generators, host side)
+          algebra_amd/csrc/curve_consts.hpp (subgroup generators, host side; the signed 30-bit constants of csrc/fp30s.cuh)
           algebra_amd/csrc/check_consts.hpp (what the base-set check needs: COEFF_B, the subgroup order r and, for
           BLS12-381 G1, the endomorphism constant beta and x^2 -- csrc/pointcheck.cuh)
           algebra_amd/csrc/codec_consts.hpp (what the compressed-point codec needs: square-root exponents, (p-1)/2,
@@ -71,6 +71,25 @@ def field_consts(p, g):
 
 def limbs(x, n, w):
     return [(x >> (w * i)) & ((1 << w) - 1) for i in range(n)]
+
+
+def signed_digits(x, n, w):
+    """x >= 0 as n digits of w bits in [-2^(w-1), 2^(w-1)); the top digit takes what is left"""
+    out = []
+    for _ in range(n - 1):
+        d = x & ((1 << w) - 1)
+        if d >= 1 << (w - 1):
+            d -= 1 << w
+        out.append(d)
+        x = (x - d) >> w
+    out.append(x)
+    return out
+
+
+# fields that get the signed 30-bit form of fp30s.cuh (S30_<field> in curve_consts.hpp), and the multiple of p that makes
+# an accumulator coordinate (|v| < 2.2 p, ec30s.cuh) positive on its way out
+S30_FIELDS = ["BLS12_381_FQ"]
+S30_OUT_K = 4
 
 
 def c_arr(x, n, w):
@@ -318,6 +337,20 @@ def main():
             for c in t:
                 words += limbs(c * f["R"] % p, n, 64)
         h.append("static const uint64_t GEN_%s[%d] = {%s};" % (name, len(words), ", ".join("0x%016xULL" % v for v in words)))
+    # signed 30-bit form of the accumulate kernel (fp30s.cuh): 13 digits in [-2^29, 2^29), Montgomery radix 2^390
+    for name in S30_FIELDS:
+        p = fc[name]["p"]
+        sw, sl = 30, 13
+        assert sw * sl >= 32 * fc[name]["n64"] * 2 and p >> (sw * (sl - 1)) < 1 << (sw - 1)
+        sd = lambda x: "{" + ", ".join("%d" % v for v in signed_digits(x, sl, sw)) + "}"
+        h.append("struct S30_%s {" % name)
+        h.append("  static constexpr int W = %d, L = %d;" % (sw, sl))
+        h.append("  static constexpr int32_t P[%d] = %s;   // p, signed digits" % (sl, sd(p)))
+        h.append("  static constexpr uint32_t INV = 0x%08xu;   // -p^-1 mod 2^W" % (fc[name]["inv64"] & ((1 << sw) - 1)))
+        h.append("  static constexpr int32_t ONE[%d] = %s;   // 2^(W L) mod p, signed digits: the residue 1" % (sl, sd(pow(2, sw * sl, p))))
+        h.append("  static constexpr int OUT_K = %d;           // OUT_K p is added to a signed residue on its way to the canonical form" % S30_OUT_K)
+        h.append("  static constexpr int32_t OUT_KP[%d] = %s;   // OUT_K p, signed digits" % (sl, sd(S30_OUT_K * p)))
+        h.append("};")
     h.append("} // namespace arkhip")
     open(os.path.join(root, "algebra_amd", "csrc", "curve_consts.hpp"), "w").write("\n".join(h) + "\n")
     open(os.path.join(root, "algebra_amd", "csrc", "check_consts.hpp"), "w").write(check_consts_header(fc))
