@@ -2,11 +2,11 @@
 // cases of xyzz_madd_lazy (ec28.cuh; bucket.rs:168-238, madd-2008-s), 3055 multiply-adds per addition instead of 3542.
 //
 // Bases and buckets live in HBM in the reference's canonical form (radix 2^384).  A gathered coordinate enters by repacking
-// only (FpS::from_canonical_shl: the residue itself in radix 2^390, in [0, 64 p)); buckets leave through FpS::to_canonical.
+// only (FpS::from_canonical_u: the residue itself in radix 2^390, in [0, 64 p)); buckets leave through FpS::to_canonical.
 //
 // Residues are SIGNED and unreduced: a difference is a digit-wise subtraction and one signed carry sweep, nothing adds a
-// multiple of p.  Every product operand is normalised (digits 0..11 in [-2^29, 2^29]), which is what the column bounds of
-// fp30s.cuh ask for.  Bounds in the comments are |value| in units of p, with R' / p > 629.9 and a product's
+// multiple of p.  Every product operand is normalised (digits 0..11 in [-2^29, 2^29]) -- but for the gathered coordinate, which is
+// unsigned beside a normalised operand -- which is what the column bounds of fp30s.cuh ask for.  Bounds in the comments are |value| in units of p, with R' / p > 629.9 and a product's
 // |a b| / R' + 0.5001;  the accumulator invariant is
 //     |x| < 2.02,  |y| < 0.61,  |zz|, |zzz| < 1          (all n)
 // re-derived exactly by tests/lazy30_model.py.
@@ -17,6 +17,11 @@
 #include "ec28.cuh"
 #include "fp30s.cuh"
 
+// 1 (default): a gathered coordinate enters unsigned; 0: recoded to signed digits, the kernel as it first shipped (A/B builds)
+#ifndef ARK_S30_UNSIGNED_GATHER
+#define ARK_S30_UNSIGNED_GATHER 1
+#endif
+
 namespace arkhip {
 
 template <class P>
@@ -25,11 +30,20 @@ struct XYZZS {
   bool inf;
 };
 
-// a gathered base (canonical limbs; the digit's sign already applied to y) as product operands: values in [0, 64), n
+// a gathered base (canonical limbs; the digit's sign already applied to y) as product operands: values in [0, 64).  Each is ONE
+// operand of U2 = x2 zz, of S2 = y2 zzz or of the first point's product by one, whose other operand is normalised, and of
+// nothing else: it stays unsigned (FpS::from_canonical_u) and skips the signed recoding -- a carry add, a sign-extending extract
+// and a carry per digit, 98 vector instructions per addition.  U2, S2 and everything after them are digit for digit what the
+// recoded operand gives (tests/lazy30_diet_host_check.hip, tests/test_gpu_lazy30_diet.py).
 template <class P>
 ARK_HD void s30_from_affine(const Fp<P>& x, const Fp<P>& y, FpS<P>& xs, FpS<P>& ys) {
+#if ARK_S30_UNSIGNED_GATHER
+  xs = FpS<P>::from_canonical_u(x.l);
+  ys = FpS<P>::from_canonical_u(y.l);
+#else
   xs = FpS<P>::from_canonical_shl(x.l);
   ys = FpS<P>::from_canonical_shl(y.l);
+#endif
 }
 // stored bucket -> accumulator: repack, then one product with the residue 1 per coordinate: < 64 / 629.9 + 0.5001 < 0.602
 template <class P>

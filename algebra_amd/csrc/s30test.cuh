@@ -55,6 +55,17 @@ ARK_HD void s30_raw_apply(int op, const i32* in, i32* out) {
       out[4 * SLOT + 1] = eq ? 1 : 0;
       return;
     }
+    case FROM_CANONICAL_U: r = F::from_canonical_u(canon(0).l); break;
+    case MADD_ENTRY: {
+      typename K::Acc acc = K::unpark(in);
+      Affine<FM> p;
+      p.x = canon(4 * SLOT + 1);
+      p.y = canon(5 * SLOT + 1);
+      const bool eq = K::madd(acc, p, in[6 * SLOT + 1] != 0);
+      K::park(acc, out);
+      out[4 * SLOT + 1] = eq ? 1 : 0;
+      return;
+    }
     default: break;
   }
 #pragma unroll

@@ -17,13 +17,18 @@ enum Op : int {
   TO_CANONICAL = 6,         // 1 -> 1 (12 canonical words)
   MADD = 7,       // parked accumulator (LazySK::park: 4 x 13 digits + the infinity flag) | base x | base y (canonical, 12 words of
                   // a slot each; the sign already on y) -> parked accumulator | 1 when the base equals the accumulated point
-  OPS = 8
+  FROM_CANONICAL_U = 8,     // 1 (12 canonical words) -> 1: the unsigned repack of a gathered coordinate
+  MADD_ENTRY = 9,    // MADD's input with the base as gathered (y WITHOUT the sign) | 1 for a negative digit -> MADD's output: the
+                     // accumulate kernel's own entry (LazySK::madd)
+  OPS = 10
 };
 constexpr int SLOT = 13;
 constexpr int in_words(int op) {
-  return op == MADD ? 4 * SLOT + 1 + 2 * SLOT : SLOT * (op == MUL || op == SUB || op == ADD_2B ? 2 : (op == SOP2 ? 4 : 1));
+  return op == MADD       ? 4 * SLOT + 1 + 2 * SLOT
+       : op == MADD_ENTRY ? 4 * SLOT + 1 + 2 * SLOT + 1
+                          : SLOT * (op == MUL || op == SUB || op == ADD_2B ? 2 : (op == SOP2 ? 4 : 1));
 }
-constexpr int out_words(int op) { return op == MADD ? 4 * SLOT + 2 : SLOT; }
+constexpr int out_words(int op) { return op == MADD || op == MADD_ENTRY ? 4 * SLOT + 2 : SLOT; }
 
 }  // namespace s30test
 }  // namespace arkhip
