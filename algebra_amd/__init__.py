@@ -6,6 +6,7 @@ HIP library replaces:
     ark_ec::VariableBaseMSM            -> algebra_amd.msm   (msm, msm_unchecked, msm_bigint)
     ark_poly::Radix2EvaluationDomain   -> algebra_amd.domain.Radix2EvaluationDomain
     ark_poly::DenseMultilinearExtension -> algebra_amd.mle.DenseMultilinearExtension
+    ark_linear_sumcheck's ListOfProductsOfPolynomials and its prover's rounds -> algebra_amd.sumcheck.ListOfProducts
 
 All arithmetic runs in libark_hip.so (hand-written HIP for gfx950) through the C ABI of
 include/ark_hip.h; this package holds no arithmetic and no CPU fallback.
@@ -21,3 +22,4 @@ from .domain import Radix2EvaluationDomain  # noqa: F401
 from .poly import DeviceVec, poly_mul, poly_mul_host  # noqa: F401
 from .points import DevicePoints  # noqa: F401
 from .mle import DenseMultilinearExtension, mle_fold_plan, mle_fold_tiles  # noqa: F401
+from .sumcheck import ListOfProducts, SumcheckProof, sumcheck_plan  # noqa: F401

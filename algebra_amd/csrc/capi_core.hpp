@@ -552,6 +552,11 @@ inline int fr_axpy_dispatch(int field, const void* a, const uint64_t* k4, const 
   ARK_FIELD_SWITCH(field, X);
 #undef X
 }
+inline int sumcheck_round_dispatch(int field, const SumcheckRound& rd, hipStream_t st) {
+#define X(NAME) sumcheck_round_##NAME(rd, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
 inline int fr_op_dispatch(int field, int op, const void* a, const void* b, void* r, size_t n, hipStream_t st) {
 #define X(NAME) field_op_##NAME(op, a, b, r, n, st)
   ARK_FIELD_SWITCH(field, X);

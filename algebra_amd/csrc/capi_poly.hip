@@ -1,10 +1,12 @@
 // C ABI of libark_hip.so: polynomial operations on device-resident vectors -- evaluation at a point, division by x - z and
 // by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products -- and dense
-// multilinear extensions: fix_variables, evaluate, relabel, a + k x (see include/ark_hip.h; kernels: polyops.cuh, mle.cuh).
+// multilinear extensions: fix_variables, evaluate, relabel, a + k x -- and the sumcheck prover's round over such tables (see
+// include/ark_hip.h; kernels: polyops.cuh, mle.cuh, sumcheck.cuh).
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "polyops.cuh"
 #include "mle.cuh"
+#include "sumcheck.cuh"
 using namespace arkhip;
 using namespace arkhip::capi;
 
@@ -130,6 +132,9 @@ inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
   return x < y + nb && y < x + na;
 }
+
+static_assert(SUMCHECK_MAX_TABLES == ARK_HIP_SUMCHECK_MAX_TABLES && SUMCHECK_MAX_TERMS == ARK_HIP_SUMCHECK_MAX_TERMS &&
+                  SUMCHECK_MAX_DEGREE == ARK_HIP_SUMCHECK_MAX_DEGREE, "the header publishes the kernels' limits");
 
 }  // namespace
 
@@ -321,6 +326,72 @@ int ark_hip_fr_axpy_device(int field, const void* d_a, const uint64_t* k, const 
   Context* c = sc.c;
   if (int rc = fr_axpy_dispatch(field, d_a, k, d_x, d_r, n, c->stream)) return rc;
   return mark_producer(c);
+}
+
+int ark_hip_sumcheck_plan(unsigned num_vars, unsigned ntables, unsigned degree, int fused, int* blocks, int* pairs_per_lane,
+                          int* stages) {
+  if (!blocks || !pairs_per_lane || !stages || num_vars == 0 || num_vars >= 64) return ARK_HIP_ERR_ARG;
+  if (ntables == 0 || ntables > (unsigned)SUMCHECK_MAX_TABLES || degree == 0 || degree > (unsigned)SUMCHECK_MAX_DEGREE) return ARK_HIP_ERR_ARG;
+  unsigned b;
+  size_t ppl;
+  sumcheck_geometry((int)num_vars - (fused ? 1 : 0), &b, &ppl);
+  *blocks = (int)b;
+  *pairs_per_lane = ppl > 0x7fffffffu ? 0x7fffffff : (int)ppl;
+  *stages = b > 1 ? 2 : 1;
+  return 0;
+}
+
+int ark_hip_sumcheck_round_device(int field, const void* const* d_tables, unsigned ntables, unsigned num_vars,
+                                  const unsigned* term_len, const unsigned* term_tables, const uint64_t* coeffs, unsigned nterms,
+                                  const uint64_t* r_prev, void* const* d_out_tables, uint64_t* out_evals) {
+  if (!field_served(field) || !d_tables || !term_len || !term_tables || !coeffs || !out_evals || (r_prev && !d_out_tables)) return ARK_HIP_ERR_ARG;
+  if (ntables == 0 || ntables > (unsigned)SUMCHECK_MAX_TABLES || nterms == 0 || nterms > (unsigned)SUMCHECK_MAX_TERMS) return ARK_HIP_ERR_ARG;
+  if (num_vars == 0 || num_vars >= 64 || num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
+  SumcheckRound rd = {};
+  rd.tm.ntables = ntables;
+  rd.tm.nterms = nterms;
+  for (unsigned j = 0, at = 0; j < nterms; j++) {
+    const unsigned len = term_len[j];
+    if (len == 0 || len > (unsigned)SUMCHECK_MAX_DEGREE) return ARK_HIP_ERR_ARG;
+    rd.tm.len[j] = len;
+    if (len > rd.tm.degree) rd.tm.degree = len;
+    for (unsigned q = 0; q < len; q++, at++) {
+      if (term_tables[at] >= ntables) return ARK_HIP_ERR_ARG;
+      rd.tm.tab[j] |= term_tables[at] << (8 * q);
+    }
+    for (int q = 0; q < 4; q++) { rd.tm.coeff[j].l[2 * q] = (u32)coeffs[4 * j + q]; rd.tm.coeff[j].l[2 * q + 1] = (u32)(coeffs[4 * j + q] >> 32); }
+    if (field_is_one(field, coeffs + 4 * j)) rd.tm.unit |= 1u << j;
+  }
+  const size_t n = (size_t)1 << num_vars;
+  for (unsigned k = 0; k < ntables; k++) {
+    if (!d_tables[k] || (r_prev && !d_out_tables[k])) return ARK_HIP_ERR_ARG;
+    rd.tb.src[k] = (const char*)d_tables[k];
+    if (!r_prev) continue;
+    rd.tb.dst[k] = (char*)d_out_tables[k];
+    for (unsigned i = 0; i < ntables; i++)
+      if (ranges_overlap(d_tables[i], n * 32, d_out_tables[k], n * 16)) return ARK_HIP_ERR_ARG;
+    for (unsigned i = 0; i < k; i++)
+      if (ranges_overlap(d_out_tables[i], n * 16, d_out_tables[k], n * 16)) return ARK_HIP_ERR_ARG;
+  }
+  const unsigned degree = rd.tm.degree;
+  rd.fused = r_prev ? 1 : 0;
+  rd.last = r_prev && num_vars == 1;
+  if (r_prev)
+    for (int q = 0; q < 4; q++) { rd.tm.r.l[2 * q] = (u32)r_prev[q]; rd.tm.r.l[2 * q + 1] = (u32)(r_prev[q] >> 32); }
+  const int m = (int)num_vars - rd.fused;
+  rd.npairs = m >= 1 ? (size_t)1 << (m - 1) : 1;
+  size_t ppl;
+  sumcheck_geometry(m, &rd.blocks, &ppl);
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  // [result area: one element per t | one partial per workgroup and t]
+  if (int rc = poly_scratch(c, (size_t)SUMCHECK_EVALS * (1 + (rd.blocks > 1 ? rd.blocks : 0)))) return rc;
+  rd.out = c->poly_work.p;
+  rd.partials = (char*)c->poly_work.p + SUMCHECK_EVALS * 32;
+  if (int rc = sumcheck_round_dispatch(field, rd, c->stream)) return rc;
+  ARK_HIP_TRY(hipMemcpyAsync(out_evals, c->poly_work.p, (size_t)(degree + 1) * 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 }  // extern "C"

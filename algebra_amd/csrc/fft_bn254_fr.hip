@@ -1,8 +1,9 @@
-// Instantiation of the radix-2 FFT and the pointwise field kernels and the polynomial and multilinear kernels for BN254_FR.
+// Instantiation of the radix-2 FFT and the pointwise field kernels and the polynomial, multilinear and sumcheck kernels for BN254_FR.
 #include "fft.cuh"
 #include "devops.cuh"
 #include "polyops.cuh"
 #include "mle.cuh"
+#include "sumcheck.cuh"
 #include "internal.hpp"
 namespace arkhip {
 int fft_run_BN254_FR(FftWorkspace& ws, void* d_data, int k, const uint64_t* root4, const uint64_t* pre4, const uint64_t* post4,
@@ -49,6 +50,7 @@ int mle_relabel_BN254_FR(const void* src, size_t n, int a, int b, int k, void* d
 int fr_axpy_BN254_FR(const void* a, const uint64_t* k4, const void* x, void* r, size_t n, hipStream_t s) {
   return fr_axpy_launch<Fp<BN254_FR>>(a, k4, x, r, n, s);
 }
+int sumcheck_round_BN254_FR(const SumcheckRound& rd, hipStream_t s) { return sumcheck_round_launch<Fp<BN254_FR>>(rd, s); }
 int fft_axis_BN254_FR(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4, hipStream_t s) {
   return fft_axis_run<BN254_FR>(ws, d_src, d_dst, G, cols, root4, s);
 }

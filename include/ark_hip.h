@@ -525,6 +525,38 @@ int ark_hip_mle_fold_plan(unsigned num_vars, unsigned dim, int* tile_log, int* p
  * fewer multiplies per element, and large tables get more of them.  Tests read from it which kernel variant a size runs. */
 int ark_hip_mle_fold_tiles(unsigned num_vars, unsigned dim, int* tiles_log);
 
+/* ---- the sumcheck prover's round on device tables --------------------------------------------
+ * The sum is a list of products of multilinear tables, each with a coefficient (ListOfProductsOfPolynomials of
+ * ark-linear-sumcheck): sum_j c_j prod_{k in term j} f_k.  Tables follow the conventions above: 2^num_vars Montgomery
+ * elements on the device, index bit 0 the first variable. */
+#define ARK_HIP_SUMCHECK_MAX_TABLES 8
+#define ARK_HIP_SUMCHECK_MAX_TERMS 8
+#define ARK_HIP_SUMCHECK_MAX_DEGREE 4
+/* One round.  d_tables: ntables device tables of 2^num_vars elements (the same table may appear twice).  Term j has
+ * term_len[j] factors (1 .. ARK_HIP_SUMCHECK_MAX_DEGREE); term_tables holds their table indices, term after term
+ * (term_len[0] + ... + term_len[nterms-1] entries, repeats allowed); coeffs holds nterms elements.  D = the longest term.
+ * Without r_prev, for m = num_vars >= 1 and T = the tables:
+ *   out_evals[t] = sum_{b < 2^(m-1)} sum_j c_j prod_{k in term j} ( T_k[2b] + t (T_k[2b+1] - T_k[2b]) ),  t = 0 .. D.
+ * With r_prev (a HOST element) the call first binds the first variable to it: it writes
+ *   T'_k[i] = T_k[2i] + r_prev (T_k[2i+1] - T_k[2i])
+ * to d_out_tables[k] (ntables tables of 2^(num_vars-1) elements) and computes the sums above over T' with m = num_vars - 1,
+ * reading every table once.  When m = 0 nothing is left to sum: the one-element tables are the values f_k(r_1 .. r_nu),
+ * out_evals[0] = sum_j c_j prod_k T'_k[0] -- what the verifier's last check compares -- and out_evals[1 .. D] are zero.
+ * out_evals: HOST, D + 1 elements; the call waits for them.  Host pointers are read before the call returns.
+ * ARK_HIP_ERR_ARG, before any device is touched: an unknown field; a null pointer; ntables, nterms or a term_len that is 0 or
+ * above its limit; a table index >= ntables; num_vars >= 64 or a table whose bytes a size_t cannot count; num_vars == 0
+ * (with or without r_prev); an output table that overlaps an input table or another output table -- there is NO in-place
+ * form, one workgroup writes where another still reads.  d_out_tables is not read without r_prev. */
+int ark_hip_sumcheck_round_device(int field, const void* const* d_tables, unsigned ntables, unsigned num_vars,
+                                  const unsigned* term_len, const unsigned* term_tables, const uint64_t* coeffs, unsigned nterms,
+                                  const uint64_t* r_prev, void* const* d_out_tables, uint64_t* out_evals);
+/* Host only, no device needed: the launch geometry of that round for 2^num_vars-element tables (fused: with r_prev).
+ * *blocks: workgroups of 256 lanes; *pairs_per_lane: pairs of rows one lane walks (> 1 once the grid is capped; saturates at INT_MAX); *stages: 1
+ * when one workgroup holds the whole sum, 2 when a second launch adds the workgroups' partial sums.  Tests read from it
+ * which variant a size runs.  ntables and degree select the kernel (tables held per lane), not the geometry. */
+int ark_hip_sumcheck_plan(unsigned num_vars, unsigned ntables, unsigned degree, int fused, int* blocks, int* pairs_per_lane,
+                          int* stages);
+
 /* ---- one process per GPU: RCCL inside the library ---------------------------------------------------------------
  * The reference chunks an MSM by base range and sums the chunk results (variable_base/mod.rs:521-557); an FFT shards by
  * coefficient range with ONE transpose between two rounds of local butterflies (the four-step form of the radix-2

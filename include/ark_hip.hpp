@@ -848,6 +848,108 @@ class DenseMultilinearExtension {
   }
 };
 
+// The sumcheck prover over device-resident tables.  ListOfProducts has the shape of ark-linear-sumcheck's
+// ListOfProductsOfPolynomials: sum_b sum_j c_j prod_{k in term j} f_k(b), the tables shared by pointer (the same
+// DenseMultilinearExtension object added to several products, or twice to one, is one table; the caller keeps the objects
+// alive and unmoved).  round() is one call of ark_hip_sumcheck_round_device on the tables where they lie; prove() runs the
+// whole prover against the caller's source of challenges.  Nothing is hashed and nothing verified here.
+template <int FIELD_ID>
+struct SumcheckProof {
+  std::vector<std::vector<Fr>> rounds;   // rounds[i]: the D + 1 evaluations g_i(0 .. D)
+  std::vector<Fr> point;                 // the nu challenges
+  std::vector<Fr> final_evaluations;     // f_k(point), the tables in the order they were first added
+  Fr final_value;                        // sum_j c_j prod_k f_k(point): what the verifier's last check compares
+};
+template <int FIELD_ID>
+class ListOfProducts {
+ public:
+  using Mle = DenseMultilinearExtension<FIELD_ID>;
+  using Vec = DeviceVec<FIELD_ID>;
+  explicit ListOfProducts(size_t num_vars) : num_vars_(num_vars), left_(num_vars) {}
+  size_t num_vars() const { return num_vars_; }
+  size_t max_multiplicands() const { return degree_; }
+  // adds coefficient * prod mles
+  void add_product(const std::vector<const Mle*>& mles, const Fr& coefficient) {
+    if (mles.empty() || mles.size() > ARK_HIP_SUMCHECK_MAX_DEGREE) throw Error(ARK_HIP_ERR_ARG, "a product has 1 to 4 factors");
+    if (lens_.size() >= ARK_HIP_SUMCHECK_MAX_TERMS) throw Error(ARK_HIP_ERR_ARG, "too many products");
+    if (started_) throw Error(ARK_HIP_ERR_ARG, "rounds have been run on this list");
+    std::vector<const Mle*> tables = tables_;
+    std::vector<unsigned> idx;
+    for (const Mle* m : mles) {
+      if (m->num_vars() != num_vars_) throw Error(ARK_HIP_ERR_ARG, "the product's num_vars differ from the list's");
+      size_t i = 0;
+      while (i < tables.size() && tables[i] != m) i++;
+      if (i == tables.size()) tables.push_back(m);
+      idx.push_back((unsigned)i);
+    }
+    if (tables.size() > ARK_HIP_SUMCHECK_MAX_TABLES) throw Error(ARK_HIP_ERR_ARG, "too many distinct tables");
+    tables_ = tables;
+    lens_.push_back((unsigned)idx.size());
+    flat_.insert(flat_.end(), idx.begin(), idx.end());
+    coeffs_.push_back(coefficient);
+    if (idx.size() > degree_) degree_ = idx.size();
+  }
+  // The D + 1 evaluations of the round polynomial over the tables as bound so far; with r_prev the first remaining variable
+  // is bound to it first, in the same launch, into tables of the list's own (the caller's are never written).
+  std::vector<Fr> round(const Fr* r_prev = nullptr) {
+    if (lens_.empty() || left_ == 0) throw Error(ARK_HIP_ERR_ARG, "no products, or every variable is bound");
+    if (!started_) {
+      for (const Mle* m : tables_) cur_.push_back(m->evaluations().device_ptr());
+      started_ = true;
+    }
+    if (!r_prev) return call(cur_, left_, nullptr, nullptr);
+    if (sets_[0].empty())   // halves and quarters: the output of a bind is never the set it reads
+      for (int s = 0; s < 2; s++)
+        for (size_t k = 0; k < tables_.size(); k++) sets_[s].push_back(Vec::uninit((size_t)1 << (num_vars_ > (size_t)(1 + s) ? num_vars_ - 1 - s : 0)));
+    std::vector<void*> outs;
+    for (Vec& v : sets_[next_]) outs.push_back(v.device_ptr());
+    std::vector<Fr> evals = call(cur_, left_, r_prev, outs.data());
+    cur_.assign(outs.begin(), outs.end());
+    left_--;
+    next_ ^= 1;
+    return evals;
+  }
+  // Runs the nu + 1 calls: call 0 has no bind, calls 1 .. nu bind the challenge before.  challenge(i, evals) gets round i's
+  // evaluations and returns the verifier's element for it.
+  template <class Challenge>
+  SumcheckProof<FIELD_ID> prove(Challenge&& challenge) {
+    if (started_ || num_vars_ == 0) throw Error(ARK_HIP_ERR_ARG, "rounds have been run on this list, or num_vars == 0");
+    SumcheckProof<FIELD_ID> out;
+    std::vector<Fr> evals = round();
+    for (size_t i = 0; i < num_vars_; i++) {
+      const Fr r = challenge(i, evals);
+      out.rounds.push_back(evals);
+      out.point.push_back(r);
+      evals = round(&r);
+    }
+    for (const void* p : cur_) {   // the one-element tables: f_k(point)
+      Fr v;
+      check(ark_hip_memcpy_d2h(v.limbs.data(), p, 32), "ark_hip_memcpy_d2h");
+      out.final_evaluations.push_back(v);
+    }
+    out.final_value = evals[0];
+    return out;
+  }
+
+ private:
+  size_t num_vars_, left_, degree_ = 0;
+  std::vector<const Mle*> tables_;
+  std::vector<unsigned> lens_, flat_;
+  std::vector<Fr> coeffs_;
+  std::vector<const void*> cur_;
+  std::vector<Vec> sets_[2];
+  int next_ = 0;
+  bool started_ = false;
+  std::vector<Fr> call(const std::vector<const void*>& tables, size_t num_vars, const Fr* r_prev, void* const* outs) {
+    std::vector<Fr> evals(degree_ + 1);
+    check(ark_hip_sumcheck_round_device(FIELD_ID, tables.data(), (unsigned)tables.size(), (unsigned)num_vars, lens_.data(), flat_.data(),
+                                        (const uint64_t*)coeffs_.data(), (unsigned)lens_.size(), r_prev ? r_prev->limbs.data() : nullptr,
+                                        outs, (uint64_t*)evals.data()),
+          "ark_hip_sumcheck_round_device");
+    return evals;
+  }
+};
+
 // ---- point vectors kept on the device: elementwise scalar multiplication, elementwise sum, two-scalar fold ----
 // The reference maps `Projective *= ScalarField` (ec/src/models/short_weierstrass/group.rs:556-570 -> mul_bigint ->
 // SWCurveConfig::mul_projective, short_weierstrass/mod.rs:101-109 -> double_and_add, ec/src/scalar_mul/mod.rs:29-60) and

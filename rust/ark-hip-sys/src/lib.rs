@@ -207,6 +207,15 @@ extern "C" {
     pub fn ark_hip_mle_fold_plan(num_vars: c_uint, dim: c_uint, tile_log: *mut c_int, passes: *mut c_int, widths: *mut c_int) -> c_int;
     /// Host only: log2 of the tiles one wave takes in each launch of that plan (`tiles_log`: 8 entries).
     pub fn ark_hip_mle_fold_tiles(num_vars: c_uint, dim: c_uint, tiles_log: *mut c_int) -> c_int;
+    /// One sumcheck round over `ntables` device tables of `2^num_vars` elements: `out_evals[t]`, `t = 0 ..= D`, of
+    /// `sum_b sum_j c_j prod_k (T_k[2b] + t (T_k[2b+1] - T_k[2b]))`; with `r_prev` (host element) the first variable is bound
+    /// to it first, into `d_out_tables`, in the same launch.  `term_tables`: the factors' table indices, term after term.
+    pub fn ark_hip_sumcheck_round_device(field: c_int, d_tables: *const *const c_void, ntables: c_uint, num_vars: c_uint,
+                                         term_len: *const c_uint, term_tables: *const c_uint, coeffs: *const u64, nterms: c_uint,
+                                         r_prev: *const u64, d_out_tables: *const *mut c_void, out_evals: *mut u64) -> c_int;
+    /// Host only: workgroups, pairs of rows per lane and reduction stages of that round.
+    pub fn ark_hip_sumcheck_plan(num_vars: c_uint, ntables: c_uint, degree: c_uint, fused: c_int, blocks: *mut c_int,
+                                 pairs_per_lane: *mut c_int, stages: *mut c_int) -> c_int;
     /// `r[i] = a[i] * k`, `k`: one Montgomery element in host memory (read before the call returns).
     pub fn ark_hip_fr_scale_device(field: c_int, d_a: *const c_void, k: *const u64, d_r: *mut c_void, n: usize) -> c_int;
     pub fn ark_hip_fft_in_place_degree_aware_device(field: c_int, dom: *const ark_hip_radix2_domain, d_data: *mut c_void,

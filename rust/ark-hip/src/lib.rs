@@ -14,7 +14,9 @@
 //!   vectors in HBM -- `evaluate_over_domain` -> pointwise `+=`, `-=`, `*=` -> `interpolate` with one upload per input
 //!   and one download, instead of two PCIe crossings per transform through the `EvaluationDomain` hook.
 //! * **multilinear provers**: [`mle::DenseMultilinearExtension`] keeps a table of 2^nu evaluations in HBM -- the commitment
-//!   is an MSM on it, `fix_variables` / `evaluate` / `relabel` bind and move its variables without a PCIe crossing.
+//!   is an MSM on it, `fix_variables` / `evaluate` / `relabel` bind and move its variables without a PCIe crossing, and
+//!   [`sumcheck::ListOfProducts`] runs the sumcheck prover's rounds over such tables: the round sums of a list of products,
+//!   with the previous challenge bound in the same pass.
 //!
 //! Beyond the reference's surface: [`msm::PreparedBases`] (a fixed SRS resident on the GPU with its per-window
 //! multiples), [`msm::MsmJob`] (asynchronous MSMs), [`msm::msm_multi`] (one MSM over all GPUs of the node).
@@ -26,11 +28,13 @@ pub mod domain;
 pub mod mle;
 pub mod msm;
 pub mod points;
+pub mod sumcheck;
 pub use ark_hip_sys as sys;
 pub use ark_hip_sys::{BLS12_377_G1, BLS12_377_G2, BLS12_381_G1, BLS12_381_G2, BN254_G1};
 pub use device::{DeviceError, DeviceEvaluations, DeviceVec};
 pub use points::DevicePoints;
 pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension};
+pub use sumcheck::{ListOfProducts, SumcheckProof};
 pub use msm::{check_bases, compress_bases, decompress_bases, serve_group_coefficients, sw_msm, sw_msm_bigint, BaseCheck, HipServed};
 #[cfg(feature = "ec-hook")]
 pub use msm::{sw_batch_mul, sw_msm_small, sw_normalize_batch};
