@@ -1,12 +1,17 @@
 // The mixed addition of the bucket-accumulation kernel on 13 signed 30-bit digits (fp30s.cuh): the formulas and special
-// cases of xyzz_madd_lazy (ec28.cuh; bucket.rs:168-238, madd-2008-s), 3055 multiply-adds per addition instead of 3542.
+// cases of xyzz_madd_lazy (ec28.cuh; bucket.rs:168-238, madd-2008-s), 3055 multiply-adds per addition instead of 3542 (3103 with the
+// differences folded into the products).
 //
 // Bases and buckets live in HBM in the reference's canonical form (radix 2^384).  A gathered coordinate enters by repacking
 // only (FpS::from_canonical_u: the residue itself in radix 2^390, in [0, 64 p)); buckets leave through FpS::to_canonical.
 //
 // Residues are SIGNED and unreduced: a difference is a digit-wise subtraction and one signed carry sweep, nothing adds a
-// multiple of p.  Every product operand is normalised (digits 0..11 in [-2^29, 2^29]) -- but for the gathered coordinate, which is
-// unsigned beside a normalised operand -- which is what the column bounds of fp30s.cuh ask for.  Bounds in the comments are |value| in units of p, with R' / p > 629.9 and a product's
+// multiple of p -- and where a product computes the minuend and nothing else reads it (P = U2 - X1, R = S2 - Y1, X3 = R^2 - PPP -
+// 2 Q), the subtrahend's digits leave inside the product's high columns instead (FpS::mul_sub, FpS::sqr_sub2; ARK_S30_FUSED_DIFF):
+// the same digits without the subtraction and its sweep, one multiply-add per digit (48 in all); only t = Q - X3 keeps a sweep.
+// Every product operand is normalised (digits 0..11 in [-2^29, 2^29]) -- but for the gathered coordinate, which is unsigned beside a
+// normalised operand -- which is what the column bounds of fp30s.cuh ask for.  Bounds in the comments are |value| in units of p,
+// with R' / p > 629.9 and a product's
 // |a b| / R' + 0.5001;  the accumulator invariant is
 //     |x| < 2.02,  |y| < 0.61,  |zz|, |zzz| < 1          (all n)
 // re-derived exactly by tests/lazy30_model.py.
@@ -20,6 +25,12 @@
 // 1 (default): a gathered coordinate enters unsigned; 0: recoded to signed digits, the kernel as it first shipped (A/B builds)
 #ifndef ARK_S30_UNSIGNED_GATHER
 #define ARK_S30_UNSIGNED_GATHER 1
+#endif
+// Differences folded into the product that computes them (FpS::mul_sub, FpS::sqr_sub2): bit 0: P = U2 - X1 and R = S2 - Y1,
+// bit 1: X3 = R^2 - PPP - 2 Q.  3 (default): both; 0: every difference digit-wise with its own carry sweep, the chain as it was
+// (A/B builds; 1 and 2 measure each fusion alone).  The digits are the same under every setting.
+#ifndef ARK_S30_FUSED_DIFF
+#define ARK_S30_FUSED_DIFF 3
 #endif
 
 namespace arkhip {
@@ -92,10 +103,16 @@ ARK_HD bool xyzz_madd_s(XYZZS<P>& acc, const FpS<P>& x2, const FpS<P>& y2) {
     acc.inf = false;
     return false;
   }
+#if ARK_S30_FUSED_DIFF & 1
+  // U2 = x2 zz and S2 = y2 zzz (< 64 * 1 / 629.9 + 0.5001 < 0.602) have no other consumer: X1 and Y1 leave inside the high columns
+  const F pd = F::mul_sub(x2, acc.zz, acc.x);         // P = U2 - X1: < 0.602 + 2.02 < 2.63 (n: the columns' own digits)
+  const F rd = F::mul_sub(y2, acc.zzz, acc.y);        // R = S2 - Y1: < 0.602 + 0.61 < 1.22 (n)
+#else
   const F u2 = F::mul(x2, acc.zz);                    // < 64 * 1 / 629.9 + 0.5001 < 0.602 (n)
   const F s2 = F::mul(y2, acc.zzz);                   // < 0.602 (n)
   const F pd = F::sub(u2, acc.x);                     // P = U2 - X1: < 0.602 + 2.02 < 2.63 (n, swept)
   const F rd = F::sub(s2, acc.y);                     // R = S2 - Y1: < 0.602 + 0.61 < 1.22 (n, swept)
+#endif
   const F pp = F::sqr(pd);                            // < 2.63^2 / 629.9 + 0.5001 < 0.5111 (n): |PP| < p, the zero test is exact
   if (pp.is_zero_digits()) {                          // P = 0 mod p: same x -- doubling or infinity (bucket.rs:176-200)
     if (F::sqr(rd).is_zero_digits()) return true;     // R = 0 mod p as well (|R^2 / R'| < 0.5025): the same point
@@ -104,8 +121,13 @@ ARK_HD bool xyzz_madd_s(XYZZS<P>& acc, const FpS<P>& x2, const FpS<P>& y2) {
   }
   const F ppp = F::mul(pd, pp);                       // < 2.63 * 0.5111 / 629.9 + 0.5001 < 0.5023 (n)
   const F q = F::mul(acc.x, pp);                      // < 2.02 * 0.5111 / 629.9 + 0.5001 < 0.5018 (n)
+#if ARK_S30_FUSED_DIFF & 2
+  // R^2 (< 0.5025) and PPP + 2 Q (< 1.506) have no other consumer: a high column takes - ppp_i - 2 q_i, at most 3 2^29 more
+  const F x3 = F::sqr_sub2(rd, ppp, q);               // R^2 - PPP - 2 Q: < 0.5025 + 1.506 < 2.009 (n: the columns' own digits)
+#else
   const F e = F::add_2b(ppp, q);                      // PPP + 2 Q: < 1.506 (n, swept; digits before the sweep <= 3 2^29)
   const F x3 = F::sub(F::sqr(rd), e);                 // R^2 - PPP - 2 Q: < 0.5025 + 1.506 < 2.009 (n, swept)
+#endif
   const F t = F::sub(q, x3);                          // Q - X3: < 2.511 (n, swept)
   // Y3 = R (Q - X3) - Y1 PPP as ONE sum of two products: (1.22 * 2.511 + 0.61 * 0.5023) / 629.9 + 0.5001 < 0.506.
   // All four operands n with top digits below 2^23 (|value| < 2.63 p < 2^383): the 26-term column of fp30s.cuh.

@@ -3,8 +3,8 @@
 //
 // One call = one op on n lanes.  Lane t reads IN_WORDS(op) int32 words at in[t * IN_WORDS] and writes OUT_WORDS(op) words at
 // out[t * OUT_WORDS].  A field element is a slot of 13 signed digits AS THE TEST CHOSE THEM (not canonical words); a canonical
-// element takes the first 12 words of a slot.  s30_raw_apply is __host__ __device__: compiled for the device, mul / sqr / sop2
-// are the v_mad_i64_i32 column chains the accumulate kernel runs; compiled for the host they are the portable _c forms, and
+// element takes the first 12 words of a slot.  s30_raw_apply is __host__ __device__: compiled for the device, mul / sqr / sop2 / mul_sub /
+// sqr_sub2 are the v_mad_i64_i32 column chains the accumulate kernel runs; compiled for the host they are the portable _c forms, and
 // the same vector files go through both.  The kernel indexes memory by lane only.
 #pragma once
 #include "curves.cuh"
@@ -66,6 +66,8 @@ ARK_HD void s30_raw_apply(int op, const i32* in, i32* out) {
       out[4 * SLOT + 1] = eq ? 1 : 0;
       return;
     }
+    case MUL_SUB: r = F::mul_sub(ld(0), ld(1), ld(2)); break;
+    case SQR_SUB2: r = F::sqr_sub2(ld(0), ld(1), ld(2)); break;
     default: break;
   }
 #pragma unroll

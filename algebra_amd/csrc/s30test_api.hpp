@@ -20,13 +20,15 @@ enum Op : int {
   FROM_CANONICAL_U = 8,     // 1 (12 canonical words) -> 1: the unsigned repack of a gathered coordinate
   MADD_ENTRY = 9,    // MADD's input with the base as gathered (y WITHOUT the sign) | 1 for a negative digit -> MADD's output: the
                      // accumulate kernel's own entry (LazySK::madd)
-  OPS = 10
+  MUL_SUB = 10,   // 3 -> 1: a b - s inside the product's high columns
+  SQR_SUB2 = 11,  // 3 -> 1: a^2 - s - 2 d
+  OPS = 12
 };
 constexpr int SLOT = 13;
 constexpr int in_words(int op) {
   return op == MADD       ? 4 * SLOT + 1 + 2 * SLOT
        : op == MADD_ENTRY ? 4 * SLOT + 1 + 2 * SLOT + 1
-                          : SLOT * (op == MUL || op == SUB || op == ADD_2B ? 2 : (op == SOP2 ? 4 : 1));
+                          : SLOT * (op == MUL || op == SUB || op == ADD_2B ? 2 : op == SOP2 ? 4 : op == MUL_SUB || op == SQR_SUB2 ? 3 : 1);
 }
 constexpr int out_words(int op) { return op == MADD || op == MADD_ENTRY ? 4 * SLOT + 2 : SLOT; }
 
