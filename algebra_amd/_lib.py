@@ -153,6 +153,11 @@ SYMBOLS = {
     "ark_hip_fr_axpy_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_mle_fold_plan": (C.c_int, [C.c_uint, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ark_hip_mle_fold_tiles": (C.c_int, [C.c_uint, C.c_uint, C.POINTER(C.c_int)]),
+    "ark_hip_mle_eq_table_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]),
+    "ark_hip_mle_quotients_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ark_hip_mle_eq_plan": (C.c_int, [C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ark_hip_mle_quotients_plan": (C.c_int, [C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int)]),
     "ark_hip_sumcheck_round_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
                                                 C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "ark_hip_sumcheck_plan": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

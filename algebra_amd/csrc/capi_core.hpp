@@ -552,6 +552,16 @@ inline int fr_axpy_dispatch(int field, const void* a, const uint64_t* k4, const 
   ARK_FIELD_SWITCH(field, X);
 #undef X
 }
+inline int mle_eq_dispatch(int field, const void* hi, const FrConst& top, int unit, const MlePoint& pt, int log_n, void* dst, hipStream_t st) {
+#define X(NAME) mle_eq_##NAME(hi, top, unit, pt, log_n, dst, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int mle_quot_dispatch(int field, const void* src, int log_n, int w, const MlePoint& pt, void* quot, void* dst, hipStream_t st) {
+#define X(NAME) mle_quot_##NAME(src, log_n, w, pt, quot, dst, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
 inline int sumcheck_round_dispatch(int field, const SumcheckRound& rd, hipStream_t st) {
 #define X(NAME) sumcheck_round_##NAME(rd, st)
   ARK_FIELD_SWITCH(field, X);

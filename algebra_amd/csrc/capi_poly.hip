@@ -1,11 +1,12 @@
 // C ABI of libark_hip.so: polynomial operations on device-resident vectors -- evaluation at a point, division by x - z and
 // by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products -- and dense
-// multilinear extensions: fix_variables, evaluate, relabel, a + k x -- and the sumcheck prover's round over such tables (see
-// include/ark_hip.h; kernels: polyops.cuh, mle.cuh, sumcheck.cuh).
+// multilinear extensions: fix_variables, evaluate, relabel, a + k x, the eq table and an opening's quotients -- and the
+// sumcheck prover's round over such tables (see include/ark_hip.h; kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh).
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "polyops.cuh"
 #include "mle.cuh"
+#include "mle_open.cuh"
 #include "sumcheck.cuh"
 using namespace arkhip;
 using namespace arkhip::capi;
@@ -127,6 +128,10 @@ inline int mle_fold_run(Context* c, int field, const void* d_evals, unsigned num
     cur = dst;
   }
   return 0;
+}
+inline void mle_point_fill(MlePoint& pt, const uint64_t* point, int w) {
+  for (int j = 0; j < w; j++, point += 4)
+    for (int q = 0; q < 4; q++) { pt.r[j].l[2 * q] = (u32)point[q]; pt.r[j].l[2 * q + 1] = (u32)(point[q] >> 32); }
 }
 inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -300,6 +305,90 @@ int ark_hip_mle_evaluate_device(int field, const void* d_evals, unsigned num_var
   }
   if (int rc = mle_fold_run(c, field, d_evals, num_vars, point, num_vars, nullptr)) return rc;
   return result_to_host(c, out);
+}
+
+int ark_hip_mle_eq_plan(unsigned num_vars, int* tile_log, int* passes, int* widths, int* tiles_log) {
+  if (!tile_log || !passes || !widths || !tiles_log || num_vars >= 64) return ARK_HIP_ERR_ARG;
+  *tile_log = MLE_TILE_LOG;
+  for (int p = 0; p < MLE_MAX_PASSES; p++) widths[p] = tiles_log[p] = 0;
+  *passes = mle_eq_passes((int)num_vars, widths);
+  for (int p = 0, m = 0; p < *passes; p++) tiles_log[p] = mle_eq_group_log(m += widths[p]);
+  return 0;
+}
+
+int ark_hip_mle_eq_table_device(int field, const uint64_t* point, unsigned num_vars, const uint64_t* scale, void* d_out) {
+  if (!field_served(field) || !d_out || num_vars >= 64 || (num_vars && !point)) return ARK_HIP_ERR_ARG;
+  if (num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
+  int widths[MLE_MAX_PASSES];
+  const int passes = mle_eq_passes((int)num_vars, widths);
+  FrConst top = {};
+  if (scale)
+    for (int q = 0; q < 4; q++) { top.l[2 * q] = (u32)scale[q]; top.l[2 * q + 1] = (u32)(scale[q] >> 32); }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  // [result slot (unused) | the table of the top widths[0] variables | of the top widths[0] + widths[1] | ...]
+  size_t scratch = 1;
+  for (int p = 0, m = 0; p + 1 < passes; p++) scratch += (size_t)1 << (m += widths[p]);
+  if (int rc = poly_scratch(c, scratch)) return rc;
+  char* w = (char*)c->poly_work.p + 32;
+  const void* hi = nullptr;
+  for (int p = 0, m = 0; p < passes; p++) {
+    m += widths[p];
+    MlePoint pt = {};   // zeros for the variables a short launch lacks
+    mle_point_fill(pt, point + 4 * ((size_t)num_vars - m), widths[p]);
+    void* dst = p + 1 < passes ? (void*)w : d_out;
+    if (int rc = mle_eq_dispatch(field, hi, top, scale ? 0 : 1, pt, m, dst, c->stream)) return rc;
+    w += ((size_t)1 << m) * 32;
+    hi = dst;
+  }
+  return mark_producer(c);
+}
+
+int ark_hip_mle_quotients_plan(unsigned num_vars, int* tile_log, int* passes, int* widths, int* tiles_log) {
+  if (!tile_log || !passes || !widths || !tiles_log || num_vars >= 64) return ARK_HIP_ERR_ARG;
+  *tile_log = MLE_TILE_LOG;
+  for (int p = 0; p < MLE_MAX_PASSES; p++) widths[p] = tiles_log[p] = 0;   // a wave of the quotient kernel takes one tile
+  *passes = mle_fold_passes((int)num_vars, widths);
+  return 0;
+}
+
+int ark_hip_mle_quotients_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* point, void* d_quot,
+                                 uint64_t* out_value) {
+  if (!field_served(field) || !d_evals || num_vars >= 64 || (num_vars && (!point || !d_quot))) return ARK_HIP_ERR_ARG;
+  if (num_vars > 58) return ARK_HIP_ERR_ARG;
+  const size_t n = (size_t)1 << num_vars;
+  if (num_vars && ranges_overlap(d_evals, n * 32, d_quot, (n - 1) * 32)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (num_vars == 0) {   // a constant: no quotient, the value is its one table entry
+    if (!out_value) return 0;
+    ARK_HIP_TRY(hipMemcpyAsync(out_value, d_evals, 32, hipMemcpyDeviceToHost, c->stream));
+    ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  int widths[MLE_MAX_PASSES];
+  const int passes = mle_fold_passes((int)num_vars, widths);
+  // [result slot | the table after launch 0 | after launch 1 | ...], as mle_fold_run
+  size_t scratch = 1;
+  for (int p = 0, m = (int)num_vars; p + 1 < passes; p++) scratch += (size_t)1 << (m -= widths[p]);
+  if (int rc = poly_scratch(c, scratch)) return rc;
+  char* w = (char*)c->poly_work.p + 32;
+  const void* cur = d_evals;
+  int m = (int)num_vars;
+  for (int p = 0; p < passes; p++) {
+    MlePoint pt = {};
+    mle_point_fill(pt, point, widths[p]);
+    point += 4 * widths[p];
+    void* dst = p + 1 < passes ? (void*)w : c->poly_work.p;
+    // the segment of variable i = num_vars - m starts at element 2^num_vars - 2^m
+    char* quot = (char*)d_quot + (n - ((size_t)1 << m)) * 32;
+    if (int rc = mle_quot_dispatch(field, cur, m, widths[p], pt, quot, dst, c->stream)) return rc;
+    m -= widths[p];
+    w += ((size_t)1 << m) * 32;
+    cur = dst;
+  }
+  if (out_value) return result_to_host(c, out_value);
+  return mark_producer(c);
 }
 
 int ark_hip_mle_relabel_device(int field, const void* d_evals, unsigned num_vars, unsigned a, unsigned b, unsigned k, void* d_out) {

@@ -3,6 +3,7 @@
 #include "devops.cuh"
 #include "polyops.cuh"
 #include "mle.cuh"
+#include "mle_open.cuh"
 #include "sumcheck.cuh"
 #include "internal.hpp"
 namespace arkhip {
@@ -49,6 +50,12 @@ int mle_relabel_BLS12_381_FR(const void* src, size_t n, int a, int b, int k, voi
 }
 int fr_axpy_BLS12_381_FR(const void* a, const uint64_t* k4, const void* x, void* r, size_t n, hipStream_t s) {
   return fr_axpy_launch<Fp<BLS12_381_FR>>(a, k4, x, r, n, s);
+}
+int mle_eq_BLS12_381_FR(const void* hi, const FrConst& top, int unit, const MlePoint& pt, int log_n, void* dst, hipStream_t s) {
+  return mle_eq_launch<Fp<BLS12_381_FR>>(hi, top, unit, pt, log_n, dst, s);
+}
+int mle_quot_BLS12_381_FR(const void* src, int log_n, int w, const MlePoint& pt, void* quot, void* dst, hipStream_t s) {
+  return mle_quot_launch<Fp<BLS12_381_FR>>(src, log_n, w, pt, quot, dst, s);
 }
 int sumcheck_round_BLS12_381_FR(const SumcheckRound& rd, hipStream_t s) { return sumcheck_round_launch<Fp<BLS12_381_FR>>(rd, s); }
 int fft_axis_BLS12_381_FR(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4, hipStream_t s) {

@@ -16,6 +16,7 @@ struct FftWorkspace;
 struct FftTimings;
 struct PolyPowers;
 struct MlePoint;
+struct FrConst;
 struct SumcheckRound;
 
 // one function per curve / field, defined in msm_<curve>.hip / fft_<field>.hip
@@ -77,6 +78,8 @@ ARK_DECL_CURVE(BLS12_381_G2)
   int mle_fold_##NAME(const void* d_src, int log_n, int w, const MlePoint& pt, void* d_dst, hipStream_t s);         \
   int mle_relabel_##NAME(const void* d_src, size_t n, int a, int b, int k, void* d_dst, hipStream_t s);             \
   int fr_axpy_##NAME(const void* d_a, const uint64_t* k4, const void* d_x, void* d_r, size_t n, hipStream_t s);     \
+  int mle_eq_##NAME(const void* d_hi, const FrConst& top, int unit, const MlePoint& pt, int log_n, void* d_dst, hipStream_t s); \
+  int mle_quot_##NAME(const void* d_src, int log_n, int w, const MlePoint& pt, void* d_quot, void* d_dst, hipStream_t s); \
   int sumcheck_round_##NAME(const SumcheckRound& rd, hipStream_t s);                                                \
   int fft_roots_##NAME(FftWorkspace& ws, int k, const uint64_t* root4, hipStream_t s, const uint32_t** out);        \
   int fft_scalars_##NAME(FftWorkspace& ws, const uint64_t* base4, const uint64_t* mul4, size_t count, void* d_out,  \

@@ -7,6 +7,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import curves as cv
 from ._lib import check, lib
 from .poly import DeviceVec
 
@@ -24,6 +25,50 @@ def mle_fold_tiles(num_vars, dim):
     tiles = (C.c_int * 8)()
     check(lib().ark_hip_mle_fold_tiles(num_vars, dim, tiles), "ark_hip_mle_fold_tiles")
     return [tiles[i] for i in range(len(mle_fold_plan(num_vars, dim)[1]))]
+
+
+def _plan5(entry, num_vars):
+    t, ps = C.c_int(), C.c_int()
+    widths, tiles = (C.c_int * 8)(), (C.c_int * 8)()
+    check(getattr(lib(), entry)(num_vars, C.byref(t), C.byref(ps), widths, tiles), entry)
+    return t.value, [widths[i] for i in range(ps.value)], [tiles[i] for i in range(ps.value)]
+
+
+def mle_eq_plan(num_vars):
+    """(tile_log, [variables of each launch], [log2 of the tiles one wave takes in it]) of DenseMultilinearExtension.eq:
+    launch p writes the table of the top widths[0] + .. + widths[p] variables"""
+    return _plan5("ark_hip_mle_eq_plan", num_vars)
+
+
+def mle_quotients_plan(num_vars):
+    """(tile_log, [variables bound by each launch], [log2 of the tiles one wave takes in it]) of `quotients`"""
+    return _plan5("ark_hip_mle_quotients_plan", num_vars)
+
+
+class DeviceSegment:
+    """`len` elements inside a DeviceVec, from element `offset` on: a view, no copy.  `ptr` is a device pointer that the
+    MSM's device entries accept as a scalar vector; the view keeps its owner alive."""
+
+    def __init__(self, owner, offset, length):
+        self.owner, self.offset, self.len, self.field = owner, int(offset), int(length), owner.field
+        self.ptr = C.c_void_p(owner.ptr.value + 32 * self.offset if self.len else 0)
+
+    def __len__(self):
+        return self.len
+
+    def to_host(self):
+        out = np.empty((self.len, 4), dtype=np.uint64)
+        if self.len:
+            check(lib().ark_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), self.ptr, out.nbytes), "ark_hip_memcpy_d2h")
+        return out
+
+
+def _device_pointer(x):
+    if hasattr(x, "data_ptr"):
+        return C.c_void_p(x.data_ptr())
+    if hasattr(x, "ptr"):
+        return x.ptr
+    return x if isinstance(x, C.c_void_p) else C.c_void_p(int(x))
 
 
 def _element(x):
@@ -94,6 +139,52 @@ class DenseMultilinearExtension:
         check(lib().ark_hip_mle_evaluate_device(self.field, self.evaluations.ptr, self.num_vars, pt.ctypes.data_as(C.c_void_p),
                                                 out.ctypes.data_as(C.c_void_p)), "ark_hip_mle_evaluate_device")
         return out
+
+    # ---- openings ------------------------------------------------------------------------
+    @classmethod
+    def eq(cls, field, point, scale=None):
+        """the table eq(point, b) = prod_i (b_i ? point_i : 1 - point_i), times `scale` (an element; None: one), built on
+        the device: <f, eq(r)> = f(r).  point: numpy uint64 [num_vars, 4] (Montgomery)"""
+        pt = _elements(point)
+        num_vars = pt.shape[0]
+        out = DeviceVec(field, 1 << num_vars, _zero=False)
+        k = None if scale is None else _element(scale)
+        check(lib().ark_hip_mle_eq_table_device(out.field, pt.ctypes.data_as(C.c_void_p), num_vars,
+                                                None if k is None else k.ctypes.data_as(C.c_void_p), out.ptr),
+              "ark_hip_mle_eq_table_device")
+        return cls(num_vars, out)
+
+    def quotients(self, point, wait=True):
+        """(f(point), [q_0, .., q_{num_vars-1}]) with f(x) - f(point) = sum_i (x_i - point_i) q_i(x_{i+1}, ..): q_i is a
+        DeviceSegment of 2^(num_vars-1-i) elements, all of them views into one DeviceVec.  wait=False returns None for the
+        value and leaves the call asynchronous."""
+        pt = _elements(point, self.num_vars)
+        n = 1 << self.num_vars
+        quot = DeviceVec(self.field, n - 1, _zero=False)
+        out = np.zeros(4, dtype=np.uint64) if wait else None
+        check(lib().ark_hip_mle_quotients_device(self.field, self.evaluations.ptr, self.num_vars, pt.ctypes.data_as(C.c_void_p),
+                                                 quot.ptr, out.ctypes.data_as(C.c_void_p) if wait else None),
+              "ark_hip_mle_quotients_device")
+        return out, [DeviceSegment(quot, n - (n >> i), n >> (i + 1)) for i in range(self.num_vars)]
+
+    def open(self, point, bases_per_level, curve):
+        """(f(point), [commitment to q_i for every i]): `quotients`, then one device MSM per level over the segment where it
+        lies.  bases_per_level[i]: a device array (pointer, tensor or DeviceVec-like) of 2^(num_vars-1-i) affine points of
+        `curve`, whose scalar field is the table's.  The points are Jacobian x|y|z as the MSM returns them.  No
+        verification and no hashing happens here."""
+        cid = cv.curve_id(curve)
+        if cv.field_id(cv.scalar_field(cid)) != self.field:
+            raise ValueError("the curve's scalar field is not the table's field")
+        if len(bases_per_level) != self.num_vars:
+            raise ValueError("one base array per variable expected")
+        value, segments = self.quotients(point)
+        points = []
+        for seg, bases in zip(segments, bases_per_level):
+            out = np.zeros(cv.projective_words(cid), dtype=np.uint64)
+            check(lib().ark_hip_msm_sw_device(cid, _device_pointer(bases), seg.ptr, len(seg), 1, out.ctypes.data_as(C.c_void_p)),
+                  "ark_hip_msm_sw_device")
+            points.append(out)
+        return value, points
 
     # ---- relabel ------------------------------------------------------------------------------------------------
     def _relabel(self, a, b, k, dst):

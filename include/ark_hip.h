@@ -524,6 +524,31 @@ int ark_hip_mle_fold_plan(unsigned num_vars, unsigned dim, int* tile_log, int* p
  * 0 past the last launch).  The fold kernel is compiled once per (variables bound, tiles per wave); more tiles per wave mean
  * fewer multiplies per element, and large tables get more of them.  Tests read from it which kernel variant a size runs. */
 int ark_hip_mle_fold_tiles(unsigned num_vars, unsigned dim, int* tiles_log);
+/* The table of eq(point, .): d_out[b] = scale * prod_{i < num_vars} (bit i of b ? point[i] :
+ * 1 - point[i]) for all b < 2^num_vars -- the weights with <f, eq(r)> = f(r), the first factor of a zero-check's sum.
+ * point: HOST, num_vars elements; scale: a HOST element, or NULL for one.  num_vars = 0 writes the one element `scale`.
+ * The products are taken in Montgomery form, so the output is Montgomery residues like every table here.  A write-only
+ * pass: ceil(num_vars / 9) launches (ark_hip_mle_eq_plan), each reading 1/512 of what it writes.  Asynchronous. */
+int ark_hip_mle_eq_table_device(int field, const uint64_t* point, unsigned num_vars, const uint64_t* scale, void* d_out);
+/* The quotients of a multilinear opening at `point`:
+ *   f(x) - f(point) = sum_i (x_i - point_i) q_i(x_{i+1}, .., x_{num_vars-1}),   q_i[b] = f_i[2b+1] - f_i[2b],
+ * f_0 = f and f_{i+1} = f_i with its first variable bound to point[i]: the differences fix_variables forms and drops.
+ * d_quot receives 2^num_vars - 1 elements: segment i (0 <= i < num_vars) lies at element offset
+ * 2^num_vars - 2^(num_vars-i) and holds the 2^(num_vars-1-i) elements of q_i, each a device vector an MSM with
+ * scalars_are_montgomery = 1 commits to.  out_value: a HOST element that receives f(point) -- bit for bit what
+ * ark_hip_mle_evaluate_device returns -- and the call waits for it; NULL makes the call asynchronous.  num_vars = 0 writes
+ * no quotient (d_quot may be NULL) and the value is d_evals[0].  The input is left untouched.  There is NO in-place form,
+ * as for fix_variables: d_quot must not overlap d_evals (ARK_HIP_ERR_ARG). */
+int ark_hip_mle_quotients_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* point, void* d_quot,
+                                 uint64_t* out_value);
+/* Host only, no device needed: the launches of the two calls above for a 2^num_vars table, as ark_hip_mle_fold_plan and
+ * ark_hip_mle_fold_tiles report the fold's.  *tile_log: the most variables one launch takes; *passes: the number of
+ * launches; widths[p]: the variables launch p takes; tiles_log[p]: log2 of the tiles of 2^tile_log elements one wave takes
+ * in it (8 entries each, 0 past the last launch).  The eq table's launch p writes the table of the TOP widths[0] + .. +
+ * widths[p] variables (num_vars = 0: one launch of no variables); the quotients' launch p binds the next widths[p]
+ * variables from the first on, its kernel compiled once per width.  Tests read from them which sizes reach which variant. */
+int ark_hip_mle_eq_plan(unsigned num_vars, int* tile_log, int* passes, int* widths, int* tiles_log);
+int ark_hip_mle_quotients_plan(unsigned num_vars, int* tile_log, int* passes, int* widths, int* tiles_log);
 
 /* ---- the sumcheck prover's round on device tables --------------------------------------------
  * The sum is a list of products of multilinear tables, each with a coefficient (ListOfProductsOfPolynomials of

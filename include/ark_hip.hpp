@@ -771,6 +771,54 @@ class DenseMultilinearExtension {
                                       out.limbs.data()), "ark_hip_mle_evaluate_device");
     return out;
   }
+  // ---- openings ----
+  // the table eq(point, b) = prod_i (b_i ? point_i : 1 - point_i), times *scale (nullptr: one), built on the device
+  static DenseMultilinearExtension eq(const std::vector<Fr>& point, const Fr* scale = nullptr) {
+    const size_t nv = point.size();
+    if (nv >= 64) throw Error(ARK_HIP_ERR_ARG, "num_vars < 64");
+    Vec out = Vec::uninit((size_t)1 << nv);
+    check(ark_hip_mle_eq_table_device(FIELD_ID, (const uint64_t*)point.data(), (unsigned)nv, scale ? scale->limbs.data() : nullptr,
+                                      out.device_ptr()), "ark_hip_mle_eq_table_device");
+    return DenseMultilinearExtension(nv, std::move(out));
+  }
+  // f(point) and the quotients of f(x) - f(point) = sum_i (x_i - point_i) q_i(x_{i+1}, ..): one device vector of
+  // 2^num_vars - 1 elements, q_i being the segment_len(i) elements from segment_offset(i) on -- views, no copies
+  struct Quotients {
+    Fr value;
+    size_t num_vars = 0;
+    Vec all;
+    size_t segment_offset(size_t i) const { return ((size_t)1 << num_vars) - ((size_t)1 << (num_vars - i)); }
+    size_t segment_len(size_t i) const { return (size_t)1 << (num_vars - 1 - i); }
+    const void* segment_ptr(size_t i) const { return (const char*)all.device_ptr() + 32 * segment_offset(i); }
+    std::vector<Fr> segment_to_vec(size_t i) const {
+      std::vector<Fr> out(segment_len(i));
+      check(ark_hip_memcpy_d2h(out.data(), segment_ptr(i), out.size() * 32), "ark_hip_memcpy_d2h");
+      return out;
+    }
+  };
+  Quotients quotients(const std::vector<Fr>& point) const {
+    if (point.size() != num_vars_) throw Error(ARK_HIP_ERR_ARG, "point.len() == self.num_vars");
+    Quotients q;
+    q.num_vars = num_vars_;
+    q.all = Vec::uninit(((size_t)1 << num_vars_) - 1);
+    check(ark_hip_mle_quotients_device(FIELD_ID, evals_.device_ptr(), (unsigned)num_vars_, (const uint64_t*)point.data(),
+                                       q.all.device_ptr(), q.value.limbs.data()), "ark_hip_mle_quotients_device");
+    return q;
+  }
+  // f(point) and a commitment to every q_i: one device MSM per level over the segment where it lies.  d_bases_per_level[i]:
+  // device array of 2^(num_vars-1-i) affine points of Curve, whose scalar field is this table's.  No verification, no hashing.
+  template <class Curve>
+  std::pair<Fr, std::vector<Projective<Curve::WORDS>>> open(const std::vector<Fr>& point,
+                                                            const std::vector<const void*>& d_bases_per_level) const {
+    static_assert(Curve::SCALAR_FIELD == FIELD_ID, "the curve's scalar field is the table's field");
+    if (d_bases_per_level.size() != num_vars_) throw Error(ARK_HIP_ERR_ARG, "one base array per variable");
+    Quotients q = quotients(point);
+    std::vector<Projective<Curve::WORDS>> pts(num_vars_);
+    for (size_t i = 0; i < num_vars_; i++)
+      check(ark_hip_msm_sw_device(Curve::ID, d_bases_per_level[i], q.segment_ptr(i), q.segment_len(i), 1,
+                                  reinterpret_cast<uint64_t*>(&pts[i])), "ark_hip_msm_sw_device");
+    return {q.value, std::move(pts)};
+  }
   // exchanges the k variables from position a with those from position b (dense.rs:76-92, :195-199)
   DenseMultilinearExtension relabel(size_t a, size_t b, size_t k) const {
     Vec out = Vec::uninit(evals_.len());

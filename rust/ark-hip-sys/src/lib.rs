@@ -207,6 +207,17 @@ extern "C" {
     pub fn ark_hip_mle_fold_plan(num_vars: c_uint, dim: c_uint, tile_log: *mut c_int, passes: *mut c_int, widths: *mut c_int) -> c_int;
     /// Host only: log2 of the tiles one wave takes in each launch of that plan (`tiles_log`: 8 entries).
     pub fn ark_hip_mle_fold_tiles(num_vars: c_uint, dim: c_uint, tiles_log: *mut c_int) -> c_int;
+    /// `d_out[b] = scale * prod_i (bit i of b ? point[i] : 1 - point[i])` for `b < 2^num_vars`; `scale`: a host element or
+    /// null for one.  Asynchronous.
+    pub fn ark_hip_mle_eq_table_device(field: c_int, point: *const u64, num_vars: c_uint, scale: *const u64, d_out: *mut c_void) -> c_int;
+    /// The quotients of a multilinear opening at `point`: `d_quot` receives `2^num_vars - 1` elements, `q_i` at element
+    /// offset `2^num_vars - 2^(num_vars-i)`; `out_value` (host, may be null: asynchronous) receives `f(point)`.
+    pub fn ark_hip_mle_quotients_device(field: c_int, d_evals: *const c_void, num_vars: c_uint, point: *const u64, d_quot: *mut c_void,
+                                        out_value: *mut u64) -> c_int;
+    /// Host only: the launches of the two entries above (`widths`, `tiles_log`: 8 entries each).
+    pub fn ark_hip_mle_eq_plan(num_vars: c_uint, tile_log: *mut c_int, passes: *mut c_int, widths: *mut c_int, tiles_log: *mut c_int) -> c_int;
+    pub fn ark_hip_mle_quotients_plan(num_vars: c_uint, tile_log: *mut c_int, passes: *mut c_int, widths: *mut c_int,
+                                      tiles_log: *mut c_int) -> c_int;
     /// One sumcheck round over `ntables` device tables of `2^num_vars` elements: `out_evals[t]`, `t = 0 ..= D`, of
     /// `sum_b sum_j c_j prod_k (T_k[2b] + t (T_k[2b+1] - T_k[2b]))`; with `r_prev` (host element) the first variable is bound
     /// to it first, into `d_out_tables`, in the same launch.  `term_tables`: the factors' table indices, term after term.

@@ -16,7 +16,8 @@
 //! * **multilinear provers**: [`mle::DenseMultilinearExtension`] keeps a table of 2^nu evaluations in HBM -- the commitment
 //!   is an MSM on it, `fix_variables` / `evaluate` / `relabel` bind and move its variables without a PCIe crossing, and
 //!   [`sumcheck::ListOfProducts`] runs the sumcheck prover's rounds over such tables: the round sums of a list of products,
-//!   with the previous challenge bound in the same pass.
+//!   with the previous challenge bound in the same pass.  `DenseMultilinearExtension::eq` builds the table of `eq(r, .)` on the
+//!   device, `quotients` / `open` the quotients of a multilinear opening and their commitments.
 //!
 //! Beyond the reference's surface: [`msm::PreparedBases`] (a fixed SRS resident on the GPU with its per-window
 //! multiples), [`msm::MsmJob`] (asynchronous MSMs), [`msm::msm_multi`] (one MSM over all GPUs of the node).
@@ -33,7 +34,7 @@ pub use ark_hip_sys as sys;
 pub use ark_hip_sys::{BLS12_377_G1, BLS12_377_G2, BLS12_381_G1, BLS12_381_G2, BN254_G1};
 pub use device::{DeviceError, DeviceEvaluations, DeviceVec};
 pub use points::DevicePoints;
-pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension};
+pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension, Quotients};
 pub use sumcheck::{ListOfProducts, SumcheckProof};
 pub use msm::{check_bases, compress_bases, decompress_bases, serve_group_coefficients, sw_msm, sw_msm_bigint, BaseCheck, HipServed};
 #[cfg(feature = "ec-hook")]

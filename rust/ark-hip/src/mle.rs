@@ -3,6 +3,8 @@
 //! committing to it is an MSM with Montgomery scalars on `evaluations().as_device_ptr()`, and `fix_variables` / `evaluate`
 //! bind its variables where the table lies.  Index bit 0 is the first variable, as in the reference.
 use crate::device::{DeviceError, DeviceVec};
+use crate::msm::HipServed;
+use ark_ec::short_weierstrass::{Affine, Projective};
 use ark_ff::FftField;
 use ark_hip_sys as sys;
 use ark_std::vec::Vec;
@@ -14,6 +16,40 @@ pub struct DeviceMultilinearExtension<F: FftField> {
 }
 /// the reference's name for it
 pub type DenseMultilinearExtension<F> = DeviceMultilinearExtension<F>;
+
+/// What [`DeviceMultilinearExtension::quotients`] returns: `f(point)` and the quotients `q_i` of
+/// `f(x) - f(point) = sum_i (x_i - point_i) q_i(x_{i+1}, ..)`, all in one device vector; `q_i` is the view of
+/// `segment_len(i)` elements from `segment_offset(i)` on.
+pub struct Quotients<F: FftField> {
+    pub value: F,
+    num_vars: usize,
+    all: DeviceVec<F>,
+}
+impl<F: FftField> Quotients<F> {
+    pub fn num_vars(&self) -> usize {
+        self.num_vars
+    }
+    pub fn segment_offset(&self, i: usize) -> usize {
+        (1usize << self.num_vars) - (1usize << (self.num_vars - i))
+    }
+    pub fn segment_len(&self, i: usize) -> usize {
+        1usize << (self.num_vars - 1 - i)
+    }
+    /// device pointer of `q_i`: a scalar vector for the MSM's device entries (Montgomery form)
+    pub fn segment_ptr(&self, i: usize) -> *const c_void {
+        unsafe { (self.all.as_device_ptr() as *const u8).add(32 * self.segment_offset(i)) as *const c_void }
+    }
+    pub fn segment_to_vec(&self, i: usize) -> Result<Vec<F>, DeviceError> {
+        let n = self.segment_len(i);
+        let mut out: Vec<F> = Vec::with_capacity(n);
+        rc(unsafe { sys::ark_hip_memcpy_d2h(out.as_mut_ptr() as *mut c_void, self.segment_ptr(i), n * 32) })?;
+        unsafe { out.set_len(n) };
+        Ok(out)
+    }
+    pub fn all(&self) -> &DeviceVec<F> {
+        &self.all
+    }
+}
 
 fn rc(code: core::ffi::c_int) -> Result<(), DeviceError> {
     if code == 0 { Ok(()) } else { Err(DeviceError::Library(code)) }
@@ -86,6 +122,57 @@ impl<F: FftField> DeviceMultilinearExtension<F> {
                                              out.as_mut_ptr())
         })?;
         Ok(sys::from_limbs::<F>(&out))
+    }
+    /// The table `eq(point, b) = prod_i (b_i ? point_i : 1 - point_i)`, times `scale` (`None`: one), built on the device:
+    /// `<f, eq(r)> = f(r)`.
+    pub fn eq(point: &[F], scale: Option<&F>) -> Result<Self, DeviceError> {
+        let num_vars = point.len();
+        if num_vars >= 64 {
+            return Err(DeviceError::Mismatch);
+        }
+        let mut out = DeviceVec::<F>::alloc(1usize << num_vars)?;
+        let pt = flat(point);
+        let k = scale.map(|x| sys::limbs(x));
+        rc(unsafe {
+            sys::ark_hip_mle_eq_table_device(out.field(), pt.as_ptr(), num_vars as c_uint, k.as_ref().map_or(core::ptr::null(), |x| x.as_ptr()),
+                                             out.as_device_mut_ptr())
+        })?;
+        Ok(Self { num_vars, evals: out })
+    }
+    /// `f(point)` and the quotients of the opening at `point`; waits for the value.
+    pub fn quotients(&self, point: &[F]) -> Result<Quotients<F>, DeviceError> {
+        self.evals.here()?;
+        if point.len() != self.num_vars {
+            return Err(DeviceError::Mismatch);
+        }
+        let mut all = DeviceVec::<F>::alloc((1usize << self.num_vars) - 1)?;
+        let pt = flat(point);
+        let mut out = [0u64; 4];
+        rc(unsafe {
+            sys::ark_hip_mle_quotients_device(self.evals.field(), self.evals.as_device_ptr(), self.num_vars as c_uint, pt.as_ptr(),
+                                              all.as_device_mut_ptr(), out.as_mut_ptr())
+        })?;
+        Ok(Quotients { value: sys::from_limbs::<F>(&out), num_vars: self.num_vars, all })
+    }
+    /// `f(point)` and a commitment to every `q_i`: [`Self::quotients`], then one device MSM per level over the segment where
+    /// it lies.  No verification and no hashing happens here.
+    ///
+    /// # Safety
+    /// `d_bases_per_level[i]` is a device array of `2^(num_vars-1-i)` `Affine<P>` on the current device.
+    pub unsafe fn open<P: HipServed<ScalarField = F>>(&self, point: &[F], d_bases_per_level: &[*const Affine<P>])
+                                                      -> Result<(F, Vec<Projective<P>>), DeviceError> {
+        if d_bases_per_level.len() != self.num_vars {
+            return Err(DeviceError::Mismatch);
+        }
+        let q = self.quotients(point)?;
+        let mut points = Vec::with_capacity(self.num_vars);
+        for (i, bases) in d_bases_per_level.iter().enumerate() {
+            let mut out = core::mem::MaybeUninit::<Projective<P>>::uninit();
+            rc(sys::ark_hip_msm_sw_device(P::CURVE, *bases as *const c_void, q.segment_ptr(i), q.segment_len(i), 1,
+                                          out.as_mut_ptr() as *mut u64))?;
+            points.push(out.assume_init());
+        }
+        Ok((q.value, points))
     }
     /// `relabel` (dense.rs:195-199): a new polynomial with the `k` variables from `a` and from `b` exchanged.
     pub fn relabel(&self, a: usize, b: usize, k: usize) -> Result<Self, DeviceError> {
