@@ -21,5 +21,7 @@ from .msm import (BatchMulPreprocessing, batch_mul, ChunkedPippenger, HashMapPip
 from .domain import Radix2EvaluationDomain  # noqa: F401
 from .poly import DeviceVec, poly_mul, poly_mul_host  # noqa: F401
 from .points import DevicePoints  # noqa: F401
-from .mle import DenseMultilinearExtension, DeviceSegment, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_quotients_plan  # noqa: F401
+from .mle import (DenseMultilinearExtension, DeviceSegment, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_product_tree_launches,  # noqa: F401
+                  mle_product_tree_plan, mle_quotients_plan)
 from .sumcheck import ListOfProducts, SumcheckProof, sumcheck_plan  # noqa: F401
+from .grand_product import GrandProduct, GrandProductProof  # noqa: F401

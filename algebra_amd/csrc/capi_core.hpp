@@ -562,6 +562,16 @@ inline int mle_quot_dispatch(int field, const void* src, int log_n, int w, const
   ARK_FIELD_SWITCH(field, X);
 #undef X
 }
+inline int prod_tree_dispatch(int field, const void* src, int log_n, int w, void* dst, hipStream_t st) {
+#define X(NAME) prod_tree_##NAME(src, log_n, w, dst, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int fr_lincomb_dispatch(int field, const FrLincomb& lc, void* out, size_t n, hipStream_t st) {
+#define X(NAME) fr_lincomb_##NAME(lc, out, n, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
 inline int sumcheck_round_dispatch(int field, const SumcheckRound& rd, hipStream_t st) {
 #define X(NAME) sumcheck_round_##NAME(rd, st)
   ARK_FIELD_SWITCH(field, X);

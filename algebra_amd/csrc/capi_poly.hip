@@ -1,12 +1,14 @@
 // C ABI of libark_hip.so: polynomial operations on device-resident vectors -- evaluation at a point, division by x - z and
 // by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products -- and dense
 // multilinear extensions: fix_variables, evaluate, relabel, a + k x, the eq table and an opening's quotients -- and the
-// sumcheck prover's round over such tables (see include/ark_hip.h; kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh).
+// sumcheck prover's round over such tables, the product tree of a grand product and its fingerprints (see include/ark_hip.h;
+// kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh, grand_product.cuh).
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "polyops.cuh"
 #include "mle.cuh"
 #include "mle_open.cuh"
+#include "grand_product.cuh"
 #include "sumcheck.cuh"
 using namespace arkhip;
 using namespace arkhip::capi;
@@ -140,6 +142,7 @@ inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 
 static_assert(SUMCHECK_MAX_TABLES == ARK_HIP_SUMCHECK_MAX_TABLES && SUMCHECK_MAX_TERMS == ARK_HIP_SUMCHECK_MAX_TERMS &&
                   SUMCHECK_MAX_DEGREE == ARK_HIP_SUMCHECK_MAX_DEGREE, "the header publishes the kernels' limits");
+static_assert(PROD_TREE_MAX_W == ARK_HIP_PRODUCT_TREE_LEVELS, "the header publishes the levels of a full launch");
 
 }  // namespace
 
@@ -414,6 +417,62 @@ int ark_hip_fr_axpy_device(int field, const void* d_a, const uint64_t* k, const 
   ARK_SCOPE(sc);
   Context* c = sc.c;
   if (int rc = fr_axpy_dispatch(field, d_a, k, d_x, d_r, n, c->stream)) return rc;
+  return mark_producer(c);
+}
+
+int ark_hip_mle_product_tree_plan(unsigned num_vars, int* passes, int* widths, int* group_log) {
+  if (!passes || !widths || !group_log || num_vars >= 64) return ARK_HIP_ERR_ARG;
+  for (int p = 0; p < MLE_MAX_PASSES; p++) widths[p] = group_log[p] = 0;
+  *passes = prod_tree_plan((int)num_vars, widths);   // one chunk of 64 outputs per wave in every launch: group_log stays 0
+  return 0;
+}
+
+int ark_hip_mle_product_tree_device(int field, const void* d_evals, unsigned num_vars, void* d_tree, uint64_t* out_product) {
+  if (!field_served(field) || !d_evals || num_vars >= 64 || (num_vars && !d_tree)) return ARK_HIP_ERR_ARG;
+  if (num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
+  const size_t n = (size_t)1 << num_vars;
+  if (num_vars && ranges_overlap(d_evals, n * 32, d_tree, (n - 1) * 32)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  const void* product = d_evals;   // a constant: no tree, the product is its one table entry
+  if (num_vars) {
+    int widths[PROD_TREE_MAX_LAUNCHES];
+    const int launches = prod_tree_launches((int)num_vars, widths);
+    const void* cur = d_evals;
+    int m = (int)num_vars;
+    for (int p = 0; p < launches; p++) {
+      // L_k starts at element 2^num_vars - 2^(k+1): the launch reads L_m and writes from L_(m-1) on
+      char* dst = (char*)d_tree + (n - ((size_t)1 << m)) * 32;
+      if (int rc = prod_tree_dispatch(field, cur, m, widths[p], dst, c->stream)) return rc;
+      m -= widths[p];
+      cur = (char*)d_tree + (n - ((size_t)2 << m)) * 32;
+    }
+    product = cur;
+  }
+  if (!out_product) return num_vars ? mark_producer(c) : 0;
+  ARK_HIP_TRY(hipMemcpyAsync(out_product, product, 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int ark_hip_fr_lincomb_device(int field, const void* const* d_tables, unsigned ntables, const uint64_t* coeffs, const uint64_t* c0,
+                              void* d_out, size_t n) {
+  if (!field_served(field) || !d_tables || !coeffs || !d_out || ntables == 0 || ntables > (unsigned)LINCOMB_MAX_TABLES) return ARK_HIP_ERR_ARG;
+  if (n > ((size_t)-1) / 32) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
+  FrLincomb lc = {};
+  lc.ntables = ntables;
+  lc.has_c0 = c0 ? 1 : 0;
+  for (unsigned k = 0; k < ntables; k++) {
+    if (!d_tables[k]) return ARK_HIP_ERR_ARG;
+    if (d_tables[k] != d_out && ranges_overlap(d_tables[k], n * 32, d_out, n * 32)) return ARK_HIP_ERR_ARG;
+    lc.tab[k] = (const char*)d_tables[k];
+    for (int q = 0; q < 4; q++) { lc.coeff[k].l[2 * q] = (u32)coeffs[4 * k + q]; lc.coeff[k].l[2 * q + 1] = (u32)(coeffs[4 * k + q] >> 32); }
+  }
+  if (c0)
+    for (int q = 0; q < 4; q++) { lc.c0.l[2 * q] = (u32)c0[q]; lc.c0.l[2 * q + 1] = (u32)(c0[q] >> 32); }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (int rc = fr_lincomb_dispatch(field, lc, d_out, n, c->stream)) return rc;
   return mark_producer(c);
 }
 

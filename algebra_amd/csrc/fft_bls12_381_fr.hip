@@ -4,6 +4,7 @@
 #include "polyops.cuh"
 #include "mle.cuh"
 #include "mle_open.cuh"
+#include "grand_product.cuh"
 #include "sumcheck.cuh"
 #include "internal.hpp"
 namespace arkhip {
@@ -57,6 +58,10 @@ int mle_eq_BLS12_381_FR(const void* hi, const FrConst& top, int unit, const MleP
 int mle_quot_BLS12_381_FR(const void* src, int log_n, int w, const MlePoint& pt, void* quot, void* dst, hipStream_t s) {
   return mle_quot_launch<Fp<BLS12_381_FR>>(src, log_n, w, pt, quot, dst, s);
 }
+int prod_tree_BLS12_381_FR(const void* src, int log_n, int w, void* dst, hipStream_t s) {
+  return prod_tree_launch<Fp<BLS12_381_FR>>(src, log_n, w, dst, s);
+}
+int fr_lincomb_BLS12_381_FR(const FrLincomb& lc, void* out, size_t n, hipStream_t s) { return fr_lincomb_launch<Fp<BLS12_381_FR>>(lc, out, n, s); }
 int sumcheck_round_BLS12_381_FR(const SumcheckRound& rd, hipStream_t s) { return sumcheck_round_launch<Fp<BLS12_381_FR>>(rd, s); }
 int fft_axis_BLS12_381_FR(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4, hipStream_t s) {
   return fft_axis_run<BLS12_381_FR>(ws, d_src, d_dst, G, cols, root4, s);

@@ -18,6 +18,7 @@ struct PolyPowers;
 struct MlePoint;
 struct FrConst;
 struct SumcheckRound;
+struct FrLincomb;
 
 // one function per curve / field, defined in msm_<curve>.hip / fft_<field>.hip
 #define ARK_DECL_CURVE(NAME)                                                                                    \
@@ -80,6 +81,8 @@ ARK_DECL_CURVE(BLS12_381_G2)
   int fr_axpy_##NAME(const void* d_a, const uint64_t* k4, const void* d_x, void* d_r, size_t n, hipStream_t s);     \
   int mle_eq_##NAME(const void* d_hi, const FrConst& top, int unit, const MlePoint& pt, int log_n, void* d_dst, hipStream_t s); \
   int mle_quot_##NAME(const void* d_src, int log_n, int w, const MlePoint& pt, void* d_quot, void* d_dst, hipStream_t s); \
+  int prod_tree_##NAME(const void* d_src, int log_n, int w, void* d_dst, hipStream_t s);                            \
+  int fr_lincomb_##NAME(const FrLincomb& lc, void* d_out, size_t n, hipStream_t s);                                 \
   int sumcheck_round_##NAME(const SumcheckRound& rd, hipStream_t s);                                                \
   int fft_roots_##NAME(FftWorkspace& ws, int k, const uint64_t* root4, hipStream_t s, const uint32_t** out);        \
   int fft_scalars_##NAME(FftWorkspace& ws, const uint64_t* base4, const uint64_t* mul4, size_t count, void* d_out,  \

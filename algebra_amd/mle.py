@@ -45,6 +45,26 @@ def mle_quotients_plan(num_vars):
     return _plan5("ark_hip_mle_quotients_plan", num_vars)
 
 
+PRODUCT_TREE_LEVELS = 3     # ARK_HIP_PRODUCT_TREE_LEVELS of include/ark_hip.h: the most levels one launch forms
+
+
+def mle_product_tree_plan(num_vars):
+    """([levels of each run of launches], [log2 of the chunks of 64 outputs one wave takes in them: always 0]) of
+    `product_tree`, as ark_hip_mle_product_tree_plan reports them: the full launches as one run, then the remainder launch"""
+    ps = C.c_int()
+    widths, groups = (C.c_int * 8)(), (C.c_int * 8)()
+    check(lib().ark_hip_mle_product_tree_plan(num_vars, C.byref(ps), widths, groups), "ark_hip_mle_product_tree_plan")
+    return [widths[i] for i in range(ps.value)], [groups[i] for i in range(ps.value)]
+
+
+def mle_product_tree_launches(num_vars):
+    """[(levels, group_log)] launch by launch: the runs of mle_product_tree_plan spelled out"""
+    out = []
+    for w, g in zip(*mle_product_tree_plan(num_vars)):
+        out += [(PRODUCT_TREE_LEVELS, g)] * (w // PRODUCT_TREE_LEVELS) if w >= PRODUCT_TREE_LEVELS else [(w, g)]
+    return out
+
+
 class DeviceSegment:
     """`len` elements inside a DeviceVec, from element `offset` on: a view, no copy.  `ptr` is a device pointer that the
     MSM's device entries accept as a scalar vector; the view keeps its owner alive."""
@@ -61,6 +81,9 @@ class DeviceSegment:
         if self.len:
             check(lib().ark_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), self.ptr, out.nbytes), "ark_hip_memcpy_d2h")
         return out
+
+    def free(self):
+        """a view owns nothing: the memory goes with its owner (so a DenseMultilinearExtension over a view frees nothing)"""
 
 
 def _device_pointer(x):
@@ -185,6 +208,42 @@ class DenseMultilinearExtension:
                   "ark_hip_msm_sw_device")
             points.append(out)
         return value, points
+
+    # ---- grand products ------------------------------------------------------------------
+    def product_tree(self, wait=True):
+        """(product, [level_1, .., level_nu]): the binary product tree pairing over the LAST variable.  level_j has
+        2^(num_vars-j) elements, level_j[i] = level_(j-1)[i] * level_(j-1)[i + 2^(num_vars-j)] with level_0 the table; all
+        are DeviceSegments of one DeviceVec of 2^num_vars - 1 elements whose last is the product.  wait=False returns None
+        for the product and leaves the call asynchronous.  The table is not written."""
+        n = 1 << self.num_vars
+        tree = DeviceVec(self.field, n - 1, _zero=False)
+        out = np.zeros(4, dtype=np.uint64) if wait else None
+        check(lib().ark_hip_mle_product_tree_device(self.field, self.evaluations.ptr, self.num_vars, tree.ptr if n > 1 else None,
+                                                    out.ctypes.data_as(C.c_void_p) if wait else None),
+              "ark_hip_mle_product_tree_device")
+        return out, [DeviceSegment(tree, n - (n >> (j - 1)), n >> j) for j in range(1, self.num_vars + 1)]
+
+    @classmethod
+    def linear_combination(cls, tables, coeffs, c0=None):
+        """the new extension c0 + sum_k coeffs[k] tables[k], entry by entry in one pass: 1 to 8 extensions of one field and
+        size; coeffs: numpy uint64 [len(tables), 4] (Montgomery); c0: an element or None for zero"""
+        tables = list(tables)
+        if not 1 <= len(tables) <= 8:
+            raise ValueError("1 to 8 tables")
+        first = tables[0]
+        for t in tables:
+            if t.field != first.field:
+                raise ValueError("polynomials over different fields")
+            if t.num_vars != first.num_vars:
+                raise ValueError("num_vars differ: %d and %d" % (t.num_vars, first.num_vars))
+        k = _elements(coeffs, len(tables))
+        g = None if c0 is None else _element(c0)
+        out = DeviceVec(first.field, len(first), _zero=False)
+        ptrs = (C.c_void_p * len(tables))(*[t.evaluations.ptr.value for t in tables])
+        check(lib().ark_hip_fr_lincomb_device(first.field, ptrs, len(tables), k.ctypes.data_as(C.c_void_p),
+                                              None if g is None else g.ctypes.data_as(C.c_void_p), out.ptr, len(out)),
+              "ark_hip_fr_lincomb_device")
+        return cls(first.num_vars, out)
 
     # ---- relabel ------------------------------------------------------------------------------------------------
     def _relabel(self, a, b, k, dst):

@@ -550,6 +550,35 @@ int ark_hip_mle_quotients_device(int field, const void* d_evals, unsigned num_va
 int ark_hip_mle_eq_plan(unsigned num_vars, int* tile_log, int* passes, int* widths, int* tiles_log);
 int ark_hip_mle_quotients_plan(unsigned num_vars, int* tile_log, int* passes, int* widths, int* tiles_log);
 
+/* ---- grand products on device tables -----------------------------------------------------------
+ * The binary product tree over a table, pairing over the LAST variable: L_nu = the table, L_k[i] = L_{k+1}[i] *
+ * L_{k+1}[i + 2^k] for i < 2^k, L_0 = [the product of all entries].  The two factors of a level are the two contiguous
+ * halves of the level above, so L_k(r) = sum_x eq(r, x) L_{k+1}(x, 0) L_{k+1}(x, 1) is a sumcheck over two views
+ * (ark_hip_sumcheck_round_device), and the layered proof of the product ends in one evaluation of the table.
+ * d_tree: 2^num_vars - 1 elements in the layout of ark_hip_mle_quotients_device: level j (1 <= j <= num_vars) is
+ * L_{num_vars-j}, 2^(num_vars-j) elements at element offset 2^num_vars - 2^(num_vars-j+1); the product is the last element.
+ * out_product: a HOST element, the call waits for it; NULL makes the call asynchronous.  num_vars = 0: no tree (d_tree may
+ * be NULL), the product is d_evals[0].  The input is left untouched; d_tree must not overlap d_evals (ARK_HIP_ERR_ARG).
+ * ARK_HIP_ERR_ARG comes before any device is touched for an unknown field, a null pointer, num_vars >= 64 or a table
+ * whose bytes a size_t cannot count, as for ark_hip_mle_quotients_device.  No scratch: later launches read the levels the
+ * earlier ones wrote in d_tree. */
+#define ARK_HIP_PRODUCT_TREE_LEVELS 3
+int ark_hip_mle_product_tree_device(int field, const void* d_evals, unsigned num_vars, void* d_tree, uint64_t* out_product);
+/* Host only, no device needed: the launches of that call.  A launch forms up to ARK_HIP_PRODUCT_TREE_LEVELS consecutive
+ * levels from the level above them; a table of 58 variables takes 20 launches, so entry p (8 entries each, 0 past the last)
+ * is a RUN of consecutive launches of one kernel instantiation: first the full launches, widths[0] levels in all,
+ * ARK_HIP_PRODUCT_TREE_LEVELS per launch; then the one remainder launch of 1 or 2 levels.  At most two entries; the widths
+ * sum to num_vars.  group_log[p] = log2 of the chunks of 64 output indices one wave takes: always 0 (several chunks per
+ * wave were measured no faster and are not built).  Levels of fewer than 64 elements are left to the same kernel in launches
+ * of one partly filled wave; there is no separate tail kernel. */
+int ark_hip_mle_product_tree_plan(unsigned num_vars, int* passes, int* widths, int* group_log);
+/* d_out[i] = c0 + sum_k coeffs[k] * d_tables[k][i] for i < n, in one pass: the fingerprints gamma + sum_k c_k T_k[i] that
+ * are the leaves of a grand product.  d_tables: HOST array of ntables device pointers; coeffs: HOST, ntables elements; c0:
+ * a HOST element or NULL for zero; 1 <= ntables <= 8.  d_out may be the same pointer as one of the tables; any other
+ * overlap of d_out with a table is ARK_HIP_ERR_ARG.  Asynchronous. */
+int ark_hip_fr_lincomb_device(int field, const void* const* d_tables, unsigned ntables, const uint64_t* coeffs,
+                              const uint64_t* c0, void* d_out, size_t n);
+
 /* ---- the sumcheck prover's round on device tables --------------------------------------------
  * The sum is a list of products of multilinear tables, each with a coefficient (ListOfProductsOfPolynomials of
  * ark-linear-sumcheck): sum_j c_j prod_{k in term j} f_k.  Tables follow the conventions above: 2^num_vars Montgomery

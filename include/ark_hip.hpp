@@ -571,11 +571,24 @@ class DeviceVec {
     return v;
   }
   static DeviceVec from_vec(const std::vector<Fr>& x) { return from_slice(x.data(), x.size()); }
-  DeviceVec(DeviceVec&& o) noexcept : p_(o.p_), len_(o.len_), cap_(o.cap_), dev_(o.dev_) { o.p_ = nullptr; o.len_ = o.cap_ = 0; }
+  DeviceVec(DeviceVec&& o) noexcept : p_(o.p_), len_(o.len_), cap_(o.cap_), dev_(o.dev_), view_(o.view_) { o.p_ = nullptr; o.len_ = o.cap_ = 0; }
   DeviceVec& operator=(DeviceVec&& o) noexcept {
-    if (this != &o) { release(); p_ = o.p_; len_ = o.len_; cap_ = o.cap_; dev_ = o.dev_; o.p_ = nullptr; o.len_ = o.cap_ = 0; }
+    if (this != &o) { release(); p_ = o.p_; len_ = o.len_; cap_ = o.cap_; dev_ = o.dev_; view_ = o.view_; o.p_ = nullptr; o.len_ = o.cap_ = 0; }
     return *this;
   }
+  // len elements from element offset of `owner` on: a VIEW, no copy -- it frees nothing and must not outlive or outgrow its
+  // owner (the halves of a product tree's level as the evaluations of a DenseMultilinearExtension)
+  static DeviceVec view(const DeviceVec& owner, size_t offset, size_t len) {
+    owner.here();
+    if (offset > owner.len_ || len > owner.len_ - offset) throw Error(ARK_HIP_ERR_ARG, "the view leaves its owner");
+    DeviceVec v;
+    v.p_ = len ? (char*)owner.p_ + 32 * offset : nullptr;
+    v.len_ = v.cap_ = len;
+    v.dev_ = owner.dev_;
+    v.view_ = true;
+    return v;
+  }
+  bool is_view() const { return view_; }
   DeviceVec(const DeviceVec&) = delete;
   DeviceVec& operator=(const DeviceVec&) = delete;
   ~DeviceVec() { release(); }
@@ -667,6 +680,7 @@ class DeviceVec {
   void* p_ = nullptr;
   size_t len_ = 0, cap_ = 0;
   int dev_ = -1;
+  bool view_ = false;
   void alloc(size_t len) {
     dev_ = ark_hip_get_device();
     len_ = cap_ = len;
@@ -686,6 +700,7 @@ class DeviceVec {
   }
   void release() {
     if (!p_) return;
+    if (view_) { p_ = nullptr; return; }   // a view owns nothing
     const int cur = ark_hip_get_device();
     if (dev_ >= 0 && cur != dev_) (void)ark_hip_set_device(dev_);   // freed on the device that owns it
     (void)ark_hip_free(p_);
@@ -818,6 +833,50 @@ class DenseMultilinearExtension {
       check(ark_hip_msm_sw_device(Curve::ID, d_bases_per_level[i], q.segment_ptr(i), q.segment_len(i), 1,
                                   reinterpret_cast<uint64_t*>(&pts[i])), "ark_hip_msm_sw_device");
     return {q.value, std::move(pts)};
+  }
+  // ---- grand products ----
+  // The binary product tree pairing over the LAST variable: one device vector of 2^num_vars - 1 elements, level j
+  // (1 <= j <= num_vars) being the level_len(j) = 2^(num_vars-j) elements from level_offset(j) on, level j's element i the
+  // product of elements i and i + level_len(j) of level j - 1 (level 0: the table); the last element is the product.
+  struct ProductTree {
+    Fr product;
+    size_t num_vars = 0;
+    Vec all;
+    size_t level_offset(size_t j) const { return ((size_t)1 << num_vars) - ((size_t)2 << (num_vars - j)); }
+    size_t level_len(size_t j) const { return (size_t)1 << (num_vars - j); }
+    Vec level(size_t j) const { return Vec::view(all, level_offset(j), level_len(j)); }
+    std::vector<Fr> level_to_vec(size_t j) const { return level(j).to_vec(); }
+  };
+  ProductTree product_tree() const {
+    ProductTree t;
+    t.num_vars = num_vars_;
+    t.all = Vec::uninit(((size_t)1 << num_vars_) - 1);
+    check(ark_hip_mle_product_tree_device(FIELD_ID, evals_.device_ptr(), (unsigned)num_vars_, t.all.device_ptr(), t.product.limbs.data()),
+          "ark_hip_mle_product_tree_device");
+    return t;
+  }
+  // the launches of product_tree as ark_hip_mle_product_tree_plan reports them: (levels, log2 chunks per wave) per run
+  static std::vector<std::pair<int, int>> product_tree_plan(size_t num_vars) {
+    int passes = 0, widths[8], groups[8];
+    check(ark_hip_mle_product_tree_plan((unsigned)num_vars, &passes, widths, groups), "ark_hip_mle_product_tree_plan");
+    std::vector<std::pair<int, int>> out;
+    for (int p = 0; p < passes; p++) out.push_back({widths[p], groups[p]});
+    return out;
+  }
+  // c0 + sum_k coeffs[k] tables[k], entry by entry in one pass (c0 == nullptr: zero): the fingerprints that are the leaves
+  // of a grand product; 1 to 8 tables of one size
+  static DenseMultilinearExtension linear_combination(const std::vector<const DenseMultilinearExtension*>& tables,
+                                                      const std::vector<Fr>& coeffs, const Fr* c0 = nullptr) {
+    if (tables.empty() || tables.size() > 8 || coeffs.size() != tables.size()) throw Error(ARK_HIP_ERR_ARG, "1 to 8 tables, one coefficient each");
+    std::vector<const void*> ptrs;
+    for (auto* t : tables) {
+      if (t->num_vars_ != tables[0]->num_vars_) throw Error(ARK_HIP_ERR_ARG, "num_vars differ");
+      ptrs.push_back(t->evals_.device_ptr());
+    }
+    Vec out = Vec::uninit(tables[0]->evals_.len());
+    check(ark_hip_fr_lincomb_device(FIELD_ID, ptrs.data(), (unsigned)ptrs.size(), (const uint64_t*)coeffs.data(),
+                                    c0 ? c0->limbs.data() : nullptr, out.device_ptr(), out.len()), "ark_hip_fr_lincomb_device");
+    return DenseMultilinearExtension(tables[0]->num_vars_, std::move(out));
   }
   // exchanges the k variables from position a with those from position b (dense.rs:76-92, :195-199)
   DenseMultilinearExtension relabel(size_t a, size_t b, size_t k) const {
@@ -996,6 +1055,62 @@ class ListOfProducts {
           "ark_hip_sumcheck_round_device");
     return evals;
   }
+};
+
+// The layered proof of a grand product P = prod_b f[b] (Thaler's GKR grand product): the product tree,
+// then per layer k = 1 .. nu - 1 one sumcheck of eq(r_k, x) L_{k+1}(x, 0) L_{k+1}(x, 1) over two views of the level, which
+// leaves the claim left(rho) + tau (right(rho) - left(rho)) about L_{k+1}(rho, tau); the last claim is f(point), which
+// evaluate / open answer.  challenge(layer, round, values) gets round = -1 and the pair (left, right) for a layer's tau.
+// Nothing is hashed and nothing verified here; the table and the tree are not written.
+template <int FIELD_ID>
+struct GrandProductProof {
+  Fr product;
+  std::vector<std::optional<SumcheckProof<FIELD_ID>>> sumchecks;   // per layer; none for layer 0
+  std::vector<std::pair<Fr, Fr>> pairs;                            // per layer: L_1's two elements, then (left(rho), right(rho))
+  std::vector<Fr> point;                                           // r_nu: where the verifier's last claim about f lies
+};
+template <int FIELD_ID>
+class GrandProduct {
+ public:
+  using Mle = DenseMultilinearExtension<FIELD_ID>;
+  using Vec = DeviceVec<FIELD_ID>;
+  explicit GrandProduct(const Mle& f) : f_(f) {}
+  template <class Challenge>
+  GrandProductProof<FIELD_ID> prove(Challenge&& challenge) const {
+    const size_t nu = f_.num_vars();
+    GrandProductProof<FIELD_ID> out;
+    typename Mle::ProductTree tree = f_.product_tree();
+    out.product = tree.product;
+    if (nu == 0) return out;
+    const Fr one = Mle::eq({}).to_evaluations()[0];   // the eq table of no variables is its scale, one
+    {
+      const std::vector<Fr> l1 = nu == 1 ? f_.to_evaluations() : tree.level_to_vec(nu - 1);   // L_1
+      out.sumchecks.push_back(std::nullopt);
+      out.pairs.push_back({l1[0], l1[1]});
+      out.point = {challenge(size_t(0), -1, l1)};
+    }
+    for (size_t k = 1; k < nu; k++) {
+      const size_t h = (size_t)1 << k;
+      const bool top = k + 1 == nu;                   // L_(k+1) is the table itself
+      const Vec& up_owner = top ? f_.evaluations() : tree.all;
+      const size_t at = top ? 0 : tree.level_offset(nu - k - 1);
+      const Mle eq = Mle::eq(out.point);
+      const Mle left(k, Vec::view(up_owner, at, h)), right(k, Vec::view(up_owner, at + h, h));
+      ListOfProducts<FIELD_ID> lp(k);
+      lp.add_product({&eq, &left, &right}, one);
+      SumcheckProof<FIELD_ID> sc = lp.prove([&](size_t i, const std::vector<Fr>& evals) { return challenge(k, (int)i, evals); });
+      const std::pair<Fr, Fr> pair{sc.final_evaluations[1], sc.final_evaluations[2]};
+      const Fr tau = challenge(k, -1, std::vector<Fr>{pair.first, pair.second});
+      out.point = sc.point;
+      out.point.push_back(tau);
+      out.sumchecks.push_back(std::move(sc));
+      out.pairs.push_back(pair);
+    }
+    return out;
+  }
+
+ private:
+  const Mle& f_;
 };
 
 // ---- point vectors kept on the device: elementwise scalar multiplication, elementwise sum, two-scalar fold ----

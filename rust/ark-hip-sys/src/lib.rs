@@ -218,6 +218,16 @@ extern "C" {
     pub fn ark_hip_mle_eq_plan(num_vars: c_uint, tile_log: *mut c_int, passes: *mut c_int, widths: *mut c_int, tiles_log: *mut c_int) -> c_int;
     pub fn ark_hip_mle_quotients_plan(num_vars: c_uint, tile_log: *mut c_int, passes: *mut c_int, widths: *mut c_int,
                                       tiles_log: *mut c_int) -> c_int;
+    /// The product tree over a table, pairing over the last variable: `d_tree` receives `2^num_vars - 1` elements, level `j`
+    /// (`2^(num_vars-j)` elements) at element offset `2^num_vars - 2^(num_vars-j+1)`, the product last; `out_product` (host,
+    /// may be null: asynchronous) receives the product.
+    pub fn ark_hip_mle_product_tree_device(field: c_int, d_evals: *const c_void, num_vars: c_uint, d_tree: *mut c_void,
+                                           out_product: *mut u64) -> c_int;
+    /// Host only: the launches of that call as runs of one kernel variant (`widths`, `group_log`: 8 entries each).
+    pub fn ark_hip_mle_product_tree_plan(num_vars: c_uint, passes: *mut c_int, widths: *mut c_int, group_log: *mut c_int) -> c_int;
+    /// `d_out[i] = c0 + sum_k coeffs[k] d_tables[k][i]`; `c0`: a host element or null for zero; `1 <= ntables <= 8`.
+    pub fn ark_hip_fr_lincomb_device(field: c_int, d_tables: *const *const c_void, ntables: c_uint, coeffs: *const u64, c0: *const u64,
+                                     d_out: *mut c_void, n: usize) -> c_int;
     /// One sumcheck round over `ntables` device tables of `2^num_vars` elements: `out_evals[t]`, `t = 0 ..= D`, of
     /// `sum_b sum_j c_j prod_k (T_k[2b] + t (T_k[2b+1] - T_k[2b]))`; with `r_prev` (host element) the first variable is bound
     /// to it first, into `d_out_tables`, in the same launch.  `term_tables`: the factors' table indices, term after term.

@@ -44,6 +44,8 @@ pub struct DeviceVec<F: FftField> {
     cap: usize,
     device: c_int,
     field: c_int,
+    /// a view into another vector's memory: it frees nothing
+    view: bool,
     _f: PhantomData<F>,
 }
 // the pointer is device memory owned by this value; every access goes through the library, which locks its context
@@ -63,7 +65,23 @@ impl<F: FftField> DeviceVec<F> {
             rc(unsafe { sys::ark_hip_malloc(len * 32, &mut ptr) })?;
         }
         let device = unsafe { sys::ark_hip_get_device() };
-        Ok(Self { ptr, len, cap: len, device, field, _f: PhantomData })
+        Ok(Self { ptr, len, cap: len, device, field, view: false, _f: PhantomData })
+    }
+    /// `len` elements of `owner` from element `offset` on: a view, no copy, which frees nothing when dropped -- the halves of
+    /// a product tree's level as the evaluations of a `DenseMultilinearExtension`.  `Err(Mismatch)` if it leaves its owner.
+    ///
+    /// # Safety
+    /// The view must be dropped before its owner is dropped, resized or written through `&mut`.
+    pub unsafe fn view(owner: &Self, offset: usize, len: usize) -> Result<Self, DeviceError> {
+        owner.here()?;
+        if offset > owner.len || len > owner.len - offset {
+            return Err(DeviceError::Mismatch);
+        }
+        let ptr = if len == 0 { core::ptr::null_mut() } else { (owner.ptr as *mut u8).add(32 * offset) as *mut c_void };
+        Ok(Self { ptr, len, cap: len, device: owner.device, field: owner.field, view: true, _f: PhantomData })
+    }
+    pub fn is_view(&self) -> bool {
+        self.view
     }
     /// `vec![F::zero(); len]` on the device.
     pub fn zeros(len: usize) -> Result<Self, DeviceError> {
@@ -227,7 +245,7 @@ impl<F: FftField> DeviceVec<F> {
 }
 impl<F: FftField> Drop for DeviceVec<F> {
     fn drop(&mut self) {
-        if self.ptr.is_null() {
+        if self.ptr.is_null() || self.view {
             return;
         }
         unsafe {

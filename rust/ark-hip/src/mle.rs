@@ -51,6 +51,48 @@ impl<F: FftField> Quotients<F> {
     }
 }
 
+/// What [`DeviceMultilinearExtension::product_tree`] returns: the product of all entries and the binary product tree pairing
+/// over the LAST variable, all in one device vector of `2^num_vars - 1` elements; level `j` (`1 <= j <= num_vars`) is the
+/// `level_len(j)` elements from `level_offset(j)` on, its element `i` the product of elements `i` and `i + level_len(j)` of
+/// level `j - 1` (level 0: the table).  The last element is the product.
+pub struct ProductTree<F: FftField> {
+    pub product: F,
+    num_vars: usize,
+    all: DeviceVec<F>,
+}
+impl<F: FftField> ProductTree<F> {
+    pub fn num_vars(&self) -> usize {
+        self.num_vars
+    }
+    pub fn level_offset(&self, j: usize) -> usize {
+        (1usize << self.num_vars) - (2usize << (self.num_vars - j))
+    }
+    pub fn level_len(&self, j: usize) -> usize {
+        1usize << (self.num_vars - j)
+    }
+    pub fn level_ptr(&self, j: usize) -> *const c_void {
+        unsafe { (self.all.as_device_ptr() as *const u8).add(32 * self.level_offset(j)) as *const c_void }
+    }
+    pub fn level_to_vec(&self, j: usize) -> Result<Vec<F>, DeviceError> {
+        let n = self.level_len(j);
+        let mut out: Vec<F> = Vec::with_capacity(n);
+        rc(unsafe { sys::ark_hip_memcpy_d2h(out.as_mut_ptr() as *mut c_void, self.level_ptr(j), n * 32) })?;
+        unsafe { out.set_len(n) };
+        Ok(out)
+    }
+    pub fn all(&self) -> &DeviceVec<F> {
+        &self.all
+    }
+}
+
+/// The launches of [`DeviceMultilinearExtension::product_tree`] as `ark_hip_mle_product_tree_plan` reports them: per run of
+/// launches of one kernel variant, (levels, log2 of the chunks of 64 outputs one wave walks).  Host only.
+pub fn product_tree_plan(num_vars: usize) -> Result<Vec<(usize, usize)>, DeviceError> {
+    let (mut passes, mut widths, mut groups) = (0 as core::ffi::c_int, [0 as core::ffi::c_int; 8], [0 as core::ffi::c_int; 8]);
+    rc(unsafe { sys::ark_hip_mle_product_tree_plan(num_vars as c_uint, &mut passes, widths.as_mut_ptr(), groups.as_mut_ptr()) })?;
+    Ok((0..passes as usize).map(|p| (widths[p] as usize, groups[p] as usize)).collect())
+}
+
 fn rc(code: core::ffi::c_int) -> Result<(), DeviceError> {
     if code == 0 { Ok(()) } else { Err(DeviceError::Library(code)) }
 }
@@ -173,6 +215,42 @@ impl<F: FftField> DeviceMultilinearExtension<F> {
             points.push(out.assume_init());
         }
         Ok((q.value, points))
+    }
+    /// The binary product tree over the table and the product of all its entries; waits for the
+    /// product.  The table is not written.
+    pub fn product_tree(&self) -> Result<ProductTree<F>, DeviceError> {
+        self.evals.here()?;
+        let mut all = DeviceVec::<F>::alloc((1usize << self.num_vars) - 1)?;
+        let mut out = [0u64; 4];
+        rc(unsafe {
+            sys::ark_hip_mle_product_tree_device(self.evals.field(), self.evals.as_device_ptr(), self.num_vars as c_uint,
+                                                 all.as_device_mut_ptr(), out.as_mut_ptr())
+        })?;
+        Ok(ProductTree { product: sys::from_limbs::<F>(&out), num_vars: self.num_vars, all })
+    }
+    /// `c0 + sum_k coeffs[k] tables[k]`, entry by entry in one pass (`c0 = None`: zero): the fingerprints that are the
+    /// leaves of a grand product.  `Err(Mismatch)` unless there are 1 to 8 tables of one size with one coefficient each.
+    pub fn linear_combination(tables: &[&Self], coeffs: &[F], c0: Option<&F>) -> Result<Self, DeviceError> {
+        if tables.is_empty() || tables.len() > 8 || coeffs.len() != tables.len() {
+            return Err(DeviceError::Mismatch);
+        }
+        let num_vars = tables[0].num_vars;
+        let mut ptrs: Vec<*const c_void> = Vec::with_capacity(tables.len());
+        for t in tables {
+            t.evals.here()?;
+            if t.num_vars != num_vars {
+                return Err(DeviceError::Mismatch);
+            }
+            ptrs.push(t.evals.as_device_ptr());
+        }
+        let mut out = DeviceVec::<F>::alloc(1usize << num_vars)?;
+        let k = flat(coeffs);
+        let g = c0.map(|x| sys::limbs(x));
+        rc(unsafe {
+            sys::ark_hip_fr_lincomb_device(out.field(), ptrs.as_ptr(), ptrs.len() as c_uint, k.as_ptr(),
+                                           g.as_ref().map_or(core::ptr::null(), |x| x.as_ptr()), out.as_device_mut_ptr(), out.len())
+        })?;
+        Ok(Self { num_vars, evals: out })
     }
     /// `relabel` (dense.rs:195-199): a new polynomial with the `k` variables from `a` and from `b` exchanged.
     pub fn relabel(&self, a: usize, b: usize, k: usize) -> Result<Self, DeviceError> {
