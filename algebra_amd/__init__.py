@@ -21,7 +21,8 @@ from .msm import (BatchMulPreprocessing, batch_mul, ChunkedPippenger, HashMapPip
 from .domain import Radix2EvaluationDomain  # noqa: F401
 from .poly import DeviceVec, poly_mul, poly_mul_host  # noqa: F401
 from .points import DevicePoints  # noqa: F401
-from .mle import (DenseMultilinearExtension, DeviceSegment, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_product_tree_launches,  # noqa: F401
-                  mle_product_tree_plan, mle_quotients_plan)
+from .mle import (DenseMultilinearExtension, DeviceSegment, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_fraction_tree_launches,  # noqa: F401
+                  mle_fraction_tree_plan, mle_product_tree_launches, mle_product_tree_plan, mle_quotients_plan)
 from .sumcheck import ListOfProducts, SumcheckProof, sumcheck_plan  # noqa: F401
 from .grand_product import GrandProduct, GrandProductProof  # noqa: F401
+from .fraction_sum import FractionalSum, FractionalSumProof  # noqa: F401

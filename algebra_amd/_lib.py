@@ -161,6 +161,9 @@ SYMBOLS = {
     "ark_hip_mle_product_tree_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]),
     "ark_hip_mle_product_tree_plan": (C.c_int, [C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ark_hip_fr_lincomb_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_mle_fraction_tree_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ark_hip_mle_fraction_tree_plan": (C.c_int, [C.c_uint, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ark_hip_fr_count_indices_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "ark_hip_sumcheck_round_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
                                                 C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "ark_hip_sumcheck_plan": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -572,6 +572,16 @@ inline int fr_lincomb_dispatch(int field, const FrLincomb& lc, void* out, size_t
   ARK_FIELD_SWITCH(field, X);
 #undef X
 }
+inline int frac_tree_dispatch(int field, const void* nsrc, const void* dsrc, int log_n, int w, void* ndst, void* ddst, hipStream_t st) {
+#define X(NAME) frac_tree_##NAME(nsrc, dsrc, log_n, w, ndst, ddst, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
+inline int fr_count_dispatch(int field, const void* indices, size_t n, void* out, size_t table_len, hipStream_t st) {
+#define X(NAME) fr_count_##NAME(indices, n, out, table_len, st)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
 inline int sumcheck_round_dispatch(int field, const SumcheckRound& rd, hipStream_t st) {
 #define X(NAME) sumcheck_round_##NAME(rd, st)
   ARK_FIELD_SWITCH(field, X);

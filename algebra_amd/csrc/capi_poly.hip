@@ -1,14 +1,16 @@
 // C ABI of libark_hip.so: polynomial operations on device-resident vectors -- evaluation at a point, division by x - z and
 // by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products -- and dense
 // multilinear extensions: fix_variables, evaluate, relabel, a + k x, the eq table and an opening's quotients -- and the
-// sumcheck prover's round over such tables, the product tree of a grand product and its fingerprints (see include/ark_hip.h;
-// kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh, grand_product.cuh).
+// sumcheck prover's round over such tables, the product tree of a grand product and its fingerprints, the fraction tree and the
+// multiplicities of a lookup (see include/ark_hip.h; kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh,
+// grand_product.cuh, fraction_sum.cuh).
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "polyops.cuh"
 #include "mle.cuh"
 #include "mle_open.cuh"
 #include "grand_product.cuh"
+#include "fraction_sum.cuh"
 #include "sumcheck.cuh"
 using namespace arkhip;
 using namespace arkhip::capi;
@@ -143,6 +145,18 @@ inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 static_assert(SUMCHECK_MAX_TABLES == ARK_HIP_SUMCHECK_MAX_TABLES && SUMCHECK_MAX_TERMS == ARK_HIP_SUMCHECK_MAX_TERMS &&
                   SUMCHECK_MAX_DEGREE == ARK_HIP_SUMCHECK_MAX_DEGREE, "the header publishes the kernels' limits");
 static_assert(PROD_TREE_MAX_W == ARK_HIP_PRODUCT_TREE_LEVELS, "the header publishes the levels of a full launch");
+static_assert(FRAC_TREE_MAX_W == ARK_HIP_FRACTION_TREE_LEVELS || FRAC_TREE_VARIANT_BUILD, "the header publishes the levels of a full launch");
+// the field's one (R mod p) as a host element
+template <class FP>
+int fr_one(uint64_t* out) {
+  Fp<FP>::one().store(out);
+  return 0;
+}
+inline int fr_one_any(int field, uint64_t* out) {
+#define X(NAME) fr_one<NAME>(out)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
 
 }  // namespace
 
@@ -473,6 +487,60 @@ int ark_hip_fr_lincomb_device(int field, const void* const* d_tables, unsigned n
   ARK_SCOPE(sc);
   Context* c = sc.c;
   if (int rc = fr_lincomb_dispatch(field, lc, d_out, n, c->stream)) return rc;
+  return mark_producer(c);
+}
+
+int ark_hip_mle_fraction_tree_plan(unsigned num_vars, int has_num, int* passes, int* widths, int* group_log) {
+  if (!passes || !widths || !group_log || num_vars >= 64) return ARK_HIP_ERR_ARG;
+  (void)has_num;   // ones for numerators change the first launch's kernel variant, not the launches
+  for (int p = 0; p < MLE_MAX_PASSES; p++) widths[p] = group_log[p] = 0;
+  *passes = frac_tree_plan((int)num_vars, widths);   // one chunk of 64 outputs per wave in every launch: group_log stays 0
+  return 0;
+}
+
+int ark_hip_mle_fraction_tree_device(int field, const void* d_num, const void* d_den, unsigned num_vars, void* d_num_tree,
+                                     void* d_den_tree, uint64_t* out_root) {
+  if (!field_served(field) || !d_den || num_vars >= 64 || (num_vars && (!d_num_tree || !d_den_tree))) return ARK_HIP_ERR_ARG;
+  if (num_vars > 58) return ARK_HIP_ERR_ARG;   // a table's bytes must fit a size_t
+  const size_t n = (size_t)1 << num_vars;
+  if (num_vars) {
+    const size_t tb = (n - 1) * 32;
+    if (ranges_overlap(d_num_tree, tb, d_den_tree, tb) || ranges_overlap(d_den, n * 32, d_num_tree, tb) ||
+        ranges_overlap(d_den, n * 32, d_den_tree, tb))
+      return ARK_HIP_ERR_ARG;
+    if (d_num && (ranges_overlap(d_num, n * 32, d_num_tree, tb) || ranges_overlap(d_num, n * 32, d_den_tree, tb))) return ARK_HIP_ERR_ARG;
+  }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  const void *ncur = d_num, *dcur = d_den;   // a constant: no trees, the root is the one fraction
+  if (num_vars) {
+    int widths[FRAC_TREE_MAX_LAUNCHES];
+    const int launches = frac_tree_launches((int)num_vars, widths);
+    int m = (int)num_vars;
+    for (int p = 0; p < launches; p++) {
+      // level k starts at element 2^num_vars - 2^(k+1) of its tree: the launch reads level m and writes from level m - 1 on
+      const size_t dst = (n - ((size_t)1 << m)) * 32;
+      if (int rc = frac_tree_dispatch(field, ncur, dcur, m, widths[p], (char*)d_num_tree + dst, (char*)d_den_tree + dst, c->stream)) return rc;
+      m -= widths[p];
+      ncur = (char*)d_num_tree + (n - ((size_t)2 << m)) * 32;
+      dcur = (char*)d_den_tree + (n - ((size_t)2 << m)) * 32;
+    }
+  }
+  if (!out_root) return num_vars ? mark_producer(c) : 0;
+  if (ncur) ARK_HIP_TRY(hipMemcpyAsync(out_root, ncur, 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipMemcpyAsync(out_root + 4, dcur, 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!ncur) return fr_one_any(field, out_root);   // no variables and ones for numerators
+  return 0;
+}
+
+int ark_hip_fr_count_indices_device(int field, const uint32_t* d_indices, size_t n, void* d_out, size_t table_len) {
+  if (!field_served(field) || !d_out || (n && !d_indices) || table_len == 0) return ARK_HIP_ERR_ARG;
+  if ((uint64_t)n >> 32 || table_len > ((size_t)1 << 58)) return ARK_HIP_ERR_ARG;   // a count fits a cell's first word
+  if (n && ranges_overlap(d_indices, n * 4, d_out, table_len * 32)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (int rc = fr_count_dispatch(field, d_indices, n, d_out, table_len, c->stream)) return rc;
   return mark_producer(c);
 }
 

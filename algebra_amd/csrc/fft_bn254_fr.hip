@@ -5,6 +5,7 @@
 #include "mle.cuh"
 #include "mle_open.cuh"
 #include "grand_product.cuh"
+#include "fraction_sum.cuh"
 #include "sumcheck.cuh"
 #include "internal.hpp"
 namespace arkhip {
@@ -62,6 +63,12 @@ int prod_tree_BN254_FR(const void* src, int log_n, int w, void* dst, hipStream_t
   return prod_tree_launch<Fp<BN254_FR>>(src, log_n, w, dst, s);
 }
 int fr_lincomb_BN254_FR(const FrLincomb& lc, void* out, size_t n, hipStream_t s) { return fr_lincomb_launch<Fp<BN254_FR>>(lc, out, n, s); }
+int frac_tree_BN254_FR(const void* nsrc, const void* dsrc, int log_n, int w, void* ndst, void* ddst, hipStream_t s) {
+  return frac_tree_launch<Fp<BN254_FR>>(nsrc, dsrc, log_n, w, ndst, ddst, s);
+}
+int fr_count_BN254_FR(const void* indices, size_t n, void* out, size_t table_len, hipStream_t s) {
+  return fr_count_launch<Fp<BN254_FR>>(indices, n, out, table_len, s);
+}
 int sumcheck_round_BN254_FR(const SumcheckRound& rd, hipStream_t s) { return sumcheck_round_launch<Fp<BN254_FR>>(rd, s); }
 int fft_axis_BN254_FR(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4, hipStream_t s) {
   return fft_axis_run<BN254_FR>(ws, d_src, d_dst, G, cols, root4, s);

@@ -83,6 +83,8 @@ ARK_DECL_CURVE(BLS12_381_G2)
   int mle_quot_##NAME(const void* d_src, int log_n, int w, const MlePoint& pt, void* d_quot, void* d_dst, hipStream_t s); \
   int prod_tree_##NAME(const void* d_src, int log_n, int w, void* d_dst, hipStream_t s);                            \
   int fr_lincomb_##NAME(const FrLincomb& lc, void* d_out, size_t n, hipStream_t s);                                 \
+  int frac_tree_##NAME(const void* d_nsrc, const void* d_dsrc, int log_n, int w, void* d_ndst, void* d_ddst, hipStream_t s); \
+  int fr_count_##NAME(const void* d_indices, size_t n, void* d_out, size_t table_len, hipStream_t s);               \
   int sumcheck_round_##NAME(const SumcheckRound& rd, hipStream_t s);                                                \
   int fft_roots_##NAME(FftWorkspace& ws, int k, const uint64_t* root4, hipStream_t s, const uint32_t** out);        \
   int fft_scalars_##NAME(FftWorkspace& ws, const uint64_t* base4, const uint64_t* mul4, size_t count, void* d_out,  \

@@ -65,6 +65,28 @@ def mle_product_tree_launches(num_vars):
     return out
 
 
+FRACTION_TREE_LEVELS = 2    # ARK_HIP_FRACTION_TREE_LEVELS of include/ark_hip.h: the most levels one launch forms
+
+
+def mle_fraction_tree_plan(num_vars, has_num=True):
+    """([levels of each run of launches], [always 0]) of `fraction_tree`, as ark_hip_mle_fraction_tree_plan reports them: the
+    full launches as one run, then the remainder launch"""
+    ps = C.c_int()
+    widths, groups = (C.c_int * 8)(), (C.c_int * 8)()
+    check(lib().ark_hip_mle_fraction_tree_plan(num_vars, 1 if has_num else 0, C.byref(ps), widths, groups),
+          "ark_hip_mle_fraction_tree_plan")
+    return [widths[i] for i in range(ps.value)], [groups[i] for i in range(ps.value)]
+
+
+def mle_fraction_tree_launches(num_vars, has_num=True):
+    """[(levels, numerators are read)] launch by launch: the runs of mle_fraction_tree_plan spelled out; only the first
+    launch of a sum with ones for numerators reads none"""
+    out = []
+    for w in mle_fraction_tree_plan(num_vars, has_num)[0]:
+        out += [FRACTION_TREE_LEVELS] * (w // FRACTION_TREE_LEVELS) if w >= FRACTION_TREE_LEVELS else [w]
+    return [(w, bool(has_num) or i > 0) for i, w in enumerate(out)]
+
+
 class DeviceSegment:
     """`len` elements inside a DeviceVec, from element `offset` on: a view, no copy.  `ptr` is a device pointer that the
     MSM's device entries accept as a scalar vector; the view keeps its owner alive."""
@@ -244,6 +266,56 @@ class DenseMultilinearExtension:
                                               None if g is None else g.ctypes.data_as(C.c_void_p), out.ptr, len(out)),
               "ark_hip_fr_lincomb_device")
         return cls(first.num_vars, out)
+
+    # ---- fractional sums -------------------------------------------------------------------
+    def fraction_tree(self, num=None, wait=True):
+        """(root, [num_level_1, ..], [den_level_1, ..]) of the sum of fractions num[b] / self[b]: the tree that adds
+        fractions pairing over the LAST variable, N = n0 d1 + n1 d0, D = d0 d1.  `num`: an extension of the same size, or
+        None for ones.  level_j has 2^(num_vars-j) elements; the levels of a tree are DeviceSegments of one DeviceVec of
+        2^num_vars - 1 elements in product_tree's layout.  root: numpy uint64 [2, 4] = (P, Q) with P / Q the sum; wait=False
+        returns None for it and leaves the call asynchronous.  Nothing is inverted; the tables are not written."""
+        if num is not None:
+            if num.field != self.field:
+                raise ValueError("polynomials over different fields")
+            if num.num_vars != self.num_vars:
+                raise ValueError("num_vars differ: %d and %d" % (num.num_vars, self.num_vars))
+        n = 1 << self.num_vars
+        trees = [DeviceVec(self.field, n - 1, _zero=False) for _ in range(2)]
+        out = np.zeros((2, 4), dtype=np.uint64) if wait else None
+        check(lib().ark_hip_mle_fraction_tree_device(self.field, None if num is None else num.evaluations.ptr, self.evaluations.ptr,
+                                                     self.num_vars, trees[0].ptr if n > 1 else None, trees[1].ptr if n > 1 else None,
+                                                     out.ctypes.data_as(C.c_void_p) if wait else None),
+              "ark_hip_mle_fraction_tree_device")
+        levels = [[DeviceSegment(t, n - (n >> (j - 1)), n >> j) for j in range(1, self.num_vars + 1)] for t in trees]
+        return out, levels[0], levels[1]
+
+    @staticmethod
+    def count_indices(field, indices, table_len):
+        """the multiplicity table of a lookup: m[j] = #{i : indices[i] = j} for j < table_len as Montgomery elements, counted
+        on the device.  indices: numpy uint32 [n] (one upload).  An index >= table_len is skipped and not reported: the
+        counts sum to n exactly when none was skipped.  -> a new DenseMultilinearExtension when table_len is a power of two,
+        else a DeviceVec."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        table_len = int(table_len)
+        if table_len < 1:
+            raise ValueError("table_len must be positive")
+        out = DeviceVec(field, table_len, _zero=False)
+        d_idx = C.c_void_p(0)
+        try:
+            if idx.size:
+                check(lib().ark_hip_malloc(idx.nbytes, C.byref(d_idx)), "ark_hip_malloc")
+                check(lib().ark_hip_memcpy_h2d(d_idx, idx.ctypes.data_as(C.c_void_p), idx.nbytes), "ark_hip_memcpy_h2d")
+            check(lib().ark_hip_fr_count_indices_device(out.field, d_idx if idx.size else None, idx.size, out.ptr, table_len),
+                  "ark_hip_fr_count_indices_device")
+        except Exception:
+            out.free()
+            raise
+        finally:
+            if d_idx.value:
+                check(lib().ark_hip_free(d_idx), "ark_hip_free")
+        if table_len & (table_len - 1) == 0:
+            return DenseMultilinearExtension(table_len.bit_length() - 1, out)
+        return out
 
     # ---- relabel ------------------------------------------------------------------------------------------------
     def _relabel(self, a, b, k, dst):

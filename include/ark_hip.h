@@ -579,6 +579,38 @@ int ark_hip_mle_product_tree_plan(unsigned num_vars, int* passes, int* widths, i
 int ark_hip_fr_lincomb_device(int field, const void* const* d_tables, unsigned ntables, const uint64_t* coeffs,
                               const uint64_t* c0, void* d_out, size_t n);
 
+/* ---- fractional sums on device tables -----------------------------------------------------------
+ * A lookup argument in logUp form reduces to a sum of fractions, sum_i 1 / (gamma + w_i) = sum_j m_j / (gamma + t_j).  The
+ * fraction tree carries pairs (N, D) and adds fractions level by level, pairing over the LAST variable as the product tree
+ * does: N_nu = d_num, D_nu = d_den (2^num_vars elements each), and for i < 2^k
+ *   N_k[i] = N_{k+1}[i] * D_{k+1}[i + 2^k] + N_{k+1}[i + 2^k] * D_{k+1}[i],     D_k[i] = D_{k+1}[i] * D_{k+1}[i + 2^k];
+ * (N_0[0], D_0[0]) is the root (P, Q) with P / Q = sum_b N_nu[b] / D_nu[b].  Nothing is inverted and a zero denominator is
+ * just a value.  d_num_tree, d_den_tree: 2^num_vars - 1 elements each in the layout of ark_hip_mle_product_tree_device --
+ * level j (1 <= j <= num_vars) is L_{num_vars-j}, 2^(num_vars-j) elements at element offset 2^num_vars - 2^(num_vars-j+1),
+ * the root last.  d_num == NULL: every numerator is one (the witness side of a lookup); no numerator leaf is read, the first
+ * level is N = D[i] + D[i + h], D = D[i] * D[i + h], and d_num_tree still receives levels 1 .. num_vars.
+ * out_root: a HOST pointer to two elements (P, Q), the call waits for it; NULL makes the call asynchronous.  num_vars = 0:
+ * no trees (both tree pointers may be NULL), the root is (d_num[0] or one, d_den[0]).  The inputs are left untouched; the
+ * two trees must not overlap each other or an input (ARK_HIP_ERR_ARG).  ARK_HIP_ERR_ARG comes before any device is touched
+ * for an unknown field, a null d_den, a null tree with num_vars > 0, num_vars >= 64 or tables of more than 2^58 elements,
+ * and any such overlap.  No scratch: later launches read the levels the earlier ones wrote in the trees. */
+#define ARK_HIP_FRACTION_TREE_LEVELS 2
+int ark_hip_mle_fraction_tree_device(int field, const void* d_num, const void* d_den, unsigned num_vars, void* d_num_tree,
+                                     void* d_den_tree, uint64_t* out_root);
+/* Host only, no device needed: the launches of that call, reported as ark_hip_mle_product_tree_plan reports the product
+ * tree's.  Entry p (8 entries each, 0 past the last) is a RUN of consecutive launches of one kernel instantiation: first the
+ * full launches, widths[0] levels in all, ARK_HIP_FRACTION_TREE_LEVELS per launch; then the one remainder launch.  At most
+ * two entries; the widths sum to num_vars; group_log[p] is always 0.  has_num = 0 (ones for numerators) changes the kernel
+ * variant of the first launch, not the launches. */
+int ark_hip_mle_fraction_tree_plan(unsigned num_vars, int has_num, int* passes, int* widths, int* group_log);
+/* The multiplicity table of a lookup: d_out[j] = #{i < n : d_indices[i] = j} for j < table_len, as Montgomery elements.
+ * d_indices: n device uint32_t (may be NULL when n = 0); table_len need not be a power of two.  An index >= table_len is
+ * SKIPPED and not reported: sum_j d_out[j] = n holds exactly when none was skipped.  n = 0 writes zeros.  No scratch: the
+ * output is its own workspace (cleared, counted into with atomic adds on each cell's first word, converted in place).
+ * ARK_HIP_ERR_ARG comes before any device is touched for an unknown field, a null pointer, table_len = 0, n >= 2^32,
+ * table_len > 2^58, or d_out overlapping the indices.  Asynchronous. */
+int ark_hip_fr_count_indices_device(int field, const uint32_t* d_indices, size_t n, void* d_out, size_t table_len);
+
 /* ---- the sumcheck prover's round on device tables --------------------------------------------
  * The sum is a list of products of multilinear tables, each with a coefficient (ListOfProductsOfPolynomials of
  * ark-linear-sumcheck): sum_j c_j prod_{k in term j} f_k.  Tables follow the conventions above: 2^num_vars Montgomery

@@ -878,6 +878,48 @@ class DenseMultilinearExtension {
                                     c0 ? c0->limbs.data() : nullptr, out.device_ptr(), out.len()), "ark_hip_fr_lincomb_device");
     return DenseMultilinearExtension(tables[0]->num_vars_, std::move(out));
   }
+  // ---- fractional sums ----
+  // The tree that adds the fractions num[b] / (*this)[b], pairing over the LAST variable (N = n0 d1 + n1 d0, D = d0 d1): two
+  // device vectors of 2^num_vars - 1 elements in product_tree's layout, and the root (P, Q) with P / Q the sum.  Nothing is
+  // inverted.
+  struct FractionTree {
+    Fr root_num, root_den;
+    size_t num_vars = 0;
+    Vec num, den;
+    size_t level_offset(size_t j) const { return ((size_t)1 << num_vars) - ((size_t)2 << (num_vars - j)); }
+    size_t level_len(size_t j) const { return (size_t)1 << (num_vars - j); }
+    Vec num_level(size_t j) const { return Vec::view(num, level_offset(j), level_len(j)); }
+    Vec den_level(size_t j) const { return Vec::view(den, level_offset(j), level_len(j)); }
+  };
+  // num == nullptr: every numerator is one
+  FractionTree fraction_tree(const DenseMultilinearExtension* num) const {
+    if (num && num->num_vars_ != num_vars_) throw Error(ARK_HIP_ERR_ARG, "num_vars differ");
+    FractionTree t;
+    t.num_vars = num_vars_;
+    t.num = Vec::uninit(((size_t)1 << num_vars_) - 1);
+    t.den = Vec::uninit(((size_t)1 << num_vars_) - 1);
+    uint64_t root[8];
+    check(ark_hip_mle_fraction_tree_device(FIELD_ID, num ? num->evals_.device_ptr() : nullptr, evals_.device_ptr(), (unsigned)num_vars_,
+                                           t.num.device_ptr(), t.den.device_ptr(), root), "ark_hip_mle_fraction_tree_device");
+    std::memcpy(t.root_num.limbs.data(), root, 32);
+    std::memcpy(t.root_den.limbs.data(), root + 4, 32);
+    return t;
+  }
+  // the launches of fraction_tree as ark_hip_mle_fraction_tree_plan reports them: (levels, 0) per run
+  static std::vector<std::pair<int, int>> fraction_tree_plan(size_t num_vars, bool has_num = true) {
+    int passes = 0, widths[8], groups[8];
+    check(ark_hip_mle_fraction_tree_plan((unsigned)num_vars, has_num ? 1 : 0, &passes, widths, groups), "ark_hip_mle_fraction_tree_plan");
+    std::vector<std::pair<int, int>> out;
+    for (int p = 0; p < passes; p++) out.push_back({widths[p], groups[p]});
+    return out;
+  }
+  // the multiplicity table of a lookup, m[j] = #{i : indices[i] = j} for j < table_len, counted on the device from n device
+  // uint32_t.  An index >= table_len is skipped and not reported: the counts sum to n exactly when none was skipped.
+  static Vec count_indices(const uint32_t* d_indices, size_t n, size_t table_len) {
+    Vec out = Vec::uninit(table_len);
+    check(ark_hip_fr_count_indices_device(FIELD_ID, d_indices, n, out.device_ptr(), table_len), "ark_hip_fr_count_indices_device");
+    return out;
+  }
   // exchanges the k variables from position a with those from position b (dense.rs:76-92, :195-199)
   DenseMultilinearExtension relabel(size_t a, size_t b, size_t k) const {
     Vec out = Vec::uninit(evals_.len());
@@ -1111,6 +1153,93 @@ class GrandProduct {
 
  private:
   const Mle& f_;
+};
+
+// The layered proof of a sum of fractions P / Q = sum_b num[b] / den[b] (the GKR form of logUp): the
+// fraction tree, then per layer k = 1 .. nu - 1 one sumcheck of eq(r_k, x) (n0 d1 + n1 d0 + lambda d0 d1)(x) -- three products
+// over the eq table and four views of the halves of the levels above -- whose sum is N_k(r_k) + lambda D_k(r_k); it leaves
+// the claims n0 + tau (n1 - n0) and d0 + tau (d1 - d0) about N_{k+1}(rho, tau) and D_{k+1}(rho, tau).  The last claims are
+// num(point) and den(point), which evaluate / open answer.  With ones for numerators (num == nullptr) the level above the
+// last layer is the leaves: its products are eq d1, eq d0 and lambda eq d0 d1, and its values the pair (d0, d1).
+// challenge(layer, round, values): round >= 0 carries that round's evaluations; TAU_ROUND = -1 carries the layer's values
+// and asks for its tau; LAMBDA_ROUND = -2 carries no values and asks for the layer's batching challenge, before its sumcheck.
+// Nothing is hashed and nothing verified here; the tables and the trees are not written.
+template <int FIELD_ID>
+struct FractionalSumProof {
+  Fr root_num, root_den;                                           // (P, Q)
+  std::vector<std::optional<SumcheckProof<FIELD_ID>>> sumchecks;   // per layer; none for layer 0
+  std::vector<std::vector<Fr>> values;                             // per layer: (n0, n1, d0, d1), or (d0, d1) where the numerators are ones
+  std::vector<Fr> point;                                           // r_nu: where the verifier's last claims lie
+};
+template <int FIELD_ID>
+class FractionalSum {
+ public:
+  using Mle = DenseMultilinearExtension<FIELD_ID>;
+  using Vec = DeviceVec<FIELD_ID>;
+  static constexpr int TAU_ROUND = -1;
+  static constexpr int LAMBDA_ROUND = -2;
+  // num == nullptr: every numerator is one
+  FractionalSum(const Mle* num, const Mle& den) : num_(num), den_(den) {
+    if (num && num->num_vars() != den.num_vars()) throw Error(ARK_HIP_ERR_ARG, "num_vars differ");
+  }
+  template <class Challenge>
+  FractionalSumProof<FIELD_ID> prove(Challenge&& challenge) const {
+    const size_t nu = den_.num_vars();
+    FractionalSumProof<FIELD_ID> out;
+    typename Mle::FractionTree tree = den_.fraction_tree(num_);
+    out.root_num = tree.root_num;
+    out.root_den = tree.root_den;
+    if (nu == 0) return out;
+    const Fr one = Mle::eq({}).to_evaluations()[0];   // the eq table of no variables is its scale, one
+    {
+      std::vector<Fr> v;                              // N_1 (unless it is the implicit ones), then D_1
+      if (nu > 1) v = tree.num_level(nu - 1).to_vec();
+      else if (num_) v = num_->to_evaluations();
+      const std::vector<Fr> d1 = nu == 1 ? den_.to_evaluations() : tree.den_level(nu - 1).to_vec();
+      v.insert(v.end(), d1.begin(), d1.end());
+      out.sumchecks.push_back(std::nullopt);
+      out.point = {challenge(size_t(0), TAU_ROUND, v)};
+      out.values.push_back(std::move(v));
+    }
+    for (size_t k = 1; k < nu; k++) {
+      const Fr lambda = challenge(k, LAMBDA_ROUND, std::vector<Fr>{});
+      const size_t h = (size_t)1 << k;
+      const bool top = k + 1 == nu;                   // the levels above are the tables themselves
+      const size_t at = top ? 0 : tree.level_offset(nu - k - 1);
+      const Vec& d_owner = top ? den_.evaluations() : tree.den;
+      const Mle eq = Mle::eq(out.point);
+      const Mle d0(k, Vec::view(d_owner, at, h)), d1(k, Vec::view(d_owner, at + h, h));
+      ListOfProducts<FIELD_ID> lp(k);
+      std::vector<Fr> v;
+      std::optional<SumcheckProof<FIELD_ID>> sc;
+      auto ask = [&](size_t i, const std::vector<Fr>& evals) { return challenge(k, (int)i, evals); };
+      if (top && !num_) {
+        lp.add_product({&eq, &d1}, one);
+        lp.add_product({&eq, &d0}, one);
+        lp.add_product({&eq, &d0, &d1}, lambda);
+        sc = lp.prove(ask);
+        v = {sc->final_evaluations[2], sc->final_evaluations[1]};                                  // tables: eq, d1, d0
+      } else {
+        const Vec& n_owner = top ? num_->evaluations() : tree.num;
+        const Mle n0(k, Vec::view(n_owner, at, h)), n1(k, Vec::view(n_owner, at + h, h));
+        lp.add_product({&eq, &n0, &d1}, one);
+        lp.add_product({&eq, &n1, &d0}, one);
+        lp.add_product({&eq, &d0, &d1}, lambda);
+        sc = lp.prove(ask);
+        v = {sc->final_evaluations[1], sc->final_evaluations[3], sc->final_evaluations[4], sc->final_evaluations[2]};   // eq, n0, d1, n1, d0
+      }
+      const Fr tau = challenge(k, TAU_ROUND, v);
+      out.point = sc->point;
+      out.point.push_back(tau);
+      out.sumchecks.push_back(std::move(sc));
+      out.values.push_back(std::move(v));
+    }
+    return out;
+  }
+
+ private:
+  const Mle* num_;
+  const Mle& den_;
 };
 
 // ---- point vectors kept on the device: elementwise scalar multiplication, elementwise sum, two-scalar fold ----

@@ -228,6 +228,18 @@ extern "C" {
     /// `d_out[i] = c0 + sum_k coeffs[k] d_tables[k][i]`; `c0`: a host element or null for zero; `1 <= ntables <= 8`.
     pub fn ark_hip_fr_lincomb_device(field: c_int, d_tables: *const *const c_void, ntables: c_uint, coeffs: *const u64, c0: *const u64,
                                      d_out: *mut c_void, n: usize) -> c_int;
+    /// The tree that adds the fractions `d_num[b] / d_den[b]`, pairing over the last variable (`N = n0 d1 + n1 d0`,
+    /// `D = d0 d1`): `d_num_tree`, `d_den_tree` receive `2^num_vars - 1` elements each in the layout of
+    /// `ark_hip_mle_product_tree_device`, the root last; `d_num` null: every numerator is one; `out_root` (host, two elements
+    /// `(P, Q)`, may be null: asynchronous) receives the root.
+    pub fn ark_hip_mle_fraction_tree_device(field: c_int, d_num: *const c_void, d_den: *const c_void, num_vars: c_uint,
+                                            d_num_tree: *mut c_void, d_den_tree: *mut c_void, out_root: *mut u64) -> c_int;
+    /// Host only: the launches of that call as runs of one kernel variant (`widths`, `group_log`: 8 entries each).
+    pub fn ark_hip_mle_fraction_tree_plan(num_vars: c_uint, has_num: c_int, passes: *mut c_int, widths: *mut c_int,
+                                          group_log: *mut c_int) -> c_int;
+    /// `d_out[j] = #{i < n : d_indices[i] = j}` for `j < table_len` as Montgomery elements; an index `>= table_len` is
+    /// skipped and not reported, so the counts sum to `n` exactly when none was skipped.  Asynchronous.
+    pub fn ark_hip_fr_count_indices_device(field: c_int, d_indices: *const u32, n: usize, d_out: *mut c_void, table_len: usize) -> c_int;
     /// One sumcheck round over `ntables` device tables of `2^num_vars` elements: `out_evals[t]`, `t = 0 ..= D`, of
     /// `sum_b sum_j c_j prod_k (T_k[2b] + t (T_k[2b+1] - T_k[2b]))`; with `r_prev` (host element) the first variable is bound
     /// to it first, into `d_out_tables`, in the same launch.  `term_tables`: the factors' table indices, term after term.

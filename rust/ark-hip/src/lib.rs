@@ -19,7 +19,8 @@
 //!   with the previous challenge bound in the same pass.  `DenseMultilinearExtension::eq` builds the table of `eq(r, .)` on the
 //!   device, `quotients` / `open` the quotients of a multilinear opening and their commitments, `product_tree` /
 //!   `linear_combination` the product tree and the fingerprints of a grand product, and [`grand_product::GrandProduct`] runs
-//!   its layered proof.
+//!   its layered proof; `fraction_tree` / `count_indices` the fraction tree and the multiplicities of a lookup, and
+//!   [`fraction_sum::FractionalSum`] runs the layered proof of a sum of fractions (logUp).
 //!
 //! Beyond the reference's surface: [`msm::PreparedBases`] (a fixed SRS resident on the GPU with its per-window
 //! multiples), [`msm::MsmJob`] (asynchronous MSMs), [`msm::msm_multi`] (one MSM over all GPUs of the node).
@@ -28,6 +29,7 @@
 //! tests/ through ctypes and through the compiled C++ mirror (include/ark_hip.hpp).
 pub mod device;
 pub mod domain;
+pub mod fraction_sum;
 pub mod grand_product;
 pub mod mle;
 pub mod msm;
@@ -37,9 +39,10 @@ pub use ark_hip_sys as sys;
 pub use ark_hip_sys::{BLS12_377_G1, BLS12_377_G2, BLS12_381_G1, BLS12_381_G2, BN254_G1};
 pub use device::{DeviceError, DeviceEvaluations, DeviceVec};
 pub use points::DevicePoints;
-pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension, ProductTree, Quotients};
+pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension, FractionTree, ProductTree, Quotients};
 pub use sumcheck::{ListOfProducts, SumcheckProof};
 pub use grand_product::{GrandProduct, GrandProductProof};
+pub use fraction_sum::{FractionalSum, FractionalSumProof};
 pub use msm::{check_bases, compress_bases, decompress_bases, serve_group_coefficients, sw_msm, sw_msm_bigint, BaseCheck, HipServed};
 #[cfg(feature = "ec-hook")]
 pub use msm::{sw_batch_mul, sw_msm_small, sw_normalize_batch};

@@ -93,6 +93,58 @@ pub fn product_tree_plan(num_vars: usize) -> Result<Vec<(usize, usize)>, DeviceE
     Ok((0..passes as usize).map(|p| (widths[p] as usize, groups[p] as usize)).collect())
 }
 
+/// What [`DeviceMultilinearExtension::fraction_tree`] returns: the root `(P, Q)` of the sum of fractions `num[b] / den[b]` and
+/// the two trees that add them, pairing over the LAST variable (`N = n0 d1 + n1 d0`, `D = d0 d1`), each in one device vector
+/// of `2^num_vars - 1` elements in [`ProductTree`]'s layout.  Nothing is inverted.
+pub struct FractionTree<F: FftField> {
+    pub root: (F, F),
+    num_vars: usize,
+    num: DeviceVec<F>,
+    den: DeviceVec<F>,
+}
+impl<F: FftField> FractionTree<F> {
+    pub fn num_vars(&self) -> usize {
+        self.num_vars
+    }
+    pub fn level_offset(&self, j: usize) -> usize {
+        (1usize << self.num_vars) - (2usize << (self.num_vars - j))
+    }
+    pub fn level_len(&self, j: usize) -> usize {
+        1usize << (self.num_vars - j)
+    }
+    /// the numerator tree and the denominator tree
+    pub fn num(&self) -> &DeviceVec<F> {
+        &self.num
+    }
+    pub fn den(&self) -> &DeviceVec<F> {
+        &self.den
+    }
+    fn level_to_vec(&self, all: &DeviceVec<F>, j: usize) -> Result<Vec<F>, DeviceError> {
+        let n = self.level_len(j);
+        let mut out: Vec<F> = Vec::with_capacity(n);
+        let src = unsafe { (all.as_device_ptr() as *const u8).add(32 * self.level_offset(j)) as *const c_void };
+        rc(unsafe { sys::ark_hip_memcpy_d2h(out.as_mut_ptr() as *mut c_void, src, n * 32) })?;
+        unsafe { out.set_len(n) };
+        Ok(out)
+    }
+    pub fn num_level_to_vec(&self, j: usize) -> Result<Vec<F>, DeviceError> {
+        self.level_to_vec(&self.num, j)
+    }
+    pub fn den_level_to_vec(&self, j: usize) -> Result<Vec<F>, DeviceError> {
+        self.level_to_vec(&self.den, j)
+    }
+}
+
+/// The launches of [`DeviceMultilinearExtension::fraction_tree`] as `ark_hip_mle_fraction_tree_plan` reports them: per run of
+/// launches of one kernel variant, (levels, 0).  Host only.
+pub fn fraction_tree_plan(num_vars: usize, has_num: bool) -> Result<Vec<(usize, usize)>, DeviceError> {
+    let (mut passes, mut widths, mut groups) = (0 as core::ffi::c_int, [0 as core::ffi::c_int; 8], [0 as core::ffi::c_int; 8]);
+    rc(unsafe {
+        sys::ark_hip_mle_fraction_tree_plan(num_vars as c_uint, has_num as core::ffi::c_int, &mut passes, widths.as_mut_ptr(), groups.as_mut_ptr())
+    })?;
+    Ok((0..passes as usize).map(|p| (widths[p] as usize, groups[p] as usize)).collect())
+}
+
 fn rc(code: core::ffi::c_int) -> Result<(), DeviceError> {
     if code == 0 { Ok(()) } else { Err(DeviceError::Library(code)) }
 }
@@ -251,6 +303,37 @@ impl<F: FftField> DeviceMultilinearExtension<F> {
                                            g.as_ref().map_or(core::ptr::null(), |x| x.as_ptr()), out.as_device_mut_ptr(), out.len())
         })?;
         Ok(Self { num_vars, evals: out })
+    }
+    /// The tree that adds the fractions `num[b] / self[b]` and its root; `num = None`: every numerator
+    /// is one.  Waits for the root.  The tables are not written.  `Err(Mismatch)` if the sizes differ.
+    pub fn fraction_tree(&self, num: Option<&Self>) -> Result<FractionTree<F>, DeviceError> {
+        self.evals.here()?;
+        if let Some(m) = num {
+            m.evals.here()?;
+            if m.num_vars != self.num_vars {
+                return Err(DeviceError::Mismatch);
+            }
+        }
+        let len = (1usize << self.num_vars) - 1;
+        let (mut nt, mut dt) = (DeviceVec::<F>::alloc(len)?, DeviceVec::<F>::alloc(len)?);
+        let mut out = [0u64; 8];
+        rc(unsafe {
+            sys::ark_hip_mle_fraction_tree_device(self.evals.field(), num.map_or(core::ptr::null(), |m| m.evals.as_device_ptr()),
+                                                  self.evals.as_device_ptr(), self.num_vars as c_uint, nt.as_device_mut_ptr(),
+                                                  dt.as_device_mut_ptr(), out.as_mut_ptr())
+        })?;
+        let (p, q) = ([out[0], out[1], out[2], out[3]], [out[4], out[5], out[6], out[7]]);
+        Ok(FractionTree { root: (sys::from_limbs::<F>(&p), sys::from_limbs::<F>(&q)), num_vars: self.num_vars, num: nt, den: dt })
+    }
+    /// The multiplicity table of a lookup, `m[j] = #{i : indices[i] = j}` for `j < table_len`, counted on the device from `n`
+    /// device `u32`.  An index `>= table_len` is skipped and not reported: the counts sum to `n` exactly when none was skipped.
+    ///
+    /// # Safety
+    /// `d_indices` must point to `n` `u32` in device memory of the current device.
+    pub unsafe fn count_indices(d_indices: *const u32, n: usize, table_len: usize) -> Result<DeviceVec<F>, DeviceError> {
+        let mut out = DeviceVec::<F>::alloc(table_len)?;
+        rc(sys::ark_hip_fr_count_indices_device(out.field(), d_indices, n, out.as_device_mut_ptr(), table_len))?;
+        Ok(out)
     }
     /// `relabel` (dense.rs:195-199): a new polynomial with the `k` variables from `a` and from `b` exchanged.
     pub fn relabel(&self, a: usize, b: usize, k: usize) -> Result<Self, DeviceError> {
