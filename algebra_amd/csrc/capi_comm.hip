@@ -69,12 +69,14 @@ int sums_write_failure(Context* c, char* d_block, int code, MsmSumsHeader* h_out
 // share one plan and out_xyz holds the whole job's result; otherwise the caller takes the fallback.  A scalar-range error on
 // ANY rank is every rank's error.
 int sums_reduce(Context* c, int curve, const MsmSumsHeader& mine, const char* d_blocks, int world, uint64_t* out_xyz, bool* agree) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return ARK_HIP_ERR_ARG;
   const size_t bb = sums_block_bytes(curve), pb = (size_t)CURVES[curve].fe_words * 32;
   char* d_out = (char*)c->comm_sums.p + bb * (size_t)(world + 1);
   MsmSumsHeader* hh = (MsmSumsHeader*)c->comm_sums_pinned + MAX_DEV;   // the gathered headers
   char* h_sums = (char*)((MsmSumsHeader*)c->comm_sums_pinned + 2 * MAX_DEV);
   if (mine.npairs)
-    if (int rc = msm_sum_ranks_dispatch(curve, d_blocks, world, bb, mine.npairs, d_out, c->stream)) return rc;
+    if (int rc = ops->msm_sum_ranks(d_blocks, world, bb, mine.npairs, d_out, c->stream)) return rc;
   ARK_HIP_TRY(hipMemcpy2DAsync(hh, sizeof(MsmSumsHeader), d_blocks, bb, sizeof(MsmSumsHeader), (size_t)world, hipMemcpyDeviceToHost, c->stream));
   if (mine.npairs) ARK_HIP_TRY(hipMemcpyAsync(h_sums, d_out, (size_t)mine.npairs * pb, hipMemcpyDeviceToHost, c->stream));
   if (int rc = comm_sync(c, c->stream)) return rc;   // behind the all-gather: bounded
@@ -93,7 +95,7 @@ int sums_reduce(Context* c, int curve, const MsmSumsHeader& mine, const char* d_
   *agree = same;
   if (err) return ARK_HIP_ERR_SCALAR_RANGE;
   if (!same) return 0;
-  return msm_fold_sums_dispatch(curve, mine, h_sums, out_xyz);
+  return ops->msm_fold_sums(mine, h_sums, out_xyz);
 }
 
 // ---- RCCL, opened at run time ------------------------------------------------------------------------------
@@ -295,8 +297,8 @@ int shard_consts_any(int field, const ark_hip_radix2_domain* dom, int rank, int 
   return ARK_HIP_ERR_ARG;
 }
 // the size-m transform of one rank, twiddle and scalings fused into its first / last pass
-int shard_local(Context* c, int field, const ShardConsts& sc, void* d_local, hipStream_t st) {
-  return fft_dispatch(field, c->fft, d_local, sc.km, sc.root_m, sc.has_pre ? sc.pre : nullptr, sc.has_post ? sc.post : nullptr,
+int shard_local(Context* c, const FieldOps* ops, const ShardConsts& sc, void* d_local, hipStream_t st) {
+  return ops->fft_run(c->fft, d_local, sc.km, sc.root_m, sc.has_pre ? sc.pre : nullptr, sc.has_post ? sc.post : nullptr,
                       sc.has_postc ? sc.postc : nullptr, 0, st, nullptr);
 }
 int comm_streams(Context* c) {
@@ -457,8 +459,10 @@ int ark_hip_fft_shard_local_device(int field, const ark_hip_radix2_domain* dom, 
   if (!dom || !d_local) return ARK_HIP_ERR_ARG;
   ShardConsts k;
   if (int rc = shard_consts_any(field, dom, rank, world, inverse, &k)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = shard_local(sc.c, field, k, d_local, sc.c->stream)) return rc;
+  if (int rc = shard_local(sc.c, ops, k, d_local, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 int ark_hip_fft_shard_cross_device(int field, const ark_hip_radix2_domain* dom, int world, const void* d_src, void* d_dst,
@@ -466,8 +470,10 @@ int ark_hip_fft_shard_cross_device(int field, const ark_hip_radix2_domain* dom, 
   if (!dom || !d_src || !d_dst) return ARK_HIP_ERR_ARG;
   ShardConsts k;
   if (int rc = shard_consts_any(field, dom, 0, world, inverse, &k)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fft_axis_dispatch(field, sc.c->fft, d_src, d_dst, k.G, k.sub, k.root_G, sc.c->stream)) return rc;
+  if (int rc = ops->fft_axis(sc.c->fft, d_src, d_dst, k.G, k.sub, k.root_G, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 int ark_hip_fft_sharded_device(int field, const ark_hip_radix2_domain* dom, void* d_local, int inverse) {
@@ -482,6 +488,8 @@ int ark_hip_fft_sharded_device(int field, const ark_hip_radix2_domain* dom, void
   if (!api) return ARK_HIP_ERR_COMM;
   ShardConsts k;
   if (int rc = shard_consts_any(field, dom, c->comm_rank, c->comm_world, inverse, &k)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
   if (int rc = comm_streams(c)) return rc;
   if (c->comm_tmp.cap < k.m * 32) {
     if (int rc = sync_compute(c)) return rc;
@@ -493,21 +501,21 @@ int ark_hip_fft_sharded_device(int field, const ark_hip_radix2_domain* dom, void
   const int S = comm_slices(k.sub);
   const size_t cs = k.sub / (size_t)S;
   const uint32_t* pw = nullptr;
-  if (int rc = fft_axis_prepare_dispatch(field, c->fft, k.G, k.root_G, c->stream, &pw)) return rc;
+  if (int rc = ops->fft_axis_prepare(c->fft, k.G, k.root_G, c->stream, &pw)) return rc;
   if (!inverse) {
-    if (int rc = shard_local(c, field, k, d_local, c->stream)) return rc;
+    if (int rc = shard_local(c, ops, k, d_local, c->stream)) return rc;
     ARK_HIP_TRY(hipEventRecord(c->comm_ev[0][0], c->stream));
     ARK_HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->comm_ev[0][0], 0));
     for (int i = 0; i < S; i++) {   // slice i+1 travels while the G-point kernel works on slice i
       if (int rc = exchange_slice(c, api, loc, tmp, k.sub, (size_t)i * cs, cs, c->comm_stream)) return rc;
       ARK_HIP_TRY(hipEventRecord(c->comm_ev[1][i], c->comm_stream));
       ARK_HIP_TRY(hipStreamWaitEvent(c->stream, c->comm_ev[1][i], 0));
-      if (int rc = fft_axis_launch_dispatch(field, tmp + (size_t)i * cs * 32, loc + (size_t)i * cs * 32, k.G, k.sub, cs, pw, c->stream))
+      if (int rc = ops->fft_axis_launch(tmp + (size_t)i * cs * 32, loc + (size_t)i * cs * 32, k.G, k.sub, cs, pw, c->stream))
         return rc;
     }
   } else {
     for (int i = 0; i < S; i++) {   // the exchange of slice i travels while the G-point kernel works on slice i+1
-      if (int rc = fft_axis_launch_dispatch(field, loc + (size_t)i * cs * 32, tmp + (size_t)i * cs * 32, k.G, k.sub, cs, pw, c->stream))
+      if (int rc = ops->fft_axis_launch(loc + (size_t)i * cs * 32, tmp + (size_t)i * cs * 32, k.G, k.sub, cs, pw, c->stream))
         return rc;
       ARK_HIP_TRY(hipEventRecord(c->comm_ev[0][i], c->stream));
       ARK_HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->comm_ev[0][i], 0));
@@ -515,7 +523,7 @@ int ark_hip_fft_sharded_device(int field, const ark_hip_radix2_domain* dom, void
     }
     ARK_HIP_TRY(hipEventRecord(c->comm_ev[1][0], c->comm_stream));
     ARK_HIP_TRY(hipStreamWaitEvent(c->stream, c->comm_ev[1][0], 0));
-    if (int rc = shard_local(c, field, k, d_local, c->stream)) return rc;
+    if (int rc = shard_local(c, ops, k, d_local, c->stream)) return rc;
   }
   ARK_HIP_TRY(hipGetLastError());
   return mark_producer(c);

@@ -1,5 +1,6 @@
-// Internals shared by the translation units of the C ABI (capi_runtime / capi_msm / capi_fft / capi_comm / capi_test .hip):
-// the upload staging, the per-device context and its lock, the per-curve / per-field dispatch and the MSM job plumbing.
+// Internals shared by the translation units of the C ABI (capi_runtime / capi_msm / capi_fft / capi_poly / capi_points /
+// capi_comm / capi_test .hip): the upload staging, the per-device context and its lock, the lookup of a curve's / field's
+// operations by id and the MSM job plumbing.
 // Header-only on purpose: every function is `inline` and the few globals are C++17 inline variables, so the units share ONE
 // instance of each without a link-time interface of their own (round 6 split the 3000-line capi.hip: VERDICT r5 weak #10).
 #pragma once
@@ -326,28 +327,38 @@ const CurveInfo CURVES[5] = {
     {6, ARK_HIP_BLS12_377_FR, ARK_HIP_BLS12_377_FQ, 1}, {12, ARK_HIP_BLS12_377_FR, ARK_HIP_BLS12_377_FQ, 2},
     {12, ARK_HIP_BLS12_381_FR, ARK_HIP_BLS12_381_FQ, 2}};
 
-// per-curve dispatch (one translation unit per curve, internal.hpp)
+// The operations of a curve / scalar field by its id (one translation unit each: internal.hpp), nullptr for an id this build
+// does not serve.  Pure host code, no HIP call: an invalid id is reported with no device present.
+inline const CurveOps* curve_ops(int curve) {
+  switch (curve) {
+#ifndef ARK_HIP_DEV   // the development build links BLS12-381 G1 and Fr only
+    case ARK_HIP_BN254_G1: return &curve_ops_BN254_G1();
+    case ARK_HIP_BLS12_377_G1: return &curve_ops_BLS12_377_G1();
+    case ARK_HIP_BLS12_377_G2: return &curve_ops_BLS12_377_G2();
+    case ARK_HIP_BLS12_381_G2: return &curve_ops_BLS12_381_G2();
+#endif
+    case ARK_HIP_BLS12_381_G1: return &curve_ops_BLS12_381_G1();
+  }
+  return nullptr;
+}
+inline const FieldOps* field_ops(int field) {
+  switch (field) {
+#ifndef ARK_HIP_DEV
+    case ARK_HIP_BN254_FR: return &field_ops_BN254_FR();
+    case ARK_HIP_BLS12_377_FR: return &field_ops_BLS12_377_FR();
+#endif
+    case ARK_HIP_BLS12_381_FR: return &field_ops_BLS12_381_FR();
+  }
+  return nullptr;
+}
+// host-math templates by field id (capi_hostmath.hpp, capi_poly.hip): CALL(NAME) for the field, ARK_HIP_ERR_ARG otherwise
 #ifdef ARK_HIP_DEV
-#define ARK_CURVE_SWITCH(curve, CALL)                         \
-  switch (curve) {                                            \
-    case ARK_HIP_BLS12_381_G1: return CALL(BLS12_381_G1);     \
-  }                                                           \
-  return ARK_HIP_ERR_ARG
 #define ARK_FIELD_SWITCH(field, CALL)                         \
   switch (field) {                                            \
     case ARK_HIP_BLS12_381_FR: return CALL(BLS12_381_FR);     \
   }                                                           \
   return ARK_HIP_ERR_ARG
 #else
-#define ARK_CURVE_SWITCH(curve, CALL)                         \
-  switch (curve) {                                            \
-    case ARK_HIP_BN254_G1: return CALL(BN254_G1);             \
-    case ARK_HIP_BLS12_381_G1: return CALL(BLS12_381_G1);     \
-    case ARK_HIP_BLS12_377_G1: return CALL(BLS12_377_G1);     \
-    case ARK_HIP_BLS12_377_G2: return CALL(BLS12_377_G2);     \
-    case ARK_HIP_BLS12_381_G2: return CALL(BLS12_381_G2);     \
-  }                                                           \
-  return ARK_HIP_ERR_ARG
 #define ARK_FIELD_SWITCH(field, CALL)                         \
   switch (field) {                                            \
     case ARK_HIP_BN254_FR: return CALL(BN254_FR);             \
@@ -356,105 +367,6 @@ const CurveInfo CURVES[5] = {
   }                                                           \
   return ARK_HIP_ERR_ARG
 #endif
-
-inline int msm_enqueue_dispatch(int curve, MsmWorkspace& ws, const void* pts, size_t wstride, const MsmPlan* prep, const void* s,
-                         size_t n, int mont, hipStream_t st, bool timing, int sbytes = 0, int sbits = 0,
-                         const MsmPiece* piece = nullptr) {
-#define X(NAME) msm_enqueue_##NAME(ws, pts, wstride, prep, s, n, mont, st, timing, sbytes, sbits, piece)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int msm_finish_dispatch(int curve, MsmWorkspace& ws, int slot, uint64_t* out, MsmTimings* tm) {
-#define X(NAME) msm_finish_##NAME(ws, slot, out, tm)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int msm_sum_ranks_dispatch(int curve, const void* d_blocks, int world, size_t block_bytes, uint32_t npairs, void* d_out, hipStream_t st) {
-#define X(NAME) msm_sum_ranks_##NAME(d_blocks, world, block_bytes, npairs, d_out, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int msm_fold_sums_dispatch(int curve, const MsmSumsHeader& h, const void* h_sums, uint64_t* out_xyz) {
-#define X(NAME) msm_fold_sums_##NAME(h, h_sums, out_xyz)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int msm_sample_widths_dispatch(int curve, const void* h_scalars, size_t n, int mont, MsmWidths* out) {
-#define X(NAME) (msm_sample_widths_##NAME(h_scalars, n, mont, out), 0)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int msm_prepare_dispatch(int curve, const void* d_bases, size_t n, const MsmPlan& pl, void* d_table, void* d_tmp, hipStream_t st) {
-#define X(NAME) msm_prepare_##NAME(d_bases, n, pl, d_table, d_tmp, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int batchmul_build_dispatch(int curve, const void* h_base, int window, void* d_scratch, void* d_table, hipStream_t st) {
-#define X(NAME) batchmul_build_##NAME(h_base, window, d_scratch, d_table, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline long long batchmul_build_scratch_dispatch(int curve, int window) {   // bytes; < 0: unknown curve
-#define X(NAME) (long long)batchmul_build_scratch_##NAME(window)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int batchmul_run_dispatch(int curve, const void* d_table, int window, const void* d_scalars, size_t n, int mont, void* d_tmp, void* d_out, hipStream_t st) {
-#define X(NAME) batchmul_run_##NAME(d_table, window, d_scalars, n, mont, d_tmp, d_out, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int fft_dispatch(int field, FftWorkspace& ws, void* d, int k, const uint64_t* root, const uint64_t* pre,
-                 const uint64_t* post, const uint64_t* postc, int zlog, hipStream_t st, FftTimings* tm) {
-#define X(NAME) fft_run_##NAME(ws, d, k, root, pre, post, postc, zlog, st, tm)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-typedef int (*elementwise_fn)(int, const void*, const void*, void*, size_t, hipStream_t);
-inline int add_affine_dispatch(int curve, const void* in, void* out, size_t n, const void* d_delta, hipStream_t st) {
-#define X(NAME) sw_add_affine_##NAME(in, out, n, d_delta, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int normalize_dispatch(int curve, const void* in, void* out, size_t n, hipStream_t st) {
-#define X(NAME) sw_normalize_batch_##NAME(in, out, n, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int sw_check_dispatch(int curve, const void* in, size_t n, size_t base, int checks, int method, void* d_status, void* d_out,
-                             hipStream_t st) {
-#define X(NAME) sw_check_##NAME(in, n, base, checks, method, d_status, d_out, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int sw_decompress_dispatch(int curve, const void* d_bytes, size_t n, size_t base, int validate, int method, void* d_points,
-                                  void* d_status, void* d_out, hipStream_t st) {
-#define X(NAME) sw_decompress_##NAME(d_bytes, n, base, validate, method, d_points, d_status, d_out, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int sw_compress_dispatch(int curve, const void* d_points, size_t n, void* d_bytes, hipStream_t st) {
-#define X(NAME) sw_compress_##NAME(d_points, n, d_bytes, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int sw_vec_mul_dispatch(int curve, const void* d_points, int form, const void* d_scalars, size_t kstride, int mont, size_t n,
-                               void* d_out, void* d_tab, size_t slab, hipStream_t st) {
-#define X(NAME) sw_vec_mul_##NAME(d_points, form, d_scalars, kstride, mont, n, d_out, d_tab, slab, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int sw_vec_fold_dispatch(int curve, const void* d_lo, const void* d_hi, int form, const uint64_t* a4, const uint64_t* b4, int mont,
-                                size_t n, void* d_out, void* d_tab, size_t slab, hipStream_t st) {
-#define X(NAME) sw_vec_fold_##NAME(d_lo, d_hi, form, a4, b4, mont, n, d_out, d_tab, slab, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline int sw_vec_add_dispatch(int curve, const void* d_a, const void* d_b, int negate_b, size_t n, void* d_out, hipStream_t st) {
-#define X(NAME) sw_vec_add_##NAME(d_a, d_b, negate_b, n, d_out, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
 // points per staged chunk of a host-slice entry: 64 MiB of points (ab bytes each) unless the environment variable `env` holds a
 // positive count (the tests cross chunk seams at small sizes with it); never more than n
 inline size_t stage_chunk_points(const char* env, size_t ab, size_t n) {
@@ -465,150 +377,7 @@ inline size_t stage_chunk_points(const char* env, size_t ab, size_t n) {
   }
   return chunk > n ? n : chunk;
 }
-inline int fr_mul_dispatch(int field, const void* a, const void* b, void* r, size_t n, hipStream_t st) {
-#define X(NAME) field_op_##NAME(2, a, b, r, n, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fr_scale_dispatch(int field, const void* a, const uint64_t* k4, void* r, size_t n, hipStream_t st) {
-#define X(NAME) fr_scale_##NAME(a, k4, r, n, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
 inline bool field_is_one(int field, const uint64_t* x);
-inline int fft_roots_dispatch(int field, FftWorkspace& ws, int k, const uint64_t* root4, hipStream_t st, const uint32_t** out) {
-#define X(NAME) fft_roots_##NAME(ws, k, root4, st, out)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fft_scalars_dispatch(int field, FftWorkspace& ws, const uint64_t* base4, const uint64_t* mul4, size_t count, void* d_out,
-                         hipStream_t st) {
-#define X(NAME) fft_scalars_##NAME(ws, base4, mul4, count, d_out, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int gfft_run_dispatch(int curve, void* d_jac, int k, const uint32_t* roots, const uint32_t* pre, const uint32_t* post, void* work,
-                      hipStream_t st) {
-#define X(NAME) gfft_run_##NAME(d_jac, k, roots, pre, post, work, st)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
-}
-inline size_t gfft_work_bytes_any(int curve, int k) {
-  switch (curve) {
-#ifndef ARK_HIP_DEV
-    case ARK_HIP_BN254_G1: return gfft_work_bytes_BN254_G1(k);
-    case ARK_HIP_BLS12_377_G1: return gfft_work_bytes_BLS12_377_G1(k);
-    case ARK_HIP_BLS12_377_G2: return gfft_work_bytes_BLS12_377_G2(k);
-    case ARK_HIP_BLS12_381_G2: return gfft_work_bytes_BLS12_381_G2(k);
-#endif
-    case ARK_HIP_BLS12_381_G1: return gfft_work_bytes_BLS12_381_G1(k);
-  }
-  return 0;
-}
-inline int fr_div_dispatch(int field, const void* num, const void* den, void* r, size_t n, hipStream_t st) {
-#define X(NAME) fr_div_##NAME(num, den, r, n, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int poly_tile_value_dispatch(int field, const void* src, size_t n, const PolyPowers& pw, void* vals, hipStream_t st) {
-#define X(NAME) poly_tile_value_##NAME(src, n, pw, vals, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int poly_tile_divide_dispatch(int field, const void* src, size_t n, const PolyPowers& pw, const void* carries, void* dst,
-                                     void* rem, hipStream_t st) {
-#define X(NAME) poly_tile_divide_##NAME(src, n, pw, carries, dst, rem, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int poly_vanishing_dispatch(int field, const void* p, size_t n, size_t m, void* q, void* r, hipStream_t st) {
-#define X(NAME) poly_vanishing_##NAME(p, n, m, q, r, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int poly_lagrange_dispatch(int field, const uint64_t* a4, const uint64_t* c4, const uint64_t* w4, const uint64_t* wstep4,
-                                  int onehot, void* out, size_t n, size_t lanes, hipStream_t st) {
-#define X(NAME) poly_lagrange_##NAME(a4, c4, w4, wstep4, onehot, out, n, lanes, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fr_inner_product_dispatch(int field, const void* a, const void* b, size_t n, void* partials, void* out, hipStream_t st) {
-#define X(NAME) fr_inner_product_##NAME(a, b, n, partials, out, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int mle_fold_dispatch(int field, const void* src, int log_n, int w, const MlePoint& pt, void* dst, hipStream_t st) {
-#define X(NAME) mle_fold_##NAME(src, log_n, w, pt, dst, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int mle_relabel_dispatch(int field, const void* src, size_t n, int a, int b, int k, void* dst, hipStream_t st) {
-#define X(NAME) mle_relabel_##NAME(src, n, a, b, k, dst, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fr_axpy_dispatch(int field, const void* a, const uint64_t* k4, const void* x, void* r, size_t n, hipStream_t st) {
-#define X(NAME) fr_axpy_##NAME(a, k4, x, r, n, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int mle_eq_dispatch(int field, const void* hi, const FrConst& top, int unit, const MlePoint& pt, int log_n, void* dst, hipStream_t st) {
-#define X(NAME) mle_eq_##NAME(hi, top, unit, pt, log_n, dst, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int mle_quot_dispatch(int field, const void* src, int log_n, int w, const MlePoint& pt, void* quot, void* dst, hipStream_t st) {
-#define X(NAME) mle_quot_##NAME(src, log_n, w, pt, quot, dst, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int prod_tree_dispatch(int field, const void* src, int log_n, int w, void* dst, hipStream_t st) {
-#define X(NAME) prod_tree_##NAME(src, log_n, w, dst, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fr_lincomb_dispatch(int field, const FrLincomb& lc, void* out, size_t n, hipStream_t st) {
-#define X(NAME) fr_lincomb_##NAME(lc, out, n, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int frac_tree_dispatch(int field, const void* nsrc, const void* dsrc, int log_n, int w, void* ndst, void* ddst, hipStream_t st) {
-#define X(NAME) frac_tree_##NAME(nsrc, dsrc, log_n, w, ndst, ddst, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fr_count_dispatch(int field, const void* indices, size_t n, void* out, size_t table_len, hipStream_t st) {
-#define X(NAME) fr_count_##NAME(indices, n, out, table_len, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int sumcheck_round_dispatch(int field, const SumcheckRound& rd, hipStream_t st) {
-#define X(NAME) sumcheck_round_##NAME(rd, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fr_op_dispatch(int field, int op, const void* a, const void* b, void* r, size_t n, hipStream_t st) {
-#define X(NAME) field_op_##NAME(op, a, b, r, n, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fft_axis_dispatch(int field, FftWorkspace& ws, const void* src, void* dst, unsigned G, size_t cols, const uint64_t* root,
-                      hipStream_t st) {
-#define X(NAME) fft_axis_##NAME(ws, src, dst, G, cols, root, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fft_axis_prepare_dispatch(int field, FftWorkspace& ws, unsigned G, const uint64_t* root, hipStream_t st, const uint32_t** pw) {
-#define X(NAME) fft_axis_prepare_##NAME(ws, G, root, st, pw)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
-inline int fft_axis_launch_dispatch(int field, const void* src, void* dst, unsigned G, size_t stride, size_t cols, const uint32_t* pw,
-                             hipStream_t st) {
-#define X(NAME) fft_axis_launch_##NAME(src, dst, G, stride, cols, pw, st)
-  ARK_FIELD_SWITCH(field, X);
-#undef X
-}
 
 // ---- MSM plumbing shared by the entry points ----------------------------------------------------------
 struct PreparedBases {   // ark_hip_msm_bases: a fixed base set with its table of per-window multiples
@@ -669,8 +438,9 @@ inline int msm_enqueue_ctx(Context* c, int curve, const void* pts, size_t wstrid
   // producing this job's scalars: the second lane starts behind the last of them (mark_producer), while lane 0's own MSM
   // kernels -- which lane 1 exists to overlap -- are not waited for
   if (lane && c->lane_ev_set) ARK_HIP_TRY(hipStreamWaitEvent(st, c->lane_ev, 0));
-  int slot = msm_enqueue_dispatch(curve, c->msm[lane], pts, wstride, prep, d_scalars, n, mont, st, c->msm_timing, sbytes, sbits,
-                                  piece);
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  int slot = ops->msm_enqueue(c->msm[lane], pts, wstride, prep, d_scalars, n, mont, st, c->msm_timing, sbytes, sbits, piece);
   return slot < 0 ? slot : lane * MSM_JOBS + slot;
 }
 // Called WITHOUT the context lock by ark_hip_msm_wait -- it takes no lock but the lane's and the slot mutex, so a job can always
@@ -679,7 +449,8 @@ inline int msm_enqueue_ctx(Context* c, int curve, const void* pts, size_t wstrid
 inline int msm_finish_ctx(Context* c, int curve, int slot, uint64_t* out) {
   if (slot < 0 || slot >= 2 * MSM_JOBS) return ARK_HIP_ERR_ARG;
   MsmTimings tm;
-  const int rc = msm_finish_dispatch(curve, c->msm[slot / MSM_JOBS], slot % MSM_JOBS, out, &tm);
+  const CurveOps* ops = curve_ops(curve);
+  const int rc = ops ? ops->msm_finish(c->msm[slot / MSM_JOBS], slot % MSM_JOBS, out, &tm) : ARK_HIP_ERR_ARG;
   {   // the slot is free again
     std::lock_guard<std::mutex> sl(c->slot_mu);
     c->slot_gen.fetch_add(1, std::memory_order_release);

@@ -117,7 +117,9 @@ int ark_hip_fft_batch_in_place_device(int field, const ark_hip_radix2_domain* do
 int ark_hip_fr_mul_device(int field, const void* d_a, const void* d_b, void* d_r, size_t n) {
   if (n && (!d_a || !d_b || !d_r)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fr_mul_dispatch(field, d_a, d_b, d_r, n, sc.c->stream)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  if (int rc = ops->field_op(2, d_a, d_b, d_r, n, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 
@@ -143,6 +145,8 @@ int ark_hip_poly_mul(int field, const uint64_t* a, size_t na, const uint64_t* b,
   const size_t len = na + nb - 1;
   ark_hip_radix2_domain dom;
   if (int rc = ark_hip_radix2_domain_new(field, len, &dom)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
   const size_t n = (size_t)dom.size;
   ARK_SCOPE(sc);
   Context* c = sc.c;
@@ -170,7 +174,7 @@ int ark_hip_poly_mul(int field, const uint64_t* a, size_t na, const uint64_t* b,
   if (rc == 0) rc = fft_any(c, field, &dom, c->stage_b.p, 0, zb, c->fft_side[0]);
   (void)hipEventRecord(c->fft_ev[1], c->fft_side[0]);
   (void)hipStreamWaitEvent(c->stream, c->fft_ev[1], 0);
-  if (rc == 0) rc = fr_mul_dispatch(field, c->stage_a.p, c->stage_b.p, c->stage_a.p, n, c->stream);
+  if (rc == 0) rc = ops->field_op(2, c->stage_a.p, c->stage_b.p, c->stage_a.p, n, c->stream);
   if (rc == 0) rc = fft_any(c, field, &dom, c->stage_a.p, 1, 0, c->stream);
   if (rc) {
     (void)hipStreamSynchronize(c->stream);
@@ -201,7 +205,9 @@ int ark_hip_fr_pow(int field, const uint64_t* base, uint64_t exp, uint64_t* out)
 int ark_hip_fft_axis_device(int field, void* d_data, unsigned G, size_t cols, const uint64_t* root) {
   if (!d_data || !root) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fft_axis_dispatch(field, sc.c->fft, d_data, d_data, G, cols, root, sc.c->stream)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  if (int rc = ops->fft_axis(sc.c->fft, d_data, d_data, G, cols, root, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 
@@ -213,6 +219,9 @@ int ark_hip_fft_axis_device(int field, void* d_data, unsigned G, size_t cols, co
 // resize does.  gfft.cuh.
 static int gfft_entry(Context* c, int curve, const ark_hip_radix2_domain* dom, void* d_jac, int inverse) {
   const int field = CURVES[curve].scalar_field;
+  const CurveOps* ops = curve_ops(curve);
+  const FieldOps* fops = field_ops(field);
+  if (!ops || !fops) return ARK_HIP_ERR_ARG;
   const int k = (int)dom->log_size_of_group;
   if (k < 0 || k > 26 || dom->size != ((uint64_t)1 << k)) return ARK_HIP_ERR_ARG;
   if (!domain_is_of_field(field, dom)) return ARK_HIP_ERR_ARG;   // a domain of another scalar field than the curve's
@@ -220,22 +229,22 @@ static int gfft_entry(Context* c, int curve, const ark_hip_radix2_domain* dom, v
   const bool coset = !field_is_one(field, dom->offset);
   const uint32_t* roots = nullptr;
   if (k >= 1)
-    if (int rc = fft_roots_dispatch(field, c->fft, k, inverse ? dom->group_gen_inv : dom->group_gen, c->stream, &roots)) return rc;
-  const size_t wb = gfft_work_bytes_any(curve, k);
+    if (int rc = fops->fft_roots(c->fft, k, inverse ? dom->group_gen_inv : dom->group_gen, c->stream, &roots)) return rc;
+  const size_t wb = ops->gfft_work_bytes(k);
   if (wb == 0) return ARK_HIP_ERR_ARG;
   if (c->gfft_work.cap < wb || c->gfft_scal.cap < n * 32)
     if (int rc = sync_compute(c)) return rc;
   if (c->gfft_work.ensure(wb) || c->gfft_scal.ensure(n * 32)) return ARK_HIP_ERR_NOMEM;
   const uint32_t *pre = nullptr, *post = nullptr;
   if (!inverse && coset) {        // distribute_powers(coeffs, offset)                                   fft.rs:74-79
-    if (int rc = fft_scalars_dispatch(field, c->fft, dom->offset, nullptr, n, c->gfft_scal.p, c->stream)) return rc;
+    if (int rc = fops->fft_scalars(c->fft, dom->offset, nullptr, n, c->gfft_scal.p, c->stream)) return rc;
     pre = (const uint32_t*)c->gfft_scal.p;
   }
   if (inverse) {                  // x[i] *= size_inv * offset_inv^i  (offset_inv = 1 off a coset)         fft.rs:81-88
-    if (int rc = fft_scalars_dispatch(field, c->fft, dom->offset_inv, dom->size_inv, n, c->gfft_scal.p, c->stream)) return rc;
+    if (int rc = fops->fft_scalars(c->fft, dom->offset_inv, dom->size_inv, n, c->gfft_scal.p, c->stream)) return rc;
     post = (const uint32_t*)c->gfft_scal.p;
   }
-  if (int rc = gfft_run_dispatch(curve, d_jac, k, roots, pre, post, c->gfft_work.p, c->stream)) return rc;
+  if (int rc = ops->gfft_run(d_jac, k, roots, pre, post, c->gfft_work.p, c->stream)) return rc;
   return mark_producer(c);
 }
 int ark_hip_fft_group_in_place_device(int curve, const ark_hip_radix2_domain* dom, void* d_jac_points, int inverse) {
@@ -269,26 +278,34 @@ int ark_hip_fft_group_in_place(int curve, const ark_hip_radix2_domain* dom, uint
 int ark_hip_fr_add_device(int field, const void* d_a, const void* d_b, void* d_r, size_t n) {
   if (n && (!d_a || !d_b || !d_r)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fr_op_dispatch(field, 0, d_a, d_b, d_r, n, sc.c->stream)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  if (int rc = ops->field_op(0, d_a, d_b, d_r, n, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 int ark_hip_fr_sub_device(int field, const void* d_a, const void* d_b, void* d_r, size_t n) {
   if (n && (!d_a || !d_b || !d_r)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fr_op_dispatch(field, 1, d_a, d_b, d_r, n, sc.c->stream)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  if (int rc = ops->field_op(1, d_a, d_b, d_r, n, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 int ark_hip_fr_neg_device(int field, const void* d_a, void* d_r, size_t n) {
   if (n && (!d_a || !d_r)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fr_op_dispatch(field, 4, d_a, nullptr, d_r, n, sc.c->stream)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  if (int rc = ops->field_op(4, d_a, nullptr, d_r, n, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 // r[i] = a[i] * k; k: one Montgomery element in HOST memory, read before the call returns
 int ark_hip_fr_scale_device(int field, const void* d_a, const uint64_t* k, void* d_r, size_t n) {
   if (!k || (n && (!d_a || !d_r))) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fr_scale_dispatch(field, d_a, k, d_r, n, sc.c->stream)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  if (int rc = ops->fr_scale(d_a, k, d_r, n, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 // r[i] = a[i] / b[i] (Evaluations /= Evaluations, evaluations/univariate/mod.rs:142-163) and r[i] = 1 / a[i]
@@ -297,13 +314,17 @@ int ark_hip_fr_scale_device(int field, const void* d_a, const uint64_t* k, void*
 int ark_hip_fr_div_device(int field, const void* d_a, const void* d_b, void* d_r, size_t n) {
   if (n && (!d_a || !d_b || !d_r)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fr_div_dispatch(field, d_a, d_b, d_r, n, sc.c->stream)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  if (int rc = ops->fr_div(d_a, d_b, d_r, n, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 int ark_hip_fr_inverse_device(int field, const void* d_a, void* d_r, size_t n) {
   if (n && (!d_a || !d_r)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  if (int rc = fr_div_dispatch(field, nullptr, d_a, d_r, n, sc.c->stream)) return rc;
+  const FieldOps* ops = field_ops(field);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  if (int rc = ops->fr_div(nullptr, d_a, d_r, n, sc.c->stream)) return rc;
   return mark_producer(sc.c);
 }
 // device-to-device copy / byte fill on the context stream (a device vector's clone() and its zero-extension), ordered with

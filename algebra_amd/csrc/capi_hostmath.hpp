@@ -185,14 +185,14 @@ int fft_entry(Context* c, const ark_hip_radix2_domain* dom, void* d_data, int in
   FftTimings* tm = (c->fft_timing && st == c->stream) ? &c->fft_tm : nullptr;
   int k = (int)dom->log_size_of_group;
   if (dom->size != ((uint64_t)1 << k)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(FP::ID);
+  if (!ops) return ARK_HIP_ERR_ARG;
   if (!inverse) {
     // fft.rs:74-79: distribute_powers(offset) then DIF + derange
-    return fft_dispatch(FP::ID, c->fft, d_data, k, dom->group_gen, coset ? dom->offset : nullptr, nullptr, nullptr, zlog,
-                        st, tm);
+    return ops->fft_run(c->fft, d_data, k, dom->group_gen, coset ? dom->offset : nullptr, nullptr, nullptr, zlog, st, tm);
   }
   // fft.rs:81-88: transform with group_gen_inv, then x[i] *= size_inv * offset_inv^i
-  return fft_dispatch(FP::ID, c->fft, d_data, k, dom->group_gen_inv, nullptr, coset ? dom->offset_inv : nullptr,
-                      dom->size_inv, 0, st, tm);
+  return ops->fft_run(c->fft, d_data, k, dom->group_gen_inv, nullptr, coset ? dom->offset_inv : nullptr, dom->size_inv, 0, st, tm);
 }
 
 inline int fft_any(Context* c, int field, const ark_hip_radix2_domain* dom, void* d_data, int inverse, int zlog,

@@ -318,7 +318,8 @@ int ark_hip_msm_last_timing(double out[8]) {
 
 // ---- prepared base sets (fixed SRS) ----
 int ark_hip_msm_bases_prepare_device(int curve, const void* d_bases, size_t n, ark_hip_msm_bases** out) {
-  if (curve < 0 || curve > 4 || !out || (n && !d_bases)) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !out || (n && !d_bases)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
   PreparedBases* pb = new PreparedBases();
@@ -334,7 +335,7 @@ int ark_hip_msm_bases_prepare_device(int curve, const void* d_bases, size_t n, a
     }
     DevBuf tmp;  // one unnormalised (XYZZ) row: twice an affine row, released once the table stands
     int rc = tmp.ensure(2 * row) ? ARK_HIP_ERR_NOMEM : 0;
-    if (rc == 0) rc = msm_prepare_dispatch(curve, d_bases, n, pb->plan, pb->table.p, tmp.p, c->stream);
+    if (rc == 0) rc = ops->msm_prepare(d_bases, n, pb->plan, pb->table.p, tmp.p, c->stream);
     if (rc == 0 && hipStreamSynchronize(c->stream) != hipSuccess) rc = -1000;
     else if (rc) (void)hipStreamSynchronize(c->stream);
     tmp.release();
@@ -557,7 +558,8 @@ int ark_hip_msm_prepared_multi(int n_gpus, const ark_hip_msm_bases* const* shard
 int ark_hip_batch_mul_table_new(int curve, const uint64_t* base_xyz, size_t num_scalars, ark_hip_batch_mul_table** out) {
   // the reference sizes its window from num_scalars (:222-228); so does the device table, by its own cost rule
   // (batchmul.cuh batchmul_window)
-  if (curve < 0 || curve > 4 || !base_xyz || !out) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !base_xyz || !out) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
   const size_t ab = (size_t)CURVES[curve].fe_words * 16;
@@ -569,11 +571,11 @@ int ark_hip_batch_mul_table_new(int curve, const uint64_t* base_xyz, size_t num_
   t->logical = c->logical;
   t->window = batchmul_window(num_scalars);
   const size_t entries = (size_t)batchmul_outer(t->window) << t->window;
-  if (t->table.ensure(entries * ab) || c->stage_c.ensure((size_t)batchmul_build_scratch_dispatch(curve, t->window))) {
+  if (t->table.ensure(entries * ab) || c->stage_c.ensure(ops->batchmul_build_scratch(t->window))) {
     delete t;
     return ARK_HIP_ERR_NOMEM;
   }
-  rc = batchmul_build_dispatch(curve, aff, t->window, c->stage_c.p, t->table.p, c->stream);
+  rc = ops->batchmul_build(aff, t->window, c->stage_c.p, t->table.p, c->stream);
   if (rc == 0 && hipStreamSynchronize(c->stream) != hipSuccess) rc = -1000;
   if (rc) {
     (void)hipStreamSynchronize(c->stream);
@@ -601,7 +603,9 @@ int ark_hip_batch_mul_device(const ark_hip_batch_mul_table* table, const void* d
   if (int rc = sc.enter(t->logical)) return rc;
   if (n == 0) return 0;
   if (sc.c->stage_c.ensure(n * 2 * (size_t)CURVES[t->curve].fe_words * 16)) return ARK_HIP_ERR_NOMEM;  // XYZZ scratch
-  int rc = batchmul_run_dispatch(t->curve, t->table.p, t->window, d_scalars, n, mont, sc.c->stage_c.p, d_out_xy, sc.c->stream);
+  const CurveOps* ops = curve_ops(t->curve);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  int rc = ops->batchmul_run(t->table.p, t->window, d_scalars, n, mont, sc.c->stage_c.p, d_out_xy, sc.c->stream);
   if (rc) return rc;
   ARK_HIP_TRY(hipStreamSynchronize(sc.c->stream));
   return 0;
@@ -616,7 +620,9 @@ int ark_hip_batch_mul(const ark_hip_batch_mul_table* table, const uint64_t* scal
   if (n == 0) return 0;
   if (c->stage_a.ensure(n * 32) || c->stage_b.ensure(n * ab) || c->stage_c.ensure(n * 2 * ab)) return ARK_HIP_ERR_NOMEM;
   ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
-  int rc = batchmul_run_dispatch(t->curve, t->table.p, t->window, c->stage_a.p, n, mont, c->stage_c.p, c->stage_b.p, c->stream);
+  const CurveOps* ops = curve_ops(t->curve);
+  if (!ops) return ARK_HIP_ERR_ARG;
+  int rc = ops->batchmul_run(t->table.p, t->window, c->stage_a.p, n, mont, c->stage_c.p, c->stage_b.p, c->stream);
   if (rc) return rc;
   ARK_HIP_TRY(hipMemcpyAsync(out_xy, c->stage_b.p, n * ab, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));

@@ -35,7 +35,7 @@ int tables(Context* c, int curve, int nt, size_t n, size_t* slab) {
 }
 int mul_args(int curve, const void* points, int form, const void* scalars, size_t n_scalars, int mont, size_t n, const void* out,
              bool device) {
-  if (curve < 0 || curve > 4 || (form != ARK_HIP_FORM_AFFINE && form != ARK_HIP_FORM_PROJECTIVE) || mont < 0 || mont > 1)
+  if (!curve_ops(curve) || (form != ARK_HIP_FORM_AFFINE && form != ARK_HIP_FORM_PROJECTIVE) || mont < 0 || mont > 1)
     return ARK_HIP_ERR_ARG;
   if (n == 0) return n_scalars <= 1 ? 0 : ARK_HIP_ERR_ARG;
   if (n_scalars != 1 && n_scalars != n) return ARK_HIP_ERR_ARG;
@@ -54,11 +54,12 @@ int ark_hip_sw_mul_device(int curve, const void* d_points, int form, const void*
                           size_t n, void* d_out_xyz) {
   if (int rc = mul_args(curve, d_points, form, d_scalars, n_scalars, scalars_are_montgomery, n, d_out_xyz, true)) return rc;
   if (n == 0) return 0;
+  const CurveOps* ops = curve_ops(curve);   // served: mul_args
   ARK_SCOPE(sc);
   Context* c = sc.c;
   size_t slab = 0;
   if (int rc = tables(c, curve, 1, n, &slab)) return rc;
-  return sw_vec_mul_dispatch(curve, d_points, form, d_scalars, n_scalars == 1 && n != 1 ? 0 : 8, scalars_are_montgomery, n, d_out_xyz,
+  return ops->sw_vec_mul(d_points, form, d_scalars, n_scalars == 1 && n != 1 ? 0 : 8, scalars_are_montgomery, n, d_out_xyz,
                              c->pointvec_work.p, slab, c->stream);
 }
 
@@ -68,6 +69,7 @@ int ark_hip_sw_mul(int curve, const uint64_t* points, int form, const uint64_t* 
                    size_t n, uint64_t* out_xyz) {
   if (int rc = mul_args(curve, points, form, scalars, n_scalars, scalars_are_montgomery, n, out_xyz, false)) return rc;
   if (n == 0) return 0;
+  const CurveOps* ops = curve_ops(curve);   // served: mul_args
   ARK_SCOPE(sc);
   Context* c = sc.c;
   const size_t pb = point_bytes(curve, form), ob = point_bytes(curve, ARK_HIP_FORM_PROJECTIVE);
@@ -86,7 +88,7 @@ int ark_hip_sw_mul(int curve, const uint64_t* points, int form, const uint64_t* 
     if (int rc = c->stager.upload(c->stage_a.p, (const char*)points + off * pb, m * pb, c->stream)) return rc;
     if (!shared)
       if (int rc = c->stager.upload(c->stage_b.p, (const char*)scalars + off * 32, m * 32, c->stream)) return rc;
-    if (int rc = sw_vec_mul_dispatch(curve, c->stage_a.p, form, c->stage_b.p, shared ? 0 : 8, scalars_are_montgomery, m, c->stage_c.p,
+    if (int rc = ops->sw_vec_mul(c->stage_a.p, form, c->stage_b.p, shared ? 0 : 8, scalars_are_montgomery, m, c->stage_c.p,
                                      c->pointvec_work.p, slab, c->stream))
       return rc;
     ARK_HIP_TRY(hipMemcpyAsync((char*)out_xyz + off * ob, c->stage_c.p, m * ob, hipMemcpyDeviceToHost, c->stream));
@@ -97,19 +99,21 @@ int ark_hip_sw_mul(int curve, const uint64_t* points, int form, const uint64_t* 
 
 // asynchronous on the context stream
 int ark_hip_sw_add_device(int curve, const void* d_a_xyz, const void* d_b_xyz, int negate_b, size_t n, void* d_out_xyz) {
-  if (curve < 0 || curve > 4 || negate_b < 0 || negate_b > 1) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || negate_b < 0 || negate_b > 1) return ARK_HIP_ERR_ARG;
   if (n == 0) return 0;
   if (!d_a_xyz || !d_b_xyz || !d_out_xyz || !aligned16(d_a_xyz) || !aligned16(d_b_xyz) || !aligned16(d_out_xyz)) return ARK_HIP_ERR_ARG;
   if (!out_ok(curve, d_a_xyz, ARK_HIP_FORM_PROJECTIVE, d_out_xyz, n) || !out_ok(curve, d_b_xyz, ARK_HIP_FORM_PROJECTIVE, d_out_xyz, n))
     return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  return sw_vec_add_dispatch(curve, d_a_xyz, d_b_xyz, negate_b, n, d_out_xyz, sc.c->stream);
+  return ops->sw_vec_add(d_a_xyz, d_b_xyz, negate_b, n, d_out_xyz, sc.c->stream);
 }
 
 // asynchronous on the context stream (a and b are read before the call returns: they travel as kernel arguments)
 int ark_hip_sw_fold_device(int curve, const void* d_lo, const void* d_hi, int form, const uint64_t a[4], const uint64_t b[4],
                            int scalars_are_montgomery, size_t n, void* d_out_xyz) {
-  if (curve < 0 || curve > 4 || (form != ARK_HIP_FORM_AFFINE && form != ARK_HIP_FORM_PROJECTIVE) || scalars_are_montgomery < 0 ||
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || (form != ARK_HIP_FORM_AFFINE && form != ARK_HIP_FORM_PROJECTIVE) || scalars_are_montgomery < 0 ||
       scalars_are_montgomery > 1 || !a || !b)
     return ARK_HIP_ERR_ARG;
   if (n == 0) return 0;
@@ -119,7 +123,7 @@ int ark_hip_sw_fold_device(int curve, const void* d_lo, const void* d_hi, int fo
   Context* c = sc.c;
   size_t slab = 0;
   if (int rc = tables(c, curve, 2, n, &slab)) return rc;
-  return sw_vec_fold_dispatch(curve, d_lo, d_hi, form, a, b, scalars_are_montgomery, n, d_out_xyz, c->pointvec_work.p, slab, c->stream);
+  return ops->sw_vec_fold(d_lo, d_hi, form, a, b, scalars_are_montgomery, n, d_out_xyz, c->pointvec_work.p, slab, c->stream);
 }
 
 }  // extern "C"

@@ -19,9 +19,6 @@ namespace {
 
 constexpr int POLY_MAX_LEVELS = 8;   // 2048^6 > 2^64
 
-inline bool field_served(int field) {
-  return field == ARK_HIP_BN254_FR || field == ARK_HIP_BLS12_381_FR || field == ARK_HIP_BLS12_377_FR;
-}
 template <class FP>
 FrConst to_const(const Fp<FP>& x) {
   FrConst k;
@@ -112,7 +109,7 @@ int lagrange_constants(const ark_hip_radix2_domain* dom, const uint64_t* tau4, s
 
 // the launches that bind dim variables of a 2^num_vars table, shared by fix_variables and evaluate: the intermediate tables
 // live in Context::poly_work behind the result slot, the last launch writes `last` (nullptr: the result slot)
-inline int mle_fold_run(Context* c, int field, const void* d_evals, unsigned num_vars, const uint64_t* point, unsigned dim, void* last) {
+inline int mle_fold_run(Context* c, const FieldOps* ops, const void* d_evals, unsigned num_vars, const uint64_t* point, unsigned dim, void* last) {
   int widths[MLE_MAX_PASSES];
   const int passes = mle_fold_passes((int)dim, widths);
   size_t scratch = 1;
@@ -126,7 +123,7 @@ inline int mle_fold_run(Context* c, int field, const void* d_evals, unsigned num
     for (int j = 0; j < widths[p]; j++, point += 4)
       for (int q = 0; q < 4; q++) { pt.r[j].l[2 * q] = (u32)point[q]; pt.r[j].l[2 * q + 1] = (u32)(point[q] >> 32); }
     void* dst = p + 1 < passes ? (void*)w : last ? last : c->poly_work.p;
-    if (int rc = mle_fold_dispatch(field, cur, m, widths[p], pt, dst, c->stream)) return rc;
+    if (int rc = ops->mle_fold(cur, m, widths[p], pt, dst, c->stream)) return rc;
     m -= widths[p];
     w += ((size_t)1 << m) * 32;
     cur = dst;
@@ -170,7 +167,8 @@ int ark_hip_poly_scan_plan(size_t n, int* tile, int* levels) {
 }
 
 int ark_hip_poly_evaluate_device(int field, const void* d_coeffs, size_t n, const uint64_t* point, uint64_t* out) {
-  if (!field_served(field) || !point || !out || (n && !d_coeffs)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !point || !out || (n && !d_coeffs)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
   if (n == 0) {
@@ -185,14 +183,15 @@ int ark_hip_poly_evaluate_device(int field, const void* d_coeffs, size_t n, cons
   const void* cur = d_coeffs;
   for (int l = 0; l < L.levels; l++) {   // the last level has one tile: its value is p(z), written to the result slot
     void* vals = l + 1 < L.levels ? w + L.off[l + 1] * 32 : w;
-    if (int rc = poly_tile_value_dispatch(field, cur, L.len[l], pw[l], vals, c->stream)) return rc;
+    if (int rc = ops->poly_tile_value(cur, L.len[l], pw[l], vals, c->stream)) return rc;
     cur = vals;
   }
   return result_to_host(c, out);
 }
 
 int ark_hip_poly_divide_linear_device(int field, const void* d_coeffs, size_t n, const uint64_t* z, void* d_quot, uint64_t* out_rem) {
-  if (!field_served(field) || !z || (n && !d_coeffs) || (n > 1 && !d_quot)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !z || (n && !d_coeffs) || (n > 1 && !d_quot)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
   if (n == 0) {
@@ -207,21 +206,22 @@ int ark_hip_poly_divide_linear_device(int field, const void* d_coeffs, size_t n,
   auto vec = [&](int l) -> void* { return l == 0 ? const_cast<void*>(d_coeffs) : (void*)(w + L.off[l] * 32); };
   // up: tile values of every level that has more than one tile
   for (int l = 0; l + 1 < L.levels; l++)
-    if (int rc = poly_tile_value_dispatch(field, vec(l), L.len[l], pw[l], vec(l + 1), c->stream)) return rc;
+    if (int rc = ops->poly_tile_value(vec(l), L.len[l], pw[l], vec(l + 1), c->stream)) return rc;
   // down: the top level is one tile with no carry; every level's quotient is the carries of the level below it, written
   // over its own tile values (the last one stays: the last tile's carry is zero by definition)
   for (int l = L.levels - 1; l >= 0; l--) {
     const void* carries = l + 1 < L.levels ? vec(l + 1) : nullptr;
     void* dst = l == 0 ? d_quot : vec(l);
     void* rem = (l == 0 && out_rem) ? (void*)w : nullptr;
-    if (int rc = poly_tile_divide_dispatch(field, vec(l), L.len[l], pw[l], carries, dst, rem, c->stream)) return rc;
+    if (int rc = ops->poly_tile_divide(vec(l), L.len[l], pw[l], carries, dst, rem, c->stream)) return rc;
   }
   if (out_rem) return result_to_host(c, out_rem);
   return mark_producer(c);
 }
 
 int ark_hip_poly_divide_by_vanishing_device(int field, size_t domain_size, const void* d_coeffs, size_t n, void* d_quot, void* d_rem) {
-  if (!field_served(field) || domain_size == 0 || (n && (!d_coeffs || !d_rem)) || (n > domain_size && !d_quot)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || domain_size == 0 || (n && (!d_coeffs || !d_rem)) || (n > domain_size && !d_quot)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
   if (n == 0) return 0;
@@ -229,12 +229,13 @@ int ark_hip_poly_divide_by_vanishing_device(int field, size_t domain_size, const
     ARK_HIP_TRY(hipMemcpyAsync(d_rem, d_coeffs, n * 32, hipMemcpyDeviceToDevice, c->stream));
     return mark_producer(c);
   }
-  if (int rc = poly_vanishing_dispatch(field, d_coeffs, n, domain_size, d_quot, d_rem, c->stream)) return rc;
+  if (int rc = ops->poly_vanishing(d_coeffs, n, domain_size, d_quot, d_rem, c->stream)) return rc;
   return mark_producer(c);
 }
 
 int ark_hip_domain_lagrange_coefficients_device(int field, const ark_hip_radix2_domain* dom, const uint64_t* tau, void* d_out) {
-  if (!field_served(field) || !dom || !tau || !d_out) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !dom || !tau || !d_out) return ARK_HIP_ERR_ARG;
   if (dom->log_size_of_group > 63 || dom->size != ((uint64_t)1 << dom->log_size_of_group)) return ARK_HIP_ERR_ARG;
   if (!domain_is_of_field(field, dom)) return ARK_HIP_ERR_ARG;
   const size_t n = (size_t)dom->size;
@@ -254,15 +255,16 @@ int ark_hip_domain_lagrange_coefficients_device(int field, const ark_hip_radix2_
   }
   ARK_SCOPE(sc);
   Context* c = sc.c;
-  if (int rc = poly_lagrange_dispatch(field, a4, c4, w4, ws4, onehot, d_out, n, lanes, c->stream)) return rc;
+  if (int rc = ops->poly_lagrange(a4, c4, w4, ws4, onehot, d_out, n, lanes, c->stream)) return rc;
   // batch_inversion of the inverse coefficients (domain/mod.rs:219), lane-batched in place
   if (!onehot)
-    if (int rc = fr_div_dispatch(field, nullptr, d_out, d_out, n, c->stream)) return rc;
+    if (int rc = ops->fr_div(nullptr, d_out, d_out, n, c->stream)) return rc;
   return mark_producer(c);
 }
 
 int ark_hip_fr_inner_product_device(int field, const void* d_a, const void* d_b, size_t n, uint64_t* out) {
-  if (!field_served(field) || !out || (n && (!d_a || !d_b))) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !out || (n && (!d_a || !d_b))) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
   if (n == 0) {
@@ -271,7 +273,7 @@ int ark_hip_fr_inner_product_device(int field, const void* d_a, const void* d_b,
   }
   if (int rc = poly_scratch(c, 1 + INNER_BLOCKS)) return rc;
   char* w = (char*)c->poly_work.p;
-  if (int rc = fr_inner_product_dispatch(field, d_a, d_b, n, w + 32, w, c->stream)) return rc;
+  if (int rc = ops->fr_inner_product(d_a, d_b, n, w + 32, w, c->stream)) return rc;
   return result_to_host(c, out);
 }
 
@@ -296,7 +298,8 @@ int ark_hip_mle_fold_tiles(unsigned num_vars, unsigned dim, int* tiles_log) {
 
 int ark_hip_mle_fix_variables_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* partial_point, unsigned dim,
                                      void* d_out) {
-  if (!field_served(field) || !d_evals || !d_out || num_vars >= 64 || dim > num_vars || (dim && !partial_point)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_evals || !d_out || num_vars >= 64 || dim > num_vars || (dim && !partial_point)) return ARK_HIP_ERR_ARG;
   if (num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
   const size_t n = (size_t)1 << num_vars, n_out = n >> dim;
   if (ranges_overlap(d_evals, n * 32, d_out, n_out * 32)) return ARK_HIP_ERR_ARG;
@@ -306,12 +309,13 @@ int ark_hip_mle_fix_variables_device(int field, const void* d_evals, unsigned nu
     ARK_HIP_TRY(hipMemcpyAsync(d_out, d_evals, n * 32, hipMemcpyDeviceToDevice, c->stream));
     return mark_producer(c);
   }
-  if (int rc = mle_fold_run(c, field, d_evals, num_vars, partial_point, dim, d_out)) return rc;
+  if (int rc = mle_fold_run(c, ops, d_evals, num_vars, partial_point, dim, d_out)) return rc;
   return mark_producer(c);
 }
 
 int ark_hip_mle_evaluate_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* point, uint64_t* out) {
-  if (!field_served(field) || !d_evals || !out || num_vars >= 64 || (num_vars && !point)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_evals || !out || num_vars >= 64 || (num_vars && !point)) return ARK_HIP_ERR_ARG;
   if (num_vars > 58) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
@@ -320,7 +324,7 @@ int ark_hip_mle_evaluate_device(int field, const void* d_evals, unsigned num_var
     ARK_HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
   }
-  if (int rc = mle_fold_run(c, field, d_evals, num_vars, point, num_vars, nullptr)) return rc;
+  if (int rc = mle_fold_run(c, ops, d_evals, num_vars, point, num_vars, nullptr)) return rc;
   return result_to_host(c, out);
 }
 
@@ -334,7 +338,8 @@ int ark_hip_mle_eq_plan(unsigned num_vars, int* tile_log, int* passes, int* widt
 }
 
 int ark_hip_mle_eq_table_device(int field, const uint64_t* point, unsigned num_vars, const uint64_t* scale, void* d_out) {
-  if (!field_served(field) || !d_out || num_vars >= 64 || (num_vars && !point)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_out || num_vars >= 64 || (num_vars && !point)) return ARK_HIP_ERR_ARG;
   if (num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
   int widths[MLE_MAX_PASSES];
   const int passes = mle_eq_passes((int)num_vars, widths);
@@ -354,7 +359,7 @@ int ark_hip_mle_eq_table_device(int field, const uint64_t* point, unsigned num_v
     MlePoint pt = {};   // zeros for the variables a short launch lacks
     mle_point_fill(pt, point + 4 * ((size_t)num_vars - m), widths[p]);
     void* dst = p + 1 < passes ? (void*)w : d_out;
-    if (int rc = mle_eq_dispatch(field, hi, top, scale ? 0 : 1, pt, m, dst, c->stream)) return rc;
+    if (int rc = ops->mle_eq(hi, top, scale ? 0 : 1, pt, m, dst, c->stream)) return rc;
     w += ((size_t)1 << m) * 32;
     hi = dst;
   }
@@ -371,7 +376,8 @@ int ark_hip_mle_quotients_plan(unsigned num_vars, int* tile_log, int* passes, in
 
 int ark_hip_mle_quotients_device(int field, const void* d_evals, unsigned num_vars, const uint64_t* point, void* d_quot,
                                  uint64_t* out_value) {
-  if (!field_served(field) || !d_evals || num_vars >= 64 || (num_vars && (!point || !d_quot))) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_evals || num_vars >= 64 || (num_vars && (!point || !d_quot))) return ARK_HIP_ERR_ARG;
   if (num_vars > 58) return ARK_HIP_ERR_ARG;
   const size_t n = (size_t)1 << num_vars;
   if (num_vars && ranges_overlap(d_evals, n * 32, d_quot, (n - 1) * 32)) return ARK_HIP_ERR_ARG;
@@ -399,7 +405,7 @@ int ark_hip_mle_quotients_device(int field, const void* d_evals, unsigned num_va
     void* dst = p + 1 < passes ? (void*)w : c->poly_work.p;
     // the segment of variable i = num_vars - m starts at element 2^num_vars - 2^m
     char* quot = (char*)d_quot + (n - ((size_t)1 << m)) * 32;
-    if (int rc = mle_quot_dispatch(field, cur, m, widths[p], pt, quot, dst, c->stream)) return rc;
+    if (int rc = ops->mle_quot(cur, m, widths[p], pt, quot, dst, c->stream)) return rc;
     m -= widths[p];
     w += ((size_t)1 << m) * 32;
     cur = dst;
@@ -409,7 +415,8 @@ int ark_hip_mle_quotients_device(int field, const void* d_evals, unsigned num_va
 }
 
 int ark_hip_mle_relabel_device(int field, const void* d_evals, unsigned num_vars, unsigned a, unsigned b, unsigned k, void* d_out) {
-  if (!field_served(field) || !d_evals || !d_out || num_vars >= 64) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_evals || !d_out || num_vars >= 64) return ARK_HIP_ERR_ARG;
   if (num_vars > 58) return ARK_HIP_ERR_ARG;
   if (a > b) { const unsigned t = a; a = b; b = t; }
   const bool identity = a == b || k == 0;   // the reference returns before its assertions (dense.rs:81-83)
@@ -422,15 +429,16 @@ int ark_hip_mle_relabel_device(int field, const void* d_evals, unsigned num_vars
     if (d_out != d_evals) ARK_HIP_TRY(hipMemcpyAsync(d_out, d_evals, n * 32, hipMemcpyDeviceToDevice, c->stream));
     return mark_producer(c);
   }
-  if (int rc = mle_relabel_dispatch(field, d_evals, n, (int)a, (int)b, (int)k, d_out, c->stream)) return rc;
+  if (int rc = ops->mle_relabel(d_evals, n, (int)a, (int)b, (int)k, d_out, c->stream)) return rc;
   return mark_producer(c);
 }
 
 int ark_hip_fr_axpy_device(int field, const void* d_a, const uint64_t* k, const void* d_x, void* d_r, size_t n) {
-  if (!field_served(field) || !k || (n && (!d_a || !d_x || !d_r))) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !k || (n && (!d_a || !d_x || !d_r))) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
-  if (int rc = fr_axpy_dispatch(field, d_a, k, d_x, d_r, n, c->stream)) return rc;
+  if (int rc = ops->fr_axpy(d_a, k, d_x, d_r, n, c->stream)) return rc;
   return mark_producer(c);
 }
 
@@ -442,7 +450,8 @@ int ark_hip_mle_product_tree_plan(unsigned num_vars, int* passes, int* widths, i
 }
 
 int ark_hip_mle_product_tree_device(int field, const void* d_evals, unsigned num_vars, void* d_tree, uint64_t* out_product) {
-  if (!field_served(field) || !d_evals || num_vars >= 64 || (num_vars && !d_tree)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_evals || num_vars >= 64 || (num_vars && !d_tree)) return ARK_HIP_ERR_ARG;
   if (num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
   const size_t n = (size_t)1 << num_vars;
   if (num_vars && ranges_overlap(d_evals, n * 32, d_tree, (n - 1) * 32)) return ARK_HIP_ERR_ARG;
@@ -457,7 +466,7 @@ int ark_hip_mle_product_tree_device(int field, const void* d_evals, unsigned num
     for (int p = 0; p < launches; p++) {
       // L_k starts at element 2^num_vars - 2^(k+1): the launch reads L_m and writes from L_(m-1) on
       char* dst = (char*)d_tree + (n - ((size_t)1 << m)) * 32;
-      if (int rc = prod_tree_dispatch(field, cur, m, widths[p], dst, c->stream)) return rc;
+      if (int rc = ops->prod_tree(cur, m, widths[p], dst, c->stream)) return rc;
       m -= widths[p];
       cur = (char*)d_tree + (n - ((size_t)2 << m)) * 32;
     }
@@ -471,7 +480,8 @@ int ark_hip_mle_product_tree_device(int field, const void* d_evals, unsigned num
 
 int ark_hip_fr_lincomb_device(int field, const void* const* d_tables, unsigned ntables, const uint64_t* coeffs, const uint64_t* c0,
                               void* d_out, size_t n) {
-  if (!field_served(field) || !d_tables || !coeffs || !d_out || ntables == 0 || ntables > (unsigned)LINCOMB_MAX_TABLES) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_tables || !coeffs || !d_out || ntables == 0 || ntables > (unsigned)LINCOMB_MAX_TABLES) return ARK_HIP_ERR_ARG;
   if (n > ((size_t)-1) / 32) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
   FrLincomb lc = {};
   lc.ntables = ntables;
@@ -486,7 +496,7 @@ int ark_hip_fr_lincomb_device(int field, const void* const* d_tables, unsigned n
     for (int q = 0; q < 4; q++) { lc.c0.l[2 * q] = (u32)c0[q]; lc.c0.l[2 * q + 1] = (u32)(c0[q] >> 32); }
   ARK_SCOPE(sc);
   Context* c = sc.c;
-  if (int rc = fr_lincomb_dispatch(field, lc, d_out, n, c->stream)) return rc;
+  if (int rc = ops->fr_lincomb(lc, d_out, n, c->stream)) return rc;
   return mark_producer(c);
 }
 
@@ -500,7 +510,8 @@ int ark_hip_mle_fraction_tree_plan(unsigned num_vars, int has_num, int* passes, 
 
 int ark_hip_mle_fraction_tree_device(int field, const void* d_num, const void* d_den, unsigned num_vars, void* d_num_tree,
                                      void* d_den_tree, uint64_t* out_root) {
-  if (!field_served(field) || !d_den || num_vars >= 64 || (num_vars && (!d_num_tree || !d_den_tree))) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_den || num_vars >= 64 || (num_vars && (!d_num_tree || !d_den_tree))) return ARK_HIP_ERR_ARG;
   if (num_vars > 58) return ARK_HIP_ERR_ARG;   // a table's bytes must fit a size_t
   const size_t n = (size_t)1 << num_vars;
   if (num_vars) {
@@ -520,7 +531,7 @@ int ark_hip_mle_fraction_tree_device(int field, const void* d_num, const void* d
     for (int p = 0; p < launches; p++) {
       // level k starts at element 2^num_vars - 2^(k+1) of its tree: the launch reads level m and writes from level m - 1 on
       const size_t dst = (n - ((size_t)1 << m)) * 32;
-      if (int rc = frac_tree_dispatch(field, ncur, dcur, m, widths[p], (char*)d_num_tree + dst, (char*)d_den_tree + dst, c->stream)) return rc;
+      if (int rc = ops->frac_tree(ncur, dcur, m, widths[p], (char*)d_num_tree + dst, (char*)d_den_tree + dst, c->stream)) return rc;
       m -= widths[p];
       ncur = (char*)d_num_tree + (n - ((size_t)2 << m)) * 32;
       dcur = (char*)d_den_tree + (n - ((size_t)2 << m)) * 32;
@@ -535,12 +546,13 @@ int ark_hip_mle_fraction_tree_device(int field, const void* d_num, const void* d
 }
 
 int ark_hip_fr_count_indices_device(int field, const uint32_t* d_indices, size_t n, void* d_out, size_t table_len) {
-  if (!field_served(field) || !d_out || (n && !d_indices) || table_len == 0) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_out || (n && !d_indices) || table_len == 0) return ARK_HIP_ERR_ARG;
   if ((uint64_t)n >> 32 || table_len > ((size_t)1 << 58)) return ARK_HIP_ERR_ARG;   // a count fits a cell's first word
   if (n && ranges_overlap(d_indices, n * 4, d_out, table_len * 32)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
-  if (int rc = fr_count_dispatch(field, d_indices, n, d_out, table_len, c->stream)) return rc;
+  if (int rc = ops->fr_count(d_indices, n, d_out, table_len, c->stream)) return rc;
   return mark_producer(c);
 }
 
@@ -560,7 +572,8 @@ int ark_hip_sumcheck_plan(unsigned num_vars, unsigned ntables, unsigned degree, 
 int ark_hip_sumcheck_round_device(int field, const void* const* d_tables, unsigned ntables, unsigned num_vars,
                                   const unsigned* term_len, const unsigned* term_tables, const uint64_t* coeffs, unsigned nterms,
                                   const uint64_t* r_prev, void* const* d_out_tables, uint64_t* out_evals) {
-  if (!field_served(field) || !d_tables || !term_len || !term_tables || !coeffs || !out_evals || (r_prev && !d_out_tables)) return ARK_HIP_ERR_ARG;
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_tables || !term_len || !term_tables || !coeffs || !out_evals || (r_prev && !d_out_tables)) return ARK_HIP_ERR_ARG;
   if (ntables == 0 || ntables > (unsigned)SUMCHECK_MAX_TABLES || nterms == 0 || nterms > (unsigned)SUMCHECK_MAX_TERMS) return ARK_HIP_ERR_ARG;
   if (num_vars == 0 || num_vars >= 64 || num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
   SumcheckRound rd = {};
@@ -604,7 +617,7 @@ int ark_hip_sumcheck_round_device(int field, const void* const* d_tables, unsign
   if (int rc = poly_scratch(c, (size_t)SUMCHECK_EVALS * (1 + (rd.blocks > 1 ? rd.blocks : 0)))) return rc;
   rd.out = c->poly_work.p;
   rd.partials = (char*)c->poly_work.p + SUMCHECK_EVALS * 32;
-  if (int rc = sumcheck_round_dispatch(field, rd, c->stream)) return rc;
+  if (int rc = ops->sumcheck_round(rd, c->stream)) return rc;
   ARK_HIP_TRY(hipMemcpyAsync(out_evals, c->poly_work.p, (size_t)(degree + 1) * 32, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;

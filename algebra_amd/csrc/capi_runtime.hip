@@ -185,13 +185,14 @@ int ark_hip_sw_into_affine(int curve, const uint64_t* jac_points, size_t n, uint
 
 // out[i] = in[i] + delta on the device (affine in/out); d_in may equal d_out
 int ark_hip_sw_add_affine_device(int curve, const void* d_in, void* d_out, size_t n, const uint64_t* delta_xy) {
-  if (curve < 0 || curve > 4 || !delta_xy || (n && (!d_in || !d_out))) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !delta_xy || (n && (!d_in || !d_out))) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
   Context* c = sc.c;
   size_t ab = (size_t)CURVES[curve].fe_words * 16;
   if (c->stage_c.ensure(ab)) return ARK_HIP_ERR_NOMEM;
   ARK_HIP_TRY(hipMemcpyAsync(c->stage_c.p, delta_xy, ab, hipMemcpyHostToDevice, c->stream));
-  int rc = add_affine_dispatch(curve, d_in, d_out, n, c->stage_c.p, c->stream);
+  int rc = ops->sw_add_affine(d_in, d_out, n, c->stage_c.p, c->stream);
   if (rc) return rc;
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
@@ -199,9 +200,10 @@ int ark_hip_sw_add_affine_device(int curve, const void* d_in, void* d_out, size_
 
 // CurveGroup::normalize_batch for n Projective points in device memory -> n Affine points (device memory)
 int ark_hip_sw_normalize_batch_device(int curve, const void* d_jac, void* d_out_xy, size_t n) {
-  if (curve < 0 || curve > 4 || (n && (!d_jac || !d_out_xy))) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || (n && (!d_jac || !d_out_xy))) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  int rc = normalize_dispatch(curve, d_jac, d_out_xy, n, sc.c->stream);
+  int rc = ops->sw_normalize_batch(d_jac, d_out_xy, n, sc.c->stream);
   if (rc) return rc;
   ARK_HIP_TRY(hipStreamSynchronize(sc.c->stream));
   return 0;
@@ -210,7 +212,8 @@ int ark_hip_sw_normalize_batch_device(int curve, const void* d_jac, void* d_out_
 // The same from HOST memory (what the Rust hook behind CurveGroup::normalize_batch hands over, group.rs:302-319): one
 // upload of the n Projective points, the lane-batched inversion kernel, one download of the n Affine points.
 int ark_hip_sw_normalize_batch(int curve, const uint64_t* jac_points, size_t n, uint64_t* out_xy) {
-  if (curve < 0 || curve > 4 || (n && (!jac_points || !out_xy))) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || (n && (!jac_points || !out_xy))) return ARK_HIP_ERR_ARG;
   if (n == 0) return 0;
   ARK_SCOPE(sc);
   Context* c = sc.c;
@@ -219,7 +222,7 @@ int ark_hip_sw_normalize_batch(int curve, const uint64_t* jac_points, size_t n, 
     if (int rc = sync_compute(c)) return rc;
   if (c->stage_a.ensure(n * 3 * fb) || c->stage_b.ensure(n * 2 * fb)) return ARK_HIP_ERR_NOMEM;
   if (int rc = c->stager.upload(c->stage_a.p, jac_points, n * 3 * fb, c->stream)) return rc;
-  if (int rc = normalize_dispatch(curve, c->stage_a.p, c->stage_b.p, n, c->stream)) return rc;
+  if (int rc = ops->sw_normalize_batch(c->stage_a.p, c->stage_b.p, n, c->stream)) return rc;
   ARK_HIP_TRY(hipMemcpyAsync(out_xy, c->stage_b.p, n * 2 * fb, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
@@ -248,7 +251,8 @@ static int sw_check_end(Context* c, size_t n, uint64_t out[4]) {
 
 int ark_hip_sw_check_device(int curve, const void* d_bases_xy, size_t n, int checks, int method, void* d_status, uint64_t out[4]) {
   if (int rc = sw_check_args(curve, checks, method)) return rc;
-  if (!out || (n && !d_bases_xy)) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !out || (n && !d_bases_xy)) return ARK_HIP_ERR_ARG;
   if (n == 0) {
     out[0] = out[1] = out[2] = out[3] = 0;
     return 0;
@@ -256,7 +260,7 @@ int ark_hip_sw_check_device(int curve, const void* d_bases_xy, size_t n, int che
   ARK_SCOPE(sc);
   Context* c = sc.c;
   if (int rc = sw_check_begin(c)) return rc;
-  if (int rc = sw_check_dispatch(curve, d_bases_xy, n, 0, checks, method, d_status, c->check_work.p, c->stream)) return rc;
+  if (int rc = ops->sw_check(d_bases_xy, n, 0, checks, method, d_status, c->check_work.p, c->stream)) return rc;
   return sw_check_end(c, n, out);
 }
 
@@ -264,7 +268,8 @@ int ark_hip_sw_check_device(int curve, const void* d_bases_xy, size_t n, int che
 // launch per chunk into the same summary words, the status bytes of a chunk downloaded behind its launch.
 int ark_hip_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, int method, uint8_t* status, uint64_t out[4]) {
   if (int rc = sw_check_args(curve, checks, method)) return rc;
-  if (!out || (n && !bases_xy)) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !out || (n && !bases_xy)) return ARK_HIP_ERR_ARG;
   if (n == 0) {
     out[0] = out[1] = out[2] = out[3] = 0;
     return 0;
@@ -280,7 +285,7 @@ int ark_hip_sw_check(int curve, const uint64_t* bases_xy, size_t n, int checks, 
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = n - off < chunk ? n - off : chunk;
     if (int rc = c->stager.upload(c->stage_a.p, (const char*)bases_xy + off * ab, m * ab, c->stream)) return rc;
-    if (int rc = sw_check_dispatch(curve, c->stage_a.p, m, off, checks, method, status ? c->stage_b.p : nullptr, c->check_work.p,
+    if (int rc = ops->sw_check(c->stage_a.p, m, off, checks, method, status ? c->stage_b.p : nullptr, c->check_work.p,
                                    c->stream))
       return rc;
     if (status) ARK_HIP_TRY(hipMemcpyAsync(status + off, c->stage_b.p, m, hipMemcpyDeviceToHost, c->stream));
@@ -321,7 +326,8 @@ static int sw_decompress_end(Context* c, size_t n, uint64_t out[5]) {
 int ark_hip_sw_decompress_device(int curve, const void* d_bytes, size_t n, int validate, int method, void* d_points_xy, void* d_status,
                                  uint64_t out[5]) {
   if (int rc = sw_decompress_args(curve, validate, method)) return rc;
-  if (!out || (n && (!d_bytes || !d_points_xy))) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !out || (n && (!d_bytes || !d_points_xy))) return ARK_HIP_ERR_ARG;
   if (n == 0) {
     out[0] = out[1] = out[2] = out[3] = out[4] = 0;
     return 0;
@@ -330,7 +336,7 @@ int ark_hip_sw_decompress_device(int curve, const void* d_bytes, size_t n, int v
   ARK_SCOPE(sc);
   Context* c = sc.c;
   if (int rc = sw_decompress_begin(c)) return rc;
-  if (int rc = sw_decompress_dispatch(curve, d_bytes, n, 0, validate, method, d_points_xy, d_status, c->check_work.p, c->stream)) return rc;
+  if (int rc = ops->sw_decompress(d_bytes, n, 0, validate, method, d_points_xy, d_status, c->check_work.p, c->stream)) return rc;
   return sw_decompress_end(c, n, out);
 }
 
@@ -339,7 +345,8 @@ int ark_hip_sw_decompress_device(int curve, const void* d_bytes, size_t n, int v
 int ark_hip_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validate, int method, uint64_t* points_xy, uint8_t* status,
                           uint64_t out[5]) {
   if (int rc = sw_decompress_args(curve, validate, method)) return rc;
-  if (!out || (n && (!bytes || !points_xy))) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !out || (n && (!bytes || !points_xy))) return ARK_HIP_ERR_ARG;
   if (n == 0) {
     out[0] = out[1] = out[2] = out[3] = out[4] = 0;
     return 0;
@@ -355,7 +362,7 @@ int ark_hip_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validat
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = n - off < chunk ? n - off : chunk;
     if (int rc = c->stager.upload(c->stage_a.p, (const char*)bytes + off * eb, m * eb, c->stream)) return rc;
-    if (int rc = sw_decompress_dispatch(curve, c->stage_a.p, m, off, validate, method, c->stage_c.p, status ? c->stage_b.p : nullptr,
+    if (int rc = ops->sw_decompress(c->stage_a.p, m, off, validate, method, c->stage_c.p, status ? c->stage_b.p : nullptr,
                                         c->check_work.p, c->stream))
       return rc;
     ARK_HIP_TRY(hipMemcpyAsync((char*)points_xy + off * ab, c->stage_c.p, m * ab, hipMemcpyDeviceToHost, c->stream));
@@ -366,15 +373,17 @@ int ark_hip_sw_decompress(int curve, const uint8_t* bytes, size_t n, int validat
 
 // asynchronous on the context stream
 int ark_hip_sw_compress_device(int curve, const void* d_points_xy, size_t n, void* d_bytes) {
-  if (curve < 0 || curve > 4 || (n && (!d_points_xy || !d_bytes))) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || (n && (!d_points_xy || !d_bytes))) return ARK_HIP_ERR_ARG;
   if (n == 0) return 0;
   if (!sw_codec_ptrs_ok(curve, d_bytes, d_points_xy, n)) return ARK_HIP_ERR_ARG;
   ARK_SCOPE(sc);
-  return sw_compress_dispatch(curve, d_points_xy, n, d_bytes, sc.c->stream);
+  return ops->sw_compress(d_points_xy, n, d_bytes, sc.c->stream);
 }
 
 int ark_hip_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t* bytes) {
-  if (curve < 0 || curve > 4 || (n && (!points_xy || !bytes))) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || (n && (!points_xy || !bytes))) return ARK_HIP_ERR_ARG;
   if (n == 0) return 0;
   ARK_SCOPE(sc);
   Context* c = sc.c;
@@ -386,7 +395,7 @@ int ark_hip_sw_compress(int curve, const uint64_t* points_xy, size_t n, uint8_t*
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = n - off < chunk ? n - off : chunk;
     if (int rc = c->stager.upload(c->stage_a.p, (const char*)points_xy + off * ab, m * ab, c->stream)) return rc;
-    if (int rc = sw_compress_dispatch(curve, c->stage_a.p, m, c->stage_c.p, c->stream)) return rc;
+    if (int rc = ops->sw_compress(c->stage_a.p, m, c->stage_c.p, c->stream)) return rc;
     ARK_HIP_TRY(hipMemcpyAsync(bytes + off * eb, c->stage_c.p, m * eb, hipMemcpyDeviceToHost, c->stream));
   }
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));

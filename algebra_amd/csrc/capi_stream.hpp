@@ -107,8 +107,11 @@ inline int msm_stream(Context* c, int curve, const void* d_bases, const uint64_t
     MsmWidths widths{};
     bool skewed = false;
     const MsmKnobs knobs = msm_knobs();
-    if (knobs.probe && scalars && n >= ((size_t)1 << 19) && msm_sample_widths_dispatch(curve, scalars, n, mont, &widths) == 0)
+    const CurveOps* ops = curve_ops(curve);
+    if (knobs.probe && scalars && n >= ((size_t)1 << 19) && ops) {
+      ops->msm_sample_widths(scalars, n, mont, &widths);
       skewed = msm_widths_skewed(widths);
+    }
     plan = msm_default_plan(curve, n, msm_scalar_bits(curve), false, skewed ? &widths : nullptr, knobs, /*streamed=*/true);
     if ((size_t)step * (size_t)plan.W >= (1ull << 32)) return ARK_HIP_ERR_SIZE;
     const size_t need = plan.nbuckets() * (size_t)CURVES[curve].fe_words * 32;  // XYZZ: four field elements

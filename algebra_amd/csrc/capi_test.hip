@@ -13,6 +13,7 @@
 #include "lazytest_api.hpp"
 #include "relaxtest_api.hpp"
 #include "s30test_api.hpp"
+#include "testops_api.hpp"
 #include "scratch_list.hpp"
 #include <map>
 #include <string>
@@ -25,137 +26,61 @@ int msm_sharded_emulated(int curve, int world, const void* const* d_bases, const
                          int scalars_are_montgomery, uint64_t* out_xyz, int* path);   // capi_comm.hip
 }
 }
-namespace arkhip {   // raw-limb hooks: testops_curve.hip (per curve), testops_field.hip (per scalar field)
-#define ARK_DECL_LAZYTEST_RAW(NAME) \
-  int test_lazy_raw_op_##NAME(int op, int k, int h, const void* d_in, void* d_out, size_t n, hipStream_t s);
-#define ARK_DECL_LAZYTEST_ACC(NAME) \
-  int test_lazy_acc_op_##NAME(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s);
-ARK_DECL_LAZYTEST_RAW(BN254_G1) ARK_DECL_LAZYTEST_RAW(BLS12_381_G1) ARK_DECL_LAZYTEST_RAW(BLS12_377_G1)
-ARK_DECL_LAZYTEST_RAW(BLS12_377_G2) ARK_DECL_LAZYTEST_RAW(BLS12_381_G2)
-ARK_DECL_LAZYTEST_RAW(BN254_FR) ARK_DECL_LAZYTEST_RAW(BLS12_381_FR) ARK_DECL_LAZYTEST_RAW(BLS12_377_FR)
-ARK_DECL_LAZYTEST_ACC(BN254_G1) ARK_DECL_LAZYTEST_ACC(BLS12_381_G1) ARK_DECL_LAZYTEST_ACC(BLS12_377_G1)
-ARK_DECL_LAZYTEST_ACC(BLS12_377_G2) ARK_DECL_LAZYTEST_ACC(BLS12_381_G2)
-int test_s30_raw_op_BLS12_381_G1(int op, const void* d_in, void* d_out, size_t n, hipStream_t s);   // s30test.cuh
-#undef ARK_DECL_LAZYTEST_RAW
-#undef ARK_DECL_LAZYTEST_ACC
-#define ARK_DECL_RELAXTEST_RAW(NAME) int test_relaxed_raw_op_##NAME(int op, const void* d_in, void* d_out, size_t n, hipStream_t s);
-#define ARK_DECL_RELAXTEST_ACC(NAME) \
-  int test_relaxed_acc_op_##NAME(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s);
-ARK_DECL_RELAXTEST_RAW(BN254_G1) ARK_DECL_RELAXTEST_RAW(BLS12_381_G1) ARK_DECL_RELAXTEST_RAW(BLS12_377_G1)
-ARK_DECL_RELAXTEST_RAW(BLS12_377_G2) ARK_DECL_RELAXTEST_RAW(BLS12_381_G2)
-ARK_DECL_RELAXTEST_RAW(BN254_FR) ARK_DECL_RELAXTEST_RAW(BLS12_381_FR) ARK_DECL_RELAXTEST_RAW(BLS12_377_FR)
-ARK_DECL_RELAXTEST_ACC(BN254_G1) ARK_DECL_RELAXTEST_ACC(BLS12_381_G1) ARK_DECL_RELAXTEST_ACC(BLS12_377_G1)
-ARK_DECL_RELAXTEST_ACC(BLS12_377_G2) ARK_DECL_RELAXTEST_ACC(BLS12_381_G2)
-#undef ARK_DECL_RELAXTEST_RAW
-#undef ARK_DECL_RELAXTEST_ACC
-}  // namespace arkhip
 namespace {
-typedef int (*lazy_raw_fn)(int, int, int, const void*, void*, size_t, hipStream_t);
-// FpL / Fft29 ops: the unit of the field (a base field through the G1 curve over it); Fp2L ops: the G2 unit over the base field
-lazy_raw_fn lazy_raw_fn_of(int field, bool x2) {
-  switch (field) {
-#ifndef ARK_HIP_DEV
-    case ARK_HIP_BN254_FQ: return x2 ? nullptr : test_lazy_raw_op_BN254_G1;
-    case ARK_HIP_BN254_FR: return x2 ? nullptr : test_lazy_raw_op_BN254_FR;
-    case ARK_HIP_BLS12_381_FQ: return x2 ? test_lazy_raw_op_BLS12_381_G2 : test_lazy_raw_op_BLS12_381_G1;
-    case ARK_HIP_BLS12_381_FR: return x2 ? nullptr : test_lazy_raw_op_BLS12_381_FR;
-    case ARK_HIP_BLS12_377_FQ: return x2 ? test_lazy_raw_op_BLS12_377_G2 : test_lazy_raw_op_BLS12_377_G1;
-    case ARK_HIP_BLS12_377_FR: return x2 ? nullptr : test_lazy_raw_op_BLS12_377_FR;
-#endif
-  }
-  return nullptr;
-}
-elementwise_fn lazy_acc_fn_of(int curve) {
+// the test hooks of a curve / scalar field by its id (testops_api.hpp), nullptr for an id this build does not serve
+const TestCurveOps* test_curve_ops(int curve) {
   switch (curve) {
 #ifndef ARK_HIP_DEV
-    case 0: return test_lazy_acc_op_BN254_G1;
-    case 1: return test_lazy_acc_op_BLS12_381_G1;
-    case 2: return test_lazy_acc_op_BLS12_377_G1;
-    case 3: return test_lazy_acc_op_BLS12_377_G2;
-    case 4: return test_lazy_acc_op_BLS12_381_G2;
+    case ARK_HIP_BN254_G1: return &test_curve_ops_BN254_G1();
+    case ARK_HIP_BLS12_377_G1: return &test_curve_ops_BLS12_377_G1();
+    case ARK_HIP_BLS12_377_G2: return &test_curve_ops_BLS12_377_G2();
+    case ARK_HIP_BLS12_381_G2: return &test_curve_ops_BLS12_381_G2();
 #endif
+    case ARK_HIP_BLS12_381_G1: return &test_curve_ops_BLS12_381_G1();
   }
   return nullptr;
 }
-typedef int (*relaxed_raw_fn)(int, const void*, void*, size_t, hipStream_t);
-// Fp ops: the unit of the field (a base field through the G1 curve over it); Fp2 / Fp2Half ops: the G2 unit over the base field
-relaxed_raw_fn relaxed_raw_fn_of(int field, bool pair) {
+const TestFieldOps* test_field_ops(int field) {
   switch (field) {
 #ifndef ARK_HIP_DEV
-    case ARK_HIP_BN254_FQ: return pair ? nullptr : test_relaxed_raw_op_BN254_G1;
-    case ARK_HIP_BN254_FR: return pair ? nullptr : test_relaxed_raw_op_BN254_FR;
-    case ARK_HIP_BLS12_381_FQ: return pair ? test_relaxed_raw_op_BLS12_381_G2 : test_relaxed_raw_op_BLS12_381_G1;
-    case ARK_HIP_BLS12_381_FR: return pair ? nullptr : test_relaxed_raw_op_BLS12_381_FR;
-    case ARK_HIP_BLS12_377_FQ: return pair ? test_relaxed_raw_op_BLS12_377_G2 : test_relaxed_raw_op_BLS12_377_G1;
-    case ARK_HIP_BLS12_377_FR: return pair ? nullptr : test_relaxed_raw_op_BLS12_377_FR;
+    case ARK_HIP_BN254_FR: return &test_field_ops_BN254_FR();
+    case ARK_HIP_BLS12_377_FR: return &test_field_ops_BLS12_377_FR();
 #endif
+    case ARK_HIP_BLS12_381_FR: return &test_field_ops_BLS12_381_FR();
   }
   return nullptr;
 }
-elementwise_fn relaxed_acc_fn_of(int curve) {
-  switch (curve) {
-#ifndef ARK_HIP_DEV
-    case 0: return test_relaxed_acc_op_BN254_G1;
-    case 1: return test_relaxed_acc_op_BLS12_381_G1;
-    case 2: return test_relaxed_acc_op_BLS12_377_G1;
-    case 3: return test_relaxed_acc_op_BLS12_377_G2;
-    case 4: return test_relaxed_acc_op_BLS12_381_G2;
-#endif
+// a base field is served through the curves over it: its own ops by the G1 unit, the Fp2 ops over it by the G2 unit (-1: none)
+int curve_over(int field, bool g2) {
+  switch (field) {
+    case ARK_HIP_BN254_FQ: return g2 ? -1 : ARK_HIP_BN254_G1;
+    case ARK_HIP_BLS12_381_FQ: return g2 ? ARK_HIP_BLS12_381_G2 : ARK_HIP_BLS12_381_G1;
+    case ARK_HIP_BLS12_377_FQ: return g2 ? ARK_HIP_BLS12_377_G2 : ARK_HIP_BLS12_377_G1;
   }
-  return nullptr;
+  return -1;
+}
+// raw-limb ops of a field: a scalar field's own unit, a base field's through curve_over; pair: the Fp2L / Fp2 / Fp2Half ops
+const TestRawOps* test_raw_ops(int field, bool pair) {
+  const int curve = curve_over(field, pair);
+  if (curve >= 0) return test_curve_ops(curve);
+  return pair ? nullptr : test_field_ops(field);
+}
+// the elementwise hooks share one signature: member `op` of the hooks of `curve`, empty where this build does not serve it
+typedef std::function<int(int, const void*, const void*, void*, size_t, hipStream_t)> elementwise_fn;
+typedef int (TestCurveOps::*curve_elementwise)(int, const void*, const void*, void*, size_t, hipStream_t) const;
+elementwise_fn curve_fn(int curve, curve_elementwise op) {
+  const TestCurveOps* t = test_curve_ops(curve);
+  if (!t) return nullptr;
+  return [t, op](int k, const void* a, const void* b, void* r, size_t n, hipStream_t s) { return (t->*op)(k, a, b, r, n, s); };
+}
+// the product's field_op for a scalar field; base fields: through the G1 curve over them
+elementwise_fn field_op_fn(int field) {
+  if (const FieldOps* f = field_ops(field))
+    return [f](int op, const void* a, const void* b, void* r, size_t n, hipStream_t s) { return f->field_op(op, a, b, r, n, s); };
+  return curve_fn(curve_over(field, false), &TestCurveOps::basefield_op);
 }
 // limbs of the carry-free form of a field (params.hpp LZ_L): 14 x 28 bits for the 384-bit fields, 9 x 29 bits otherwise
 int lazy_limbs(int field) { return (field == ARK_HIP_BLS12_381_FQ || field == ARK_HIP_BLS12_377_FQ) ? 14 : 9; }
-elementwise_fn field_op_fn(int field) {
-  switch (field) {
-#ifndef ARK_HIP_DEV
-    case ARK_HIP_BN254_FR: return field_op_BN254_FR;
-    case ARK_HIP_BLS12_377_FR: return field_op_BLS12_377_FR;
-    case ARK_HIP_BN254_FQ: return test_basefield_op_BN254_G1;  // base fields: through the G1 curve over them
-    case ARK_HIP_BLS12_377_FQ: return test_basefield_op_BLS12_377_G1;
-#endif
-    case ARK_HIP_BLS12_381_FR: return field_op_BLS12_381_FR;
-    case ARK_HIP_BLS12_381_FQ: return test_basefield_op_BLS12_381_G1;
-  }
-  return nullptr;
-}
-elementwise_fn basefield_op_fn(int curve) {
-  switch (curve) {
-#ifndef ARK_HIP_DEV
-    case 0: return test_basefield_op_BN254_G1;
-    case 2: return test_basefield_op_BLS12_377_G1;
-    case 3: return test_basefield_op_BLS12_377_G2;
-    case 4: return test_basefield_op_BLS12_381_G2;
-#endif
-    case 1: return test_basefield_op_BLS12_381_G1;
-  }
-  return nullptr;
-}
-typedef int (*coord_sqrt_fn)(const void*, void*, void*, size_t, hipStream_t);
-coord_sqrt_fn coord_sqrt_fn_of(int curve) {
-  switch (curve) {
-#ifndef ARK_HIP_DEV
-    case 0: return test_coord_sqrt_BN254_G1;
-    case 2: return test_coord_sqrt_BLS12_377_G1;
-    case 3: return test_coord_sqrt_BLS12_377_G2;
-    case 4: return test_coord_sqrt_BLS12_381_G2;
-#endif
-    case 1: return test_coord_sqrt_BLS12_381_G1;
-  }
-  return nullptr;
-}
-elementwise_fn point_op_fn(int curve) {
-  switch (curve) {
-#ifndef ARK_HIP_DEV
-    case 0: return test_point_op_BN254_G1;
-    case 2: return test_point_op_BLS12_377_G1;
-    case 3: return test_point_op_BLS12_377_G2;
-    case 4: return test_point_op_BLS12_381_G2;
-#endif
-    case 1: return test_point_op_BLS12_381_G1;
-  }
-  return nullptr;
-}
 
 // ---- scratch poisoning (scratch_list.hpp) ---------------------------------------------------------------------------------
 // fill [0, bytes) with the bytes of `word`, repeated (plain vector stores; the last word may be cut)
@@ -284,7 +209,7 @@ extern "C" {
 
 // ---- test hooks ----
 static int run_elementwise(size_t abytes, size_t bbytes, size_t rbytes, const void* a, const void* b, void* r,
-                           elementwise_fn fn, int op, size_t n) {
+                           const elementwise_fn& fn, int op, size_t n) {
   if (!fn) return ARK_HIP_ERR_ARG;  // curve/field not in this (development) build
   ARK_SCOPE(sc);
   Context* c = sc.c;
@@ -312,7 +237,7 @@ int ark_hip_test_field_op(int field, int op, const uint64_t* a, const uint64_t* 
 int ark_hip_test_basefield_op(int curve, int op, const uint64_t* a, const uint64_t* b, uint64_t* r, size_t n) {
   if (curve < 0 || curve > 4 || !a || !r || op < 0 || op > 5) return ARK_HIP_ERR_ARG;
   size_t fb = (size_t)CURVES[curve].fe_words * 8;
-  return run_elementwise(n * fb, b ? n * fb : 0, n * fb, a, b, r, basefield_op_fn(curve), op, n);
+  return run_elementwise(n * fb, b ? n * fb : 0, n * fb, a, b, r, curve_fn(curve, &TestCurveOps::basefield_op), op, n);
 }
 
 int ark_hip_test_host_basefield_op(int curve, int op, const uint64_t* a, const uint64_t* b, uint64_t* r, size_t n) {
@@ -443,8 +368,8 @@ int ark_hip_test_host_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, u
 }
 int ark_hip_test_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n) {
   if (curve < 0 || curve > 4 || (n && (!in || !out || !ok))) return ARK_HIP_ERR_ARG;
-  coord_sqrt_fn fn = coord_sqrt_fn_of(curve);
-  if (!fn) return ARK_HIP_ERR_ARG;
+  const TestCurveOps* ops = test_curve_ops(curve);
+  if (!ops) return ARK_HIP_ERR_ARG;
   if (n == 0) return 0;
   ARK_SCOPE(sc);
   Context* c = sc.c;
@@ -453,7 +378,7 @@ int ark_hip_test_coord_sqrt(int curve, const uint64_t* in, uint64_t* out, uint8_
     if (int rc = sync_compute(c)) return rc;
   if (c->stage_a.ensure(n * fb) || c->stage_b.ensure(n) || c->stage_c.ensure(n * fb)) return ARK_HIP_ERR_NOMEM;
   ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, n * fb, hipMemcpyHostToDevice, c->stream));
-  if (int rc = fn(c->stage_a.p, c->stage_c.p, c->stage_b.p, n, c->stream)) return rc;
+  if (int rc = ops->coord_sqrt(c->stage_a.p, c->stage_c.p, c->stage_b.p, n, c->stream)) return rc;
   ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, n * fb, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipMemcpyAsync(ok, c->stage_b.p, n, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -468,7 +393,7 @@ int ark_hip_test_point_op(int curve, int kind, const uint64_t* acc, const uint64
   size_t bbytes = (kind == 2 || kind == 3 || kind == 12 || kind == 13) ? n * fb * 2 : ((kind == 4 || kind >= 14) ? n * fb * 4 : 0);
   size_t rbytes = n * fb * (kind == 6 ? 3 : 4);
   if (bbytes && !other) return ARK_HIP_ERR_ARG;
-  return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, point_op_fn(curve), kind, n);
+  return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, curve_fn(curve, &TestCurveOps::point_op), kind, n);
 }
 
 int ark_hip_test_lazy_raw_op(int field, int op, int k, int h, const uint32_t* in, uint32_t* out, size_t n) {
@@ -477,8 +402,8 @@ int ark_hip_test_lazy_raw_op(int field, int op, int k, int h, const uint32_t* in
   const Row* row = row_of(op);
   if (!row || !params_ok(op, k, h)) return ARK_HIP_ERR_ARG;
   const bool x2 = op >= X2_FIRST;
-  lazy_raw_fn fn = lazy_raw_fn_of(field, x2);
-  if (!fn || (x2 && (n & 1))) return ARK_HIP_ERR_ARG;
+  const TestRawOps* ops = test_raw_ops(field, x2);
+  if (!ops || (x2 && (n & 1))) return ARK_HIP_ERR_ARG;
   const size_t L = (size_t)lazy_limbs(field);
   const size_t ibytes = n * (size_t)row->arity * L * 4, obytes = n * (L + 1) * 4;
   ARK_SCOPE(sc);
@@ -486,7 +411,7 @@ int ark_hip_test_lazy_raw_op(int field, int op, int k, int h, const uint32_t* in
   if (n == 0) return 0;
   if (c->stage_a.ensure(ibytes) || c->stage_c.ensure(obytes)) return ARK_HIP_ERR_NOMEM;
   ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, ibytes, hipMemcpyHostToDevice, c->stream));
-  const int rc = fn(op, k, h, c->stage_a.p, c->stage_c.p, n, c->stream);
+  const int rc = ops->lazy_raw_op(op, k, h, c->stage_a.p, c->stage_c.p, n, c->stream);
   if (rc) return rc == -1 ? ARK_HIP_ERR_ARG : rc;   // -1: not an op of this field's unit (Fft29 outside the scalar fields, ..)
   ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, obytes, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -506,7 +431,7 @@ int ark_hip_test_lazy_acc_op(int curve, int kind, const void* acc, const void* o
   else if (kind == ACC_ADD_ACC) bbytes = n * slot;
   const size_t rbytes = n * (kind == ACC_TO_BUCKET ? 4 * fb : slot);
   if (bbytes && !other) return ARK_HIP_ERR_ARG;
-  return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, lazy_acc_fn_of(curve), kind, n);
+  return run_elementwise(abytes, bbytes, rbytes, acc, bbytes ? other : nullptr, out, curve_fn(curve, &TestCurveOps::lazy_acc_op), kind, n);
 }
 
 int ark_hip_test_s30_op(int op, const void* in, void* out, size_t n) {
@@ -518,11 +443,7 @@ int ark_hip_test_s30_op(int op, const void* in, void* out, size_t n) {
   if (n == 0) return 0;
   if (c->stage_a.ensure(ibytes) || c->stage_c.ensure(obytes)) return ARK_HIP_ERR_NOMEM;
   ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, ibytes, hipMemcpyHostToDevice, c->stream));
-#ifndef ARK_HIP_DEV
-  const int rc = test_s30_raw_op_BLS12_381_G1(op, c->stage_a.p, c->stage_c.p, n, c->stream);
-#else
-  const int rc = -1;
-#endif
+  const int rc = test_curve_ops_BLS12_381_G1().s30_raw_op(op, c->stage_a.p, c->stage_c.p, n, c->stream);
   if (rc) return rc == -1 ? ARK_HIP_ERR_ARG : rc;
   ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, obytes, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -535,8 +456,8 @@ int ark_hip_test_relaxed_raw_op(int field, int op, const uint32_t* in, uint32_t*
   const Row* row = row_of(op);
   if (!row || !served(op, field)) return ARK_HIP_ERR_ARG;
   const bool pair = row->unit != U_FP;
-  relaxed_raw_fn fn = relaxed_raw_fn_of(field, pair);
-  if (!fn || (pair && (n & 1))) return ARK_HIP_ERR_ARG;
+  const TestRawOps* ops = test_raw_ops(field, pair);
+  if (!ops || (pair && (n & 1))) return ARK_HIP_ERR_ARG;
   const size_t N = (field == ARK_HIP_BLS12_381_FQ || field == ARK_HIP_BLS12_377_FQ) ? 12 : 8;
   const size_t ibytes = n * (size_t)row->arity * N * 4, obytes = n * (N + 1) * 4;
   ARK_SCOPE(sc);
@@ -544,7 +465,7 @@ int ark_hip_test_relaxed_raw_op(int field, int op, const uint32_t* in, uint32_t*
   if (n == 0) return 0;
   if (c->stage_a.ensure(ibytes) || c->stage_c.ensure(obytes)) return ARK_HIP_ERR_NOMEM;
   ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, in, ibytes, hipMemcpyHostToDevice, c->stream));
-  const int rc = fn(op, c->stage_a.p, c->stage_c.p, n, c->stream);
+  const int rc = ops->relaxed_raw_op(op, c->stage_a.p, c->stage_c.p, n, c->stream);
   if (rc) return rc == -1 ? ARK_HIP_ERR_ARG : rc;
   ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, obytes, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -557,10 +478,10 @@ int ark_hip_test_relaxed_acc_op(int curve, int kind, const void* acc, const void
   const size_t fb = (size_t)CURVES[curve].fe_words * 8;
   const size_t bbytes = kind == ACC_MADD ? n * 2 * fb : kind == ACC_ADD ? n * 4 * fb : 0;
   if (bbytes && !other) return ARK_HIP_ERR_ARG;
-  return run_elementwise(n * 4 * fb, bbytes, n * 4 * fb, acc, bbytes ? other : nullptr, out, relaxed_acc_fn_of(curve), kind, n);
+  return run_elementwise(n * 4 * fb, bbytes, n * 4 * fb, acc, bbytes ? other : nullptr, out, curve_fn(curve, &TestCurveOps::relaxed_acc_op), kind, n);
 }
 
-static int host_fold_dispatch(int curve, const uint64_t* parts, int windows, int nbits, u32 l0, const int* widths, uint64_t* out_xyz) {
+static int host_fold_any(int curve, const uint64_t* parts, int windows, int nbits, u32 l0, const int* widths, uint64_t* out_xyz) {
   switch (curve) {
     case 0: return host_fold<BN254_G1>(parts, windows, nbits, l0, widths, out_xyz);
     case 1: return host_fold<BLS12_381_G1>(parts, windows, nbits, l0, widths, out_xyz);
@@ -574,14 +495,14 @@ int ark_hip_test_msm_host_fold(int curve, const uint64_t* parts, int windows, in
                                uint64_t* out_xyz) {
   if (!parts || !widths || !out_xyz || windows < 1 || windows > 256 || nbits < 0 || nbits > 31 || log2_l0 < 0 || log2_l0 > 16)
     return ARK_HIP_ERR_ARG;
-  return host_fold_dispatch(curve, parts, windows, nbits, 1u << log2_l0, widths, out_xyz);
+  return host_fold_any(curve, parts, windows, nbits, 1u << log2_l0, widths, out_xyz);
 }
 // the same tail with the level-0 chunk length given itself (any integer 1 .. 65536, not only a power of two)
 int ark_hip_test_msm_host_fold_l0(int curve, const uint64_t* parts, int windows, int nbits, int l0, const int* widths,
                                   uint64_t* out_xyz) {
   if (!parts || !widths || !out_xyz || windows < 1 || windows > 256 || nbits < 0 || nbits > 31 || l0 < 1 || l0 > 65536)
     return ARK_HIP_ERR_ARG;
-  return host_fold_dispatch(curve, parts, windows, nbits, (u32)l0, widths, out_xyz);
+  return host_fold_any(curve, parts, windows, nbits, (u32)l0, widths, out_xyz);
 }
 // Test hook (host only, no device): the bucket reduction's geometry for a plan given as (c, W, narrow, shared), with every
 // knob at its default (msm_plan.hpp: msm_reduce_geometry)
@@ -635,7 +556,8 @@ int ark_hip_test_msm_sort_geometry(int curve, size_t n, int c, int W, int narrow
 // stream like a synchronous MSM entry, and returns with both idle.
 int ark_hip_test_msm_sort_stages(int curve, const void* scalars, int on_device, size_t n, int mont, int sbytes, int sbits,
                                  const int32_t knobs[8], uint64_t header[32], void* const* out, const size_t* cap_words) {
-  if (curve < 0 || curve > 4 || !scalars || !knobs || !header || n == 0 || (out && !cap_words)) return ARK_HIP_ERR_ARG;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !scalars || !knobs || !header || n == 0 || (out && !cap_words)) return ARK_HIP_ERR_ARG;
   if (sbytes == 0 && sbits != 0) return ARK_HIP_ERR_ARG;
   if (sbytes && sbits == 0) sbits = 8 * sbytes;
   const MsmKnobs k = knobs_of_record(knobs);
@@ -652,9 +574,7 @@ int ark_hip_test_msm_sort_stages(int curve, const void* scalars, int on_device, 
     ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, scalars, bytes, hipMemcpyHostToDevice, st));
     d_scalars = c->stage_a.p;
   }
-#define X(NAME) msm_sort_stages_##NAME(c->msm[0], d_scalars, n, mont, st, sbytes, sbits, k, header, out, cap_words)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
+  return ops->msm_sort_stages(c->msm[0], d_scalars, n, mont, st, sbytes, sbits, k, header, out, cap_words);
 }
 // Test hook: one MSM run as explicit pieces that share one plan and one bucket array, the buckets copied out behind every piece
 // (msm_piece_dump.cuh, which documents header, hctr_out and buckets_out).  bases / scalars: the n pairs in device memory
@@ -666,7 +586,8 @@ int ark_hip_test_msm_sort_stages(int curve, const void* scalars, int on_device, 
 int ark_hip_test_msm_pieces(int curve, const void* bases, const void* scalars, int on_device, size_t n, int mont, const size_t* sizes,
                             int npieces, const int32_t knobs[12], uint64_t header[80], uint32_t* hctr_out, size_t hctr_cap_words,
                             void* buckets_out, size_t buckets_cap_bytes, uint64_t* out_xyz) {
-  if (curve < 0 || curve > 4 || !bases || !scalars || !sizes || !knobs || !header || n == 0 || n >= (1ull << 31) || npieces < 1 ||
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops || !bases || !scalars || !sizes || !knobs || !header || n == 0 || n >= (1ull << 31) || npieces < 1 ||
       npieces > MPD_MAX_PIECES || knobs[9] || knobs[10] || knobs[11])
     return ARK_HIP_ERR_ARG;
   MsmKnobs k;
@@ -685,8 +606,10 @@ int ark_hip_test_msm_pieces(int curve, const void* bases, const void* scalars, i
   // the plan as msm_stream makes it: the window size from a sample of the host scalars where the probe is on and n is large
   MsmWidths widths{};
   bool skewed = false;
-  if (k.probe && !on_device && n >= ((size_t)1 << 19) && msm_sample_widths_dispatch(curve, scalars, n, mont, &widths) == 0)
+  if (k.probe && !on_device && n >= ((size_t)1 << 19)) {
+    ops->msm_sample_widths(scalars, n, mont, &widths);
     skewed = msm_widths_skewed(widths);
+  }
   const MsmPlan plan = msm_default_plan(curve, n, msm_scalar_bits(curve), false, skewed ? &widths : nullptr, k, /*streamed=*/true);
   size_t step = 0;
   for (int i = 0; i < npieces; i++) step = sizes[i] > step ? sizes[i] : step;
@@ -708,11 +631,8 @@ int ark_hip_test_msm_pieces(int curve, const void* bases, const void* scalars, i
     d_scalars = c->stage_a.p;
     d_bases = c->stage_b.p;
   }
-#define X(NAME)                                                                                                                    \
-  msm_piece_dump_##NAME(c->msm[0], d_bases, d_scalars, n, mont, st, sizes, npieces, plan, k, knobs[8] != 0, c->piece_buckets.p, \
-                        c->piece_ev, header, hctr_out, hctr_cap_words, buckets_out, buckets_cap_bytes, out_xyz)
-  ARK_CURVE_SWITCH(curve, X);
-#undef X
+  return ops->msm_piece_dump(c->msm[0], d_bases, d_scalars, n, mont, st, sizes, npieces, plan, k, knobs[8] != 0, c->piece_buckets.p,
+                             c->piece_ev, header, hctr_out, hctr_cap_words, buckets_out, buckets_cap_bytes, out_xyz);
 }
 // Test hook (host only, no device): the verified cache's tag of `words` u64 words -- tests/test_capi_host.py checks that
 // edits the round-4 hash could not see (a two-word edit built from its published constants) change it.

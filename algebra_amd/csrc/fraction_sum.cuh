@@ -25,7 +25,7 @@ namespace arkhip {
 // at W = 2 (93, 5 waves).  Builds of 1, 2 and 3 were timed in one session (tools/bench_fraction_sum.py): at 2^24 with
 // numerators 2 and 3 are level within their spreads (0.593 / 0.590 ms) and 1 is slower (0.675); with ones 2 is fastest
 // (0.461 against 0.532 and 0.549); 2 is also fastest at 2^20 and 2^22.  2 ships.
-// -DARK_FRAC_TREE_W=1|2|3 on capi_poly.hip and fft_<field>.hip builds the variants.
+// -DARK_FRAC_TREE_W=1|2|3 on capi_poly.hip and field_unit.hip builds the variants.
 #ifdef ARK_FRAC_TREE_W
 constexpr int FRAC_TREE_MAX_W = ARK_FRAC_TREE_W;
 constexpr bool FRAC_TREE_VARIANT_BUILD = true;

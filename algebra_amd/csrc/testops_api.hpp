@@ -1,0 +1,34 @@
+// TEST ONLY: the device-arithmetic hooks of one curve / one scalar field, as interfaces between capi_test.hip and the test
+// units (testops_curve.hip, testops_field.hip: one object per name, linked into libark_hip_test.so only).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+namespace arkhip {
+// raw-limb hooks (lazytest.cuh, relaxtest.cuh): a scalar field's unit serves its FpL / Fft29 / relaxed Fp ops; a G1 unit serves
+// those of its base field, a G2 unit the Fp2L / Fp2 / Fp2Half ops over it.  -1: not an op of this unit.
+struct TestRawOps {
+  virtual int lazy_raw_op(int op, int k, int h, const void* d_in, void* d_out, size_t n, hipStream_t s) const = 0;
+  virtual int relaxed_raw_op(int op, const void* d_in, void* d_out, size_t n, hipStream_t s) const = 0;
+};
+struct TestFieldOps : TestRawOps {};
+struct TestCurveOps : TestRawOps {
+  virtual int basefield_op(int op, const void* d_a, const void* d_b, void* d_r, size_t n, hipStream_t s) const = 0;
+  virtual int point_op(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s) const = 0;
+  // the square root in the coordinate field (pointcodec.cuh), reachable with inputs that no curve point gives
+  virtual int coord_sqrt(const void* d_in, void* d_out, void* d_ok, size_t n, hipStream_t s) const = 0;
+  virtual int lazy_acc_op(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s) const = 0;
+  // raw-digit hook of the signed 30-bit form (s30test.cuh): served by the G1 unit whose accumulate kernel runs on it, -1 elsewhere
+  virtual int s30_raw_op(int op, const void* d_in, void* d_out, size_t n, hipStream_t s) const = 0;
+  virtual int relaxed_acc_op(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s) const = 0;
+};
+
+const TestCurveOps& test_curve_ops_BN254_G1();
+const TestCurveOps& test_curve_ops_BLS12_381_G1();
+const TestCurveOps& test_curve_ops_BLS12_377_G1();
+const TestCurveOps& test_curve_ops_BLS12_377_G2();
+const TestCurveOps& test_curve_ops_BLS12_381_G2();
+const TestFieldOps& test_field_ops_BN254_FR();
+const TestFieldOps& test_field_ops_BLS12_381_FR();
+const TestFieldOps& test_field_ops_BLS12_377_FR();
+}  // namespace arkhip

@@ -1,18 +1,29 @@
 // The raw-limb TEST kernels of one scalar field (lazytest.cuh: the FpL ops and the Fft29 ops of the carry-free FFT pass;
 // relaxtest.cuh: the relaxed saturated-limb ops of the default FFT pass): compiled once per field with -DARK_TEST_FIELD=<name> and linked into libark_hip_test.so only.
+// TestFieldOpsOf is the one implementation of TestFieldOps (testops_api.hpp).
 #define ARK_LAZYTEST_FFT 1
 #include "lazytest.cuh"
 #include "relaxtest.cuh"
+#include "testops_api.hpp"
 #ifndef ARK_TEST_FIELD
 #error "compile with -DARK_TEST_FIELD=BLS12_381_FR (or another scalar field of params.hpp)"
 #endif
 #define ARK_CAT2(a, b) a##b
 #define ARK_CAT(a, b) ARK_CAT2(a, b)
 namespace arkhip {
-int ARK_CAT(test_lazy_raw_op_, ARK_TEST_FIELD)(int op, int k, int h, const void* in, void* out, size_t n, hipStream_t s) {
-  return lazytest::lazy_raw_op_launch<ARK_TEST_FIELD, true, void>(op, k, h, in, out, n, s);
-}
-int ARK_CAT(test_relaxed_raw_op_, ARK_TEST_FIELD)(int op, const void* in, void* out, size_t n, hipStream_t s) {
-  return relaxtest::relaxed_raw_op_launch<ARK_TEST_FIELD, 0>(op, in, out, n, s);
+namespace {
+template <class F>
+struct TestFieldOpsOf final : TestFieldOps {
+  int lazy_raw_op(int op, int k, int h, const void* in, void* out, size_t n, hipStream_t s) const override {
+    return lazytest::lazy_raw_op_launch<F, true, void>(op, k, h, in, out, n, s);
+  }
+  int relaxed_raw_op(int op, const void* in, void* out, size_t n, hipStream_t s) const override {
+    return relaxtest::relaxed_raw_op_launch<F, 0>(op, in, out, n, s);
+  }
+};
+}  // namespace
+const TestFieldOps& ARK_CAT(test_field_ops_, ARK_TEST_FIELD)() {
+  static const TestFieldOpsOf<ARK_TEST_FIELD> ops;
+  return ops;
 }
 }  // namespace arkhip

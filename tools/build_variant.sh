@@ -9,9 +9,12 @@ S=$R/algebra_amd/csrc
 O=/tmp/ark_variant_$name
 mkdir -p $O $R/algebra_amd/variants
 FL="-O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -Wno-unused-result -Wno-pass-failed -I$S $*"
-for u in runtime msm fft comm; do /opt/rocm/bin/hipcc $FL -DARK_HIP_DEV -c $S/capi_$u.hip -o $O/capi_$u.o & done
-/opt/rocm/bin/hipcc $FL -c $S/msm_bls12_381_g1.hip -o $O/msm.o &
-/opt/rocm/bin/hipcc $FL -c $S/fft_bls12_381_fr.hip -o $O/fft.o &
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/algebra_amd/variants/libark_hip_$name.so $O/capi_runtime.o $O/capi_msm.o $O/capi_fft.o $O/capi_comm.o $O/msm.o $O/fft.o
+CAPI="runtime msm fft poly comm points"   # CAPI_OBJS of csrc/Makefile
+pids=()
+for u in $CAPI; do /opt/rocm/bin/hipcc $FL -DARK_HIP_DEV -c $S/capi_$u.hip -o $O/capi_$u.o & pids+=($!); done
+/opt/rocm/bin/hipcc $FL -DARK_UNIT_CURVE=BLS12_381_G1 -c $S/curve_unit.hip -o $O/msm.o & pids+=($!)
+/opt/rocm/bin/hipcc $FL -DARK_UNIT_FIELD=BLS12_381_FR -c $S/field_unit.hip -o $O/fft.o & pids+=($!)
+for p in "${pids[@]}"; do wait $p; done   # a failed compile stops the build (set -e)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/algebra_amd/variants/libark_hip_$name.so \
+  $(for u in $CAPI; do echo $O/capi_$u.o; done) $O/msm.o $O/fft.o
 echo built $R/algebra_amd/variants/libark_hip_$name.so

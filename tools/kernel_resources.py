@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / occupancy table of one HIP translation unit (hipcc -Rpass-analysis=kernel-resource-usage).
-    python tools/kernel_resources.py algebra_amd/csrc/msm_bls12_381_g1.hip [filter]"""
+    python tools/kernel_resources.py algebra_amd/csrc/curve_unit.hip "" -DARK_UNIT_CURVE=BLS12_381_G1
+    python tools/kernel_resources.py SOURCE [filter [extra hipcc flags]]"""
 import re
 import subprocess
 import sys
