@@ -19,7 +19,7 @@ from .msm import (BatchMulPreprocessing, batch_mul, ChunkedPippenger, HashMapPip
                   base_cache_stats, base_cache_hash_stats, ResidentBases, pin_bases, msm_plan, msm_plan_widths, MSM_WIDTH_TOP,
                   BaseCheck, check_bases, BaseDecode, compressed_size, decompress_bases, compress_bases)
 from .domain import Radix2EvaluationDomain  # noqa: F401
-from .poly import DeviceVec, poly_mul, poly_mul_host  # noqa: F401
+from .poly import DeviceVec, poly_mul, poly_mul_host, prefix_scan_plan  # noqa: F401
 from .points import DevicePoints  # noqa: F401
 from .mle import (DenseMultilinearExtension, DeviceSegment, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_fraction_tree_launches,  # noqa: F401
                   mle_fraction_tree_plan, mle_product_tree_launches, mle_product_tree_plan, mle_quotients_plan)

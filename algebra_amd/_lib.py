@@ -147,6 +147,10 @@ SYMBOLS = {
     "ark_hip_domain_lagrange_coefficients_device": (C.c_int, [C.c_int, C.POINTER(Radix2DomainStruct), C.c_void_p, C.c_void_p]),
     "ark_hip_fr_inner_product_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ark_hip_poly_scan_plan": (C.c_int, [C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ark_hip_fr_prefix_product_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "ark_hip_fr_prefix_sum_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "ark_hip_fr_prefix_ratio_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ark_hip_prefix_scan_plan": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ark_hip_mle_fix_variables_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p]),
     "ark_hip_mle_evaluate_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]),
     "ark_hip_mle_relabel_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]),

@@ -1,5 +1,6 @@
 // C ABI of libark_hip.so: polynomial operations on device-resident vectors -- evaluation at a point, division by x - z and
-// by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products -- and dense
+// by the vanishing polynomial of a domain, the Lagrange coefficients of a domain at a point, inner products, prefix products,
+// prefix sums and ratio accumulators (prefixscan.cuh) -- and dense
 // multilinear extensions: fix_variables, evaluate, relabel, a + k x, the eq table and an opening's quotients -- and the
 // sumcheck prover's round over such tables, the product tree of a grand product and its fingerprints, the fraction tree and the
 // multiplicities of a lookup (see include/ark_hip.h; kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh,
@@ -7,6 +8,7 @@
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "polyops.cuh"
+#include "prefixscan.cuh"
 #include "mle.cuh"
 #include "mle_open.cuh"
 #include "grand_product.cuh"
@@ -155,9 +157,91 @@ inline int fr_one_any(int field, uint64_t* out) {
 #undef X
 }
 
+
+// The scan of a device vector under one monoid (prefixscan.cuh), reduce-then-scan: the tile totals of every level that has more
+// than one tile go up through `w` (room for poly_levels(n).total - 1 elements: [level 1 | level 2 | ...]), each is scanned
+// exclusively in place on the way down and is then the carries of the level below it.  The top level is one tile; its launch
+// writes the total of the whole vector to `total` when that is not null.  dst may be src.
+inline int scan_run(Context* c, const FieldOps* ops, int op, const void* src, size_t n, int exclusive, void* dst, void* total, char* w) {
+  const PolyLevels L = poly_levels(n);
+  auto vec = [&](int l) -> char* { return w + (L.off[l] - 1) * 32; };   // l >= 1
+  for (int l = 0; l + 1 < L.levels; l++)
+    if (int rc = ops->scan_tile_total(op, l == 0 ? src : vec(l), L.len[l], vec(l + 1), c->stream)) return rc;
+  for (int l = L.levels - 1; l >= 0; l--) {
+    const void* carries = l + 1 < L.levels ? vec(l + 1) : nullptr;
+    void* tot = l == L.levels - 1 ? total : nullptr;
+    if (int rc = ops->scan_tile(op, l == 0 ? src : vec(l), L.len[l], carries, l == 0 ? exclusive : 1, l == 0 ? dst : vec(l), tot, c->stream))
+      return rc;
+  }
+  return 0;
+}
+// ark_hip_fr_prefix_product_device / _sum_device
+inline int prefix_scan_entry(int op, int field, const void* d_a, size_t n, int exclusive, void* d_out, uint64_t* out_total) {
+  const FieldOps* ops = field_ops(field);
+  if (!ops || (n && (!d_a || !d_out)) || n > ((size_t)-1) / 32) return ARK_HIP_ERR_ARG;
+  if (n && d_out != d_a && ranges_overlap(d_a, n * 32, d_out, n * 32)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) {   // the empty product is one, the empty sum zero
+    if (!out_total) return 0;
+    if (op == SCAN_OP_PRODUCT) return fr_one_any(field, out_total);
+    memset(out_total, 0, 32);
+    return 0;
+  }
+  const PolyLevels L = poly_levels(n);
+  if (int rc = poly_scratch(c, L.total)) return rc;
+  char* w = (char*)c->poly_work.p;
+  if (int rc = scan_run(c, ops, op, d_a, n, exclusive ? 1 : 0, d_out, out_total ? (void*)w : nullptr, w + 32)) return rc;
+  if (out_total) return result_to_host(c, out_total);
+  return mark_producer(c);
+}
+
 }  // namespace
 
 extern "C" {
+
+int ark_hip_prefix_scan_plan(int op, size_t n, int* tile, int* levels) {
+  if (!tile || !levels || op < SCAN_OP_PRODUCT || op > SCAN_OP_RATIO) return ARK_HIP_ERR_ARG;
+  *tile = POLY_TILE;   // the ratio's two tiles pass through LDS one after the other: the same tile for every op
+  *levels = poly_scan_levels(n);
+  return 0;
+}
+
+int ark_hip_fr_prefix_product_device(int field, const void* d_a, size_t n, int exclusive, void* d_out, uint64_t* out_total) {
+  return prefix_scan_entry(SCAN_OP_PRODUCT, field, d_a, n, exclusive, d_out, out_total);
+}
+
+int ark_hip_fr_prefix_sum_device(int field, const void* d_a, size_t n, int exclusive, void* d_out, uint64_t* out_total) {
+  return prefix_scan_entry(SCAN_OP_SUM, field, d_a, n, exclusive, d_out, out_total);
+}
+
+int ark_hip_fr_prefix_ratio_device(int field, const void* d_num, const void* d_den, size_t n, void* d_out, uint64_t* out_last) {
+  const FieldOps* ops = field_ops(field);
+  if (!ops || (n && (!d_num || !d_den || !d_out)) || n > ((size_t)-1) / 32) return ARK_HIP_ERR_ARG;
+  if (n && d_out != d_num && ranges_overlap(d_num, n * 32, d_out, n * 32)) return ARK_HIP_ERR_ARG;
+  if (n && d_out != d_den && ranges_overlap(d_den, n * 32, d_out, n * 32)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) return out_last ? fr_one_any(field, out_last) : 0;
+  // [result slot | CN: the tile products of num and the levels of their scan | CD: the same for den | the inverses of CD]
+  const size_t tiles = (n + POLY_TILE - 1) / POLY_TILE;
+  const size_t per = tiles + (poly_levels(tiles).total - 1);
+  if (int rc = poly_scratch(c, 1 + 2 * per + tiles)) return rc;
+  char* w = (char*)c->poly_work.p;
+  char *cn = w + 32, *cd = cn + per * 32, *icd = cd + per * 32;
+  if (tiles > 1) {   // the product of num before every tile: a single tile starts from one
+    if (int rc = ops->scan_tile_total(SCAN_OP_PRODUCT, d_num, n, cn, c->stream)) return rc;
+    if (int rc = scan_run(c, ops, SCAN_OP_PRODUCT, cn, tiles, 1, cn, nullptr, cn + tiles * 32)) return rc;
+  }
+  // the product of den through every tile, and ONE inversion per tile (zero for zero)
+  if (int rc = ops->scan_tile_total(SCAN_OP_PRODUCT, d_den, n, cd, c->stream)) return rc;
+  if (tiles > 1)
+    if (int rc = scan_run(c, ops, SCAN_OP_PRODUCT, cd, tiles, 0, cd, nullptr, cd + tiles * 32)) return rc;
+  if (int rc = ops->fr_div(nullptr, cd, icd, tiles, c->stream)) return rc;
+  if (int rc = ops->ratio_tile(d_num, d_den, n, tiles > 1 ? cn : nullptr, cd, icd, d_out, out_last ? (void*)w : nullptr, c->stream)) return rc;
+  if (out_last) return result_to_host(c, out_last);
+  return mark_producer(c);
+}
 
 int ark_hip_poly_scan_plan(size_t n, int* tile, int* levels) {
   if (!tile || !levels) return ARK_HIP_ERR_ARG;

@@ -4,6 +4,7 @@
 #include "fft.cuh"
 #include "devops.cuh"
 #include "polyops.cuh"
+#include "prefixscan.cuh"
 #include "mle.cuh"
 #include "mle_open.cuh"
 #include "grand_product.cuh"
@@ -84,6 +85,17 @@ struct FieldOpsOf final : FieldOps {
     return fr_count_launch<Fp<F>>(indices, n, out, table_len, s);
   }
   int sumcheck_round(const SumcheckRound& rd, hipStream_t s) const override { return sumcheck_round_launch<Fp<F>>(rd, s); }
+  int scan_tile_total(int op, const void* src, size_t n, void* totals, hipStream_t s) const override {
+    return scan_tile_total_launch<Fp<F>>(op, src, n, totals, s);
+  }
+  int scan_tile(int op, const void* src, size_t n, const void* carries, int exclusive, void* dst, void* total,
+                hipStream_t s) const override {
+    return scan_tile_launch<Fp<F>>(op, src, n, carries, exclusive, dst, total, s);
+  }
+  int ratio_tile(const void* num, const void* den, size_t n, const void* cn, const void* cdi, const void* icd, void* out, void* last,
+                 hipStream_t s) const override {
+    return ratio_tile_launch<Fp<F>>(num, den, n, cn, cdi, icd, out, last, s);
+  }
   int fft_axis(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4,
                hipStream_t s) const override {
     return fft_axis_run<F>(ws, d_src, d_dst, G, cols, root4, s);

@@ -86,6 +86,11 @@ struct FieldOps {
                         hipStream_t s) const = 0;
   virtual int fr_count(const void* d_indices, size_t n, void* d_out, size_t table_len, hipStream_t s) const = 0;
   virtual int sumcheck_round(const SumcheckRound& rd, hipStream_t s) const = 0;
+  virtual int scan_tile_total(int op, const void* d_src, size_t n, void* d_totals, hipStream_t s) const = 0;
+  virtual int scan_tile(int op, const void* d_src, size_t n, const void* d_carries, int exclusive, void* d_dst, void* d_total,
+                        hipStream_t s) const = 0;
+  virtual int ratio_tile(const void* d_num, const void* d_den, size_t n, const void* d_cn, const void* d_cdi, const void* d_icd,
+                         void* d_out, void* d_last, hipStream_t s) const = 0;
   virtual int fft_roots(FftWorkspace& ws, int k, const uint64_t* root4, hipStream_t s, const uint32_t** out) const = 0;
   virtual int fft_scalars(FftWorkspace& ws, const uint64_t* base4, const uint64_t* mul4, size_t count, void* d_out,
                           hipStream_t s) const = 0;

@@ -60,6 +60,17 @@ def poly_mul(field, a, b):
     return out[: (nz[-1] + 1) if nz.size else 0]
 
 
+PREFIX_OPS = {"product": 0, "sum": 1, "ratio": 2}
+
+
+def prefix_scan_plan(op, n):
+    """(tile, levels) of DeviceVec.prefix_product / prefix_sum / prefix_ratio for n elements (ark_hip_prefix_scan_plan; host
+    only).  op: "product", "sum", "ratio" or 0, 1, 2."""
+    t, lv = C.c_int(), C.c_int()
+    check(lib().ark_hip_prefix_scan_plan(PREFIX_OPS.get(op, op), n, C.byref(t), C.byref(lv)), "ark_hip_prefix_scan_plan")
+    return t.value, lv.value
+
+
 class DeviceVec:
     """Fr vector owned by the library's allocator on the current GPU -- the Python mirror of `ark_hip::DeviceVec` (Rust:
     rust/ark-hip/src/device.rs, C++: include/ark_hip.hpp).  numpy in (`from_host`), numpy out (`to_host`), everything in
@@ -222,3 +233,35 @@ class DeviceVec:
         check(lib().ark_hip_fr_inner_product_device(self.field, self.ptr, other.ptr, self.len, out.ctypes.data_as(C.c_void_p)),
               "ark_hip_fr_inner_product_device")
         return out
+
+    # ---- running products and sums: the accumulator column of a univariate prover ---------------------------------
+    def _prefix(self, entry, exclusive, in_place):
+        out = self if in_place else DeviceVec(self.field, self.len, _zero=False)
+        total = np.zeros(4, dtype=np.uint64)
+        check(getattr(lib(), entry)(self.field, self.ptr, self.len, 1 if exclusive else 0, out.ptr, total.ctypes.data_as(C.c_void_p)),
+              entry)
+        return out, total
+
+    def prefix_product(self, exclusive=False, in_place=False):
+        """(vector, total): out[i] = prod_{j <= i} self[j] (exclusive: j < i, out[0] = 1) as a DeviceVec and the product of
+        everything as a numpy uint64[4]; waits for it.  in_place: the products overwrite this vector, which is returned."""
+        return self._prefix("ark_hip_fr_prefix_product_device", exclusive, in_place)
+
+    def prefix_sum(self, exclusive=False, in_place=False):
+        """(vector, total): out[i] = sum_{j <= i} self[j] (exclusive: j < i, out[0] = 0) and the sum of everything."""
+        return self._prefix("ark_hip_fr_prefix_sum_device", exclusive, in_place)
+
+    def prefix_ratio(self, den, out=None):
+        """(vector, last) with self the numerators: the accumulator z[0] = 1, z[i+1] = z[i] self[i] / den[i] for i < len and
+        last = prod_j self[j] / den[j], the value that is one for a valid permutation; waits for it.  out: the vector to
+        write (it may be self or den); a new one otherwise.  From the first zero denominator on the outputs are zero, as a
+        division by ark_hip_fr_div_device's rule gives."""
+        self._same(den)
+        if out is None:
+            out = DeviceVec(self.field, self.len, _zero=False)
+        else:
+            self._same(out)
+        last = np.zeros(4, dtype=np.uint64)
+        check(lib().ark_hip_fr_prefix_ratio_device(self.field, self.ptr, den.ptr, self.len, out.ptr, last.ctypes.data_as(C.c_void_p)),
+              "ark_hip_fr_prefix_ratio_device")
+        return out, last

@@ -489,6 +489,27 @@ int ark_hip_fr_inner_product_device(int field, const void* d_a, const void* d_b,
  * ark_hip_poly_divide_linear_device use for n coefficients (one level while a tile holds them all, one more per factor
  * `tile`), as ark_hip_msm_plan exposes the MSM's plan. */
 int ark_hip_poly_scan_plan(size_t n, int* tile, int* levels);
+/* Prefix scans along a vector -- the accumulator column of a univariate prover (the grand product z of a permutation or
+ * lookup argument, the running sum of a univariate logUp).  exclusive = 0: out[i] = prod_{j <= i} a[j]; exclusive = 1:
+ * out[i] = prod_{j < i} a[j], so out[0] = 1.  Exactly n elements are written.  *out_total = prod_{j < n} a[j] is a HOST
+ * element and the call waits for it (n = 0 gives one); out_total = NULL makes the call asynchronous like
+ * ark_hip_fr_*_device.  d_out == d_a (the same pointer) is allowed, any other overlap is ARK_HIP_ERR_ARG.  Zeros are just
+ * values: everything past a zero is zero. */
+int ark_hip_fr_prefix_product_device(int field, const void* d_a, size_t n, int exclusive, void* d_out, uint64_t* out_total);
+/* The same over addition: out[i] = sum_{j <= i} a[j] (exclusive: j < i, out[0] = 0), *out_total = sum_{j < n} a[j]. */
+int ark_hip_fr_prefix_sum_device(int field, const void* d_a, size_t n, int exclusive, void* d_out, uint64_t* out_total);
+/* The ratio accumulator z[0] = 1, z[i+1] = z[i] num[i] / den[i]: out[i] = prod_{j < i} num[j] / den[j] for i < n and
+ * *out_last = prod_{j < n} num[j] / den[j] -- the value that must be one for a valid permutation (HOST element, the call waits
+ * for it; NULL: asynchronous; n = 0 gives one).  One inversion per tile of ark_hip_prefix_scan_plan, not one per element.
+ * d_out may be the same pointer as d_num or as d_den; any other overlap is ARK_HIP_ERR_ARG.  A zero denominator behaves as the
+ * composition of the entries above would: out[i] = PN_i inv0(PD_i) with PN, PD the exclusive prefix products of num and den
+ * and inv0(0) = 0 as ark_hip_fr_div_device defines it -- every output up to and including the index of the first zero
+ * denominator is exact, every output after it is zero, and out_last follows the same rule. */
+int ark_hip_fr_prefix_ratio_device(int field, const void* d_num, const void* d_den, size_t n, void* d_out, uint64_t* out_last);
+/* Host only, no device needed: the tile length and the number of scan levels of the three entries above for n elements;
+ * op 0 / 1 / 2 = product / sum / ratio (anything else: ARK_HIP_ERR_ARG).  One level while a tile holds the vector, one more per
+ * factor `tile`. */
+int ark_hip_prefix_scan_plan(int op, size_t n, int* tile, int* levels);
 
 /* ---- dense multilinear extensions on device-resident evaluation tables ---------------------------------------------
  * DenseMultilinearExtension (poly/src/evaluations/multivariate/multilinear/dense.rs): a table of 2^num_vars evaluations over

@@ -675,6 +675,32 @@ class DeviceVec {
     check(ark_hip_fr_inner_product_device(FIELD_ID, p_, o.p_, len_, out.limbs.data()), "ark_hip_fr_inner_product_device");
     return out;
   }
+  // ---- running products and sums: the accumulator column of a univariate prover ----
+  // (vector, total): out[i] = prod_{j <= i} self[j] (exclusive: j < i, out[0] = 1) and the product of everything; waits for it
+  std::pair<DeviceVec, Fr> prefix_product(bool exclusive = false) const {
+    here();
+    DeviceVec out = uninit(len_);
+    Fr total;
+    check(ark_hip_fr_prefix_product_device(FIELD_ID, p_, len_, exclusive ? 1 : 0, out.p_, total.limbs.data()), "ark_hip_fr_prefix_product_device");
+    return {std::move(out), total};
+  }
+  // (vector, total): out[i] = sum_{j <= i} self[j] (exclusive: j < i, out[0] = 0) and the sum of everything; waits for it
+  std::pair<DeviceVec, Fr> prefix_sum(bool exclusive = false) const {
+    here();
+    DeviceVec out = uninit(len_);
+    Fr total;
+    check(ark_hip_fr_prefix_sum_device(FIELD_ID, p_, len_, exclusive ? 1 : 0, out.p_, total.limbs.data()), "ark_hip_fr_prefix_sum_device");
+    return {std::move(out), total};
+  }
+  // (z, last) with self the numerators: z[0] = 1, z[i+1] = z[i] self[i] / den[i] and last = prod_j self[j] / den[j], the value
+  // that is one for a valid permutation; waits for it.  From the first zero denominator on the outputs are zero (operator/=).
+  std::pair<DeviceVec, Fr> prefix_ratio(const DeviceVec& den) const {
+    same(den);
+    DeviceVec out = uninit(len_);
+    Fr last;
+    check(ark_hip_fr_prefix_ratio_device(FIELD_ID, p_, den.p_, len_, out.p_, last.limbs.data()), "ark_hip_fr_prefix_ratio_device");
+    return {std::move(out), last};
+  }
 
  private:
   void* p_ = nullptr;

@@ -192,6 +192,19 @@ extern "C" {
     pub fn ark_hip_fr_inner_product_device(field: c_int, d_a: *const c_void, d_b: *const c_void, n: usize, out: *mut u64) -> c_int;
     /// Host only: tile length and scan levels of the two entries above for `n` coefficients.
     pub fn ark_hip_poly_scan_plan(n: usize, tile: *mut c_int, levels: *mut c_int) -> c_int;
+    /// `out[i] = prod_{j <= i} a[j]` (`exclusive != 0`: `j < i`); the product of everything to `out_total` (host; null:
+    /// asynchronous).  `d_out` may be `d_a` itself.
+    pub fn ark_hip_fr_prefix_product_device(field: c_int, d_a: *const c_void, n: usize, exclusive: c_int, d_out: *mut c_void,
+                                            out_total: *mut u64) -> c_int;
+    /// The same over addition.
+    pub fn ark_hip_fr_prefix_sum_device(field: c_int, d_a: *const c_void, n: usize, exclusive: c_int, d_out: *mut c_void,
+                                        out_total: *mut u64) -> c_int;
+    /// `out[i] = prod_{j < i} num[j] / den[j]`, the product over all `j` to `out_last` (host; null: asynchronous); from the
+    /// first zero denominator on the outputs are zero.  `d_out` may be `d_num` or `d_den` itself.
+    pub fn ark_hip_fr_prefix_ratio_device(field: c_int, d_num: *const c_void, d_den: *const c_void, n: usize, d_out: *mut c_void,
+                                          out_last: *mut u64) -> c_int;
+    /// Host only: tile length and scan levels of the three entries above; `op` 0 / 1 / 2 = product / sum / ratio.
+    pub fn ark_hip_prefix_scan_plan(op: c_int, n: usize, tile: *mut c_int, levels: *mut c_int) -> c_int;
     /// `DenseMultilinearExtension::fix_variables` (multilinear/dense.rs:224-257) on a device table of `2^num_vars` elements:
     /// binds the first `dim` variables, writes `2^(num_vars - dim)` elements; `d_out` must not overlap `d_evals`.
     pub fn ark_hip_mle_fix_variables_device(field: c_int, d_evals: *const c_void, num_vars: c_uint, partial_point: *const u64,

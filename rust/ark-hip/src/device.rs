@@ -233,6 +233,33 @@ impl<F: FftField> DeviceVec<F> {
         rc(unsafe { sys::ark_hip_fr_inner_product_device(self.field, self.ptr, other.ptr, self.len, out.as_mut_ptr()) })?;
         Ok(sys::from_limbs::<F>(&out))
     }
+    /// `(vector, total)`: `out[i] = prod_{j <= i} self[j]` (`exclusive`: `j < i`, `out[0] = 1`) and the product of everything;
+    /// waits for it.
+    pub fn prefix_product(&self, exclusive: bool) -> Result<(Self, F), DeviceError> {
+        self.here()?;
+        let out = Self::alloc(self.len)?;
+        let mut total = [0u64; 4];
+        rc(unsafe { sys::ark_hip_fr_prefix_product_device(self.field, self.ptr, self.len, exclusive as i32, out.ptr, total.as_mut_ptr()) })?;
+        Ok((out, sys::from_limbs::<F>(&total)))
+    }
+    /// `(vector, total)`: `out[i] = sum_{j <= i} self[j]` (`exclusive`: `j < i`, `out[0] = 0`) and the sum of everything.
+    pub fn prefix_sum(&self, exclusive: bool) -> Result<(Self, F), DeviceError> {
+        self.here()?;
+        let out = Self::alloc(self.len)?;
+        let mut total = [0u64; 4];
+        rc(unsafe { sys::ark_hip_fr_prefix_sum_device(self.field, self.ptr, self.len, exclusive as i32, out.ptr, total.as_mut_ptr()) })?;
+        Ok((out, sys::from_limbs::<F>(&total)))
+    }
+    /// `(z, last)` with `self` the numerators: `z[0] = 1`, `z[i+1] = z[i] * self[i] / den[i]` and
+    /// `last = prod_j self[j] / den[j]`, the value that is one for a valid permutation; waits for it.  From the first zero
+    /// denominator on the outputs are zero, as `/=` divides.
+    pub fn prefix_ratio(&self, den: &Self) -> Result<(Self, F), DeviceError> {
+        self.same_len(den)?;
+        let out = Self::alloc(self.len)?;
+        let mut last = [0u64; 4];
+        rc(unsafe { sys::ark_hip_fr_prefix_ratio_device(self.field, self.ptr, den.ptr, self.len, out.ptr, last.as_mut_ptr()) })?;
+        Ok((out, sys::from_limbs::<F>(&last)))
+    }
     /// `EvaluationDomain::evaluate_all_lagrange_coefficients` (poly/src/domain/mod.rs:157-222) as a device vector: with
     /// [`DeviceVec::inner_product`] and the evaluations of `P` over `domain`, that is `P(tau)`.
     pub fn lagrange_coefficients(domain: &Radix2EvaluationDomain<F>, tau: &F) -> Result<Self, DeviceError> {
