@@ -172,6 +172,11 @@ SYMBOLS = {
                                                 C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "ark_hip_sumcheck_plan": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(C.c_int)]),
+    "ark_hip_transcript_challenge": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]),
+    "ark_hip_sumcheck_prove_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
+                                                C.c_void_p, C.c_uint, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+    "ark_hip_sumcheck_prove_plan": (C.c_int, [C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ark_hip_fft_set_kernel": (C.c_int, [C.c_int]),
     "ark_hip_fft_set_timing": (C.c_int, [C.c_int]),
     "ark_hip_fft_last_timing": (C.c_int, [C.POINTER(C.c_double)]),
@@ -225,6 +230,8 @@ TEST_SYMBOLS.update({
     "ark_hip_test_scratch_poison": (C.c_int, [C.c_uint32]),
     "ark_hip_test_scratch_report": (C.c_int, [C.c_uint32, C.POINTER(ScratchRow), C.c_size_t, C.POINTER(C.c_size_t)]),
     "ark_hip_test_scratch_selfcheck": (C.c_int, []),
+    "ark_hip_test_transcript_reduce": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ark_hip_test_transcript_challenge_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]),
 })
 TEST_LIB_PATH = os.path.join(_HERE, "libark_hip_test.so")
 

@@ -3,8 +3,8 @@
 // prefix sums and ratio accumulators (prefixscan.cuh) -- and dense
 // multilinear extensions: fix_variables, evaluate, relabel, a + k x, the eq table and an opening's quotients -- and the
 // sumcheck prover's round over such tables, the product tree of a grand product and its fingerprints, the fraction tree and the
-// multiplicities of a lookup (see include/ark_hip.h; kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh,
-// grand_product.cuh, fraction_sum.cuh).
+// multiplicities of a lookup, the Fiat-Shamir transcript and the whole sumcheck proof in one wait (see include/ark_hip.h;
+// kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh, transcript.cuh, grand_product.cuh, fraction_sum.cuh).
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "polyops.cuh"
@@ -143,6 +143,7 @@ inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 
 static_assert(SUMCHECK_MAX_TABLES == ARK_HIP_SUMCHECK_MAX_TABLES && SUMCHECK_MAX_TERMS == ARK_HIP_SUMCHECK_MAX_TERMS &&
                   SUMCHECK_MAX_DEGREE == ARK_HIP_SUMCHECK_MAX_DEGREE, "the header publishes the kernels' limits");
+static_assert(SUMCHECK_TAIL_MAX_VARS == ARK_HIP_SUMCHECK_TAIL_MAX_VARS, "the header publishes the tail's ceiling");
 static_assert(PROD_TREE_MAX_W == ARK_HIP_PRODUCT_TREE_LEVELS, "the header publishes the levels of a full launch");
 static_assert(FRAC_TREE_MAX_W == ARK_HIP_FRACTION_TREE_LEVELS || FRAC_TREE_VARIANT_BUILD, "the header publishes the levels of a full launch");
 // the field's one (R mod p) as a host element
@@ -196,6 +197,46 @@ inline int prefix_scan_entry(int op, int field, const void* d_a, size_t n, int e
   return mark_producer(c);
 }
 
+// the terms of a sumcheck call, checked: shared by the round entry and the whole-proof entry
+inline int sumcheck_terms(int field, unsigned ntables, const unsigned* term_len, const unsigned* term_tables, const uint64_t* coeffs,
+                          unsigned nterms, SumcheckTerms* tm) {
+  tm->ntables = ntables;
+  tm->nterms = nterms;
+  for (unsigned j = 0, at = 0; j < nterms; j++) {
+    const unsigned len = term_len[j];
+    if (len == 0 || len > (unsigned)SUMCHECK_MAX_DEGREE) return ARK_HIP_ERR_ARG;
+    tm->len[j] = len;
+    if (len > tm->degree) tm->degree = len;
+    for (unsigned q = 0; q < len; q++, at++) {
+      if (term_tables[at] >= ntables) return ARK_HIP_ERR_ARG;
+      tm->tab[j] |= term_tables[at] << (8 * q);
+    }
+    for (int q = 0; q < 4; q++) { tm->coeff[j].l[2 * q] = (u32)coeffs[4 * j + q]; tm->coeff[j].l[2 * q + 1] = (u32)(coeffs[4 * j + q] >> 32); }
+    if (field_is_one(field, coeffs + 4 * j)) tm->unit |= 1u << j;
+  }
+  return 0;
+}
+// the whole proof: where the tail takes over, and the two alternating sets of bound tables (halves and quarters) in d_work
+inline int prove_tail_from(unsigned num_vars, int tail_vars) {
+  const int t = tail_vars < 0 ? SUMCHECK_TAIL_DEFAULT_VARS : tail_vars;
+  return t > (int)num_vars ? (int)num_vars : t;
+}
+inline size_t prove_work_elems(unsigned num_vars, unsigned ntables) {
+  return (size_t)ntables * (((size_t)1 << (num_vars - 1)) + ((size_t)1 << (num_vars >= 2 ? num_vars - 2 : 0)));
+}
+// the transcript's one operation on the host: msg holds the state and room for the elements
+template <class FP>
+int transcript_host(u32* msg, const uint64_t* elements, unsigned count, uint64_t* out) {
+  typedef Fp<FP> F;
+  for (unsigned i = 0; i < count; i++) transcript_put_element<F>(msg, i, F::load(elements + 4 * (size_t)i));
+  transcript_challenge_words<F>(msg, count).store(out);
+  return 0;
+}
+inline int transcript_host_any(int field, u32* msg, const uint64_t* elements, unsigned count, uint64_t* out) {
+#define X(NAME) transcript_host<NAME>(msg, elements, count, out)
+  ARK_FIELD_SWITCH(field, X);
+#undef X
+}
 }  // namespace
 
 extern "C" {
@@ -661,20 +702,7 @@ int ark_hip_sumcheck_round_device(int field, const void* const* d_tables, unsign
   if (ntables == 0 || ntables > (unsigned)SUMCHECK_MAX_TABLES || nterms == 0 || nterms > (unsigned)SUMCHECK_MAX_TERMS) return ARK_HIP_ERR_ARG;
   if (num_vars == 0 || num_vars >= 64 || num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
   SumcheckRound rd = {};
-  rd.tm.ntables = ntables;
-  rd.tm.nterms = nterms;
-  for (unsigned j = 0, at = 0; j < nterms; j++) {
-    const unsigned len = term_len[j];
-    if (len == 0 || len > (unsigned)SUMCHECK_MAX_DEGREE) return ARK_HIP_ERR_ARG;
-    rd.tm.len[j] = len;
-    if (len > rd.tm.degree) rd.tm.degree = len;
-    for (unsigned q = 0; q < len; q++, at++) {
-      if (term_tables[at] >= ntables) return ARK_HIP_ERR_ARG;
-      rd.tm.tab[j] |= term_tables[at] << (8 * q);
-    }
-    for (int q = 0; q < 4; q++) { rd.tm.coeff[j].l[2 * q] = (u32)coeffs[4 * j + q]; rd.tm.coeff[j].l[2 * q + 1] = (u32)(coeffs[4 * j + q] >> 32); }
-    if (field_is_one(field, coeffs + 4 * j)) rd.tm.unit |= 1u << j;
-  }
+  if (int rc = sumcheck_terms(field, ntables, term_len, term_tables, coeffs, nterms, &rd.tm)) return rc;
   const size_t n = (size_t)1 << num_vars;
   for (unsigned k = 0; k < ntables; k++) {
     if (!d_tables[k] || (r_prev && !d_out_tables[k])) return ARK_HIP_ERR_ARG;
@@ -703,6 +731,81 @@ int ark_hip_sumcheck_round_device(int field, const void* const* d_tables, unsign
   rd.partials = (char*)c->poly_work.p + SUMCHECK_EVALS * 32;
   if (int rc = ops->sumcheck_round(rd, c->stream)) return rc;
   ARK_HIP_TRY(hipMemcpyAsync(out_evals, c->poly_work.p, (size_t)(degree + 1) * 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- the transcript and the whole proof in one wait ----
+int ark_hip_transcript_challenge(int field, uint8_t* state, const uint64_t* elements, unsigned count, uint64_t* out_challenge) {
+  if (!field_ops(field) || !state || !out_challenge || (count && !elements)) return ARK_HIP_ERR_ARG;
+  if (count > (1u << 24)) return ARK_HIP_ERR_ARG;
+  std::vector<u32> msg(transcript_words(count));
+  memcpy(msg.data(), state, 32);
+  const int rc = transcript_host_any(field, msg.data(), elements, count, out_challenge);
+  if (rc == 0) memcpy(state, msg.data(), 32);
+  return rc;
+}
+
+int ark_hip_sumcheck_prove_plan(unsigned num_vars, unsigned ntables, int tail_vars, size_t* work_elems, int* launches, int* tail_from) {
+  if (!work_elems || !launches || !tail_from || num_vars == 0 || num_vars > 58) return ARK_HIP_ERR_ARG;
+  if (ntables == 0 || ntables > (unsigned)SUMCHECK_MAX_TABLES || tail_vars < -1 || tail_vars > SUMCHECK_TAIL_MAX_VARS) return ARK_HIP_ERR_ARG;
+  const int tf = prove_tail_from(num_vars, tail_vars);
+  *work_elems = prove_work_elems(num_vars, ntables);
+  *launches = sumcheck_prove_launches(num_vars, tf);
+  *tail_from = tf;
+  return 0;
+}
+
+int ark_hip_sumcheck_prove_device(int field, const void* const* d_tables, unsigned ntables, unsigned num_vars, const unsigned* term_len,
+                                  const unsigned* term_tables, const uint64_t* coeffs, unsigned nterms, uint8_t* state, int tail_vars,
+                                  void* d_work, uint64_t* out_rounds, uint64_t* out_point, uint64_t* out_finals, uint64_t* out_value) {
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_tables || !term_len || !term_tables || !coeffs || !state) return ARK_HIP_ERR_ARG;
+  if (!out_rounds || !out_point || !out_finals || !out_value) return ARK_HIP_ERR_ARG;
+  if (ntables == 0 || ntables > (unsigned)SUMCHECK_MAX_TABLES || nterms == 0 || nterms > (unsigned)SUMCHECK_MAX_TERMS) return ARK_HIP_ERR_ARG;
+  if (num_vars == 0 || num_vars > 58) return ARK_HIP_ERR_ARG;   // the table's bytes must fit a size_t
+  if (tail_vars < -1 || tail_vars > SUMCHECK_TAIL_MAX_VARS) return ARK_HIP_ERR_ARG;
+  SumcheckProve pv = {};
+  if (int rc = sumcheck_terms(field, ntables, term_len, term_tables, coeffs, nterms, &pv.tm)) return rc;
+  const size_t n = (size_t)1 << num_vars, work = prove_work_elems(num_vars, ntables);
+  if (!d_work) return ARK_HIP_ERR_ARG;   // work is never zero: the one-element tables lie there
+  for (unsigned k = 0; k < ntables; k++) {
+    if (!d_tables[k] || ranges_overlap(d_tables[k], n * 32, d_work, work * 32)) return ARK_HIP_ERR_ARG;
+    pv.src[k] = (const char*)d_tables[k];
+  }
+  const size_t half = (size_t)1 << (num_vars - 1), quarter = (size_t)1 << (num_vars >= 2 ? num_vars - 2 : 0);
+  for (unsigned k = 0; k < ntables; k++) {
+    pv.set[0][k] = (char*)d_work + k * half * 32;
+    pv.set[1][k] = (char*)d_work + (ntables * half + k * quarter) * 32;
+  }
+  pv.num_vars = num_vars;
+  pv.tail_from = prove_tail_from(num_vars, tail_vars);
+  memcpy(pv.state0.w, state, 32);
+  const unsigned degree = pv.tm.degree;
+  unsigned blocks;
+  size_t ppl;
+  sumcheck_geometry((int)num_vars, &blocks, &ppl);   // the first round has the most workgroups
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  // [sums | one partial per workgroup and t | cell | state | point | rounds | finals | value]
+  const size_t o_cell = (size_t)SUMCHECK_EVALS * (1 + (blocks > 1 ? blocks : 0)), o_point = o_cell + 2, o_rounds = o_point + num_vars,
+               o_finals = o_rounds + (size_t)num_vars * (degree + 1), o_value = o_finals + ntables;
+  if (int rc = poly_scratch(c, o_value + 1)) return rc;
+  char* w = (char*)c->poly_work.p;
+  pv.sums = w;
+  pv.partials = w + SUMCHECK_EVALS * 32;
+  pv.cell = w + o_cell * 32;
+  pv.state = w + (o_cell + 1) * 32;
+  pv.point = w + o_point * 32;
+  pv.rounds = w + o_rounds * 32;
+  pv.finals = w + o_finals * 32;
+  pv.value = w + o_value * 32;
+  if (int rc = ops->sumcheck_prove(pv, c->stream)) return rc;
+  ARK_HIP_TRY(hipMemcpyAsync(out_rounds, pv.rounds, (size_t)num_vars * (degree + 1) * 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipMemcpyAsync(out_point, pv.point, (size_t)num_vars * 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipMemcpyAsync(out_finals, pv.finals, (size_t)ntables * 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipMemcpyAsync(out_value, pv.value, 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipMemcpyAsync(state, pv.state, 32, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

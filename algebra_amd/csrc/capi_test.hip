@@ -15,6 +15,7 @@
 #include "s30test_api.hpp"
 #include "testops_api.hpp"
 #include "scratch_list.hpp"
+#include "transcript.cuh"
 #include <map>
 #include <string>
 using namespace arkhip;
@@ -468,6 +469,51 @@ int ark_hip_test_relaxed_raw_op(int field, int op, const uint32_t* in, uint32_t*
   const int rc = ops->relaxed_raw_op(op, c->stage_a.p, c->stage_c.p, n, c->stream);
   if (rc) return rc == -1 ? ARK_HIP_ERR_ARG : rc;
   ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, obytes, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// the transcript's 512-bit reduction alone: on the host, or in a one-lane kernel
+extern "C++" {
+template <class FP>
+int transcript_reduce_host(const uint8_t* bytes64, uint64_t* out) {
+  u32 w[16];
+  memcpy(w, bytes64, 64);
+  transcript_reduce512<Fp<FP>>(w).store(out);
+  return 0;
+}
+}
+int ark_hip_test_transcript_reduce(int field, const uint8_t* bytes64, int on_device, uint64_t* out) {
+  const TestFieldOps* ops = test_field_ops(field);
+  if (!ops || !bytes64 || !out) return ARK_HIP_ERR_ARG;
+  if (!on_device) {
+#define X(NAME) transcript_reduce_host<NAME>(bytes64, out)
+    ARK_FIELD_SWITCH(field, X);
+#undef X
+  }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (c->stage_a.ensure(64) || c->stage_c.ensure(32)) return ARK_HIP_ERR_NOMEM;
+  ARK_HIP_TRY(hipMemcpyAsync(c->stage_a.p, bytes64, 64, hipMemcpyHostToDevice, c->stream));
+  if (int rc = ops->transcript_reduce(c->stage_a.p, c->stage_c.p, c->stream)) return rc;
+  ARK_HIP_TRY(hipMemcpyAsync(out, c->stage_c.p, 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+// the whole challenge in a one-lane kernel: the counterpart of ark_hip_transcript_challenge
+int ark_hip_test_transcript_challenge_device(int field, uint8_t* state, const uint64_t* elements, unsigned count, uint64_t* out) {
+  const TestFieldOps* ops = test_field_ops(field);
+  if (!ops || !state || !out || (count && !elements) || count > (1u << 16)) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  const size_t mbytes = (size_t)transcript_words(count) * 4, ebytes = (size_t)count * 32;
+  if (c->stage_a.ensure(mbytes) || c->stage_c.ensure(ebytes + 32)) return ARK_HIP_ERR_NOMEM;
+  char *msg = (char*)c->stage_a.p, *el = (char*)c->stage_c.p, *res = el + ebytes;   // [message] and [elements | result]
+  ARK_HIP_TRY(hipMemcpyAsync(msg, state, 32, hipMemcpyHostToDevice, c->stream));
+  if (count) ARK_HIP_TRY(hipMemcpyAsync(el, elements, ebytes, hipMemcpyHostToDevice, c->stream));
+  if (int rc = ops->transcript_challenge(msg, el, count, res, c->stream)) return rc;
+  ARK_HIP_TRY(hipMemcpyAsync(out, res, 32, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipMemcpyAsync(state, msg, 32, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -85,6 +85,7 @@ struct FieldOpsOf final : FieldOps {
     return fr_count_launch<Fp<F>>(indices, n, out, table_len, s);
   }
   int sumcheck_round(const SumcheckRound& rd, hipStream_t s) const override { return sumcheck_round_launch<Fp<F>>(rd, s); }
+  int sumcheck_prove(const SumcheckProve& pv, hipStream_t s) const override { return sumcheck_prove_run<Fp<F>>(pv, s); }
   int scan_tile_total(int op, const void* src, size_t n, void* totals, hipStream_t s) const override {
     return scan_tile_total_launch<Fp<F>>(op, src, n, totals, s);
   }

@@ -19,6 +19,7 @@ struct PolyPowers;
 struct MlePoint;
 struct FrConst;
 struct SumcheckRound;
+struct SumcheckProve;
 struct FrLincomb;
 
 // The device operations of one curve.  curve_unit.hip implements every member once, as a template over the curve; a member that
@@ -86,6 +87,7 @@ struct FieldOps {
                         hipStream_t s) const = 0;
   virtual int fr_count(const void* d_indices, size_t n, void* d_out, size_t table_len, hipStream_t s) const = 0;
   virtual int sumcheck_round(const SumcheckRound& rd, hipStream_t s) const = 0;
+  virtual int sumcheck_prove(const SumcheckProve& pv, hipStream_t s) const = 0;
   virtual int scan_tile_total(int op, const void* d_src, size_t n, void* d_totals, hipStream_t s) const = 0;
   virtual int scan_tile(int op, const void* d_src, size_t n, const void* d_carries, int exclusive, void* d_dst, void* d_total,
                         hipStream_t s) const = 0;

@@ -11,7 +11,13 @@ struct TestRawOps {
   virtual int lazy_raw_op(int op, int k, int h, const void* d_in, void* d_out, size_t n, hipStream_t s) const = 0;
   virtual int relaxed_raw_op(int op, const void* d_in, void* d_out, size_t n, hipStream_t s) const = 0;
 };
-struct TestFieldOps : TestRawOps {};
+struct TestFieldOps : TestRawOps {
+  // the transcript of transcript.cuh in a one-lane kernel: the 512-bit reduction alone (16 words -> one element), and the whole
+  // challenge (d_msg: transcript_words(count) words with the state in front, d_elements: count Montgomery elements;
+  // d_out: the element; the new state replaces d_msg's first eight words)
+  virtual int transcript_reduce(const void* d_words16, void* d_out, hipStream_t s) const = 0;
+  virtual int transcript_challenge(void* d_msg, const void* d_elements, unsigned count, void* d_out, hipStream_t s) const = 0;
+};
 struct TestCurveOps : TestRawOps {
   virtual int basefield_op(int op, const void* d_a, const void* d_b, void* d_r, size_t n, hipStream_t s) const = 0;
   virtual int point_op(int kind, const void* d_acc, const void* d_other, void* d_out, size_t n, hipStream_t s) const = 0;

@@ -24,7 +24,7 @@ from ._lib import check, lib
 from .grand_product import _one
 from .mle import DenseMultilinearExtension, DeviceSegment, _element
 from .poly import DeviceVec
-from .sumcheck import ListOfProducts
+from .sumcheck import ListOfProducts, sumcheck_prove_plan
 
 # what `challenge` gets as its round when the layer's batching challenge lambda is asked for, before the layer's sumcheck
 # (None asks for the layer's tau, as in GrandProduct.prove); the C++ and Rust mirrors use -2 (LAMBDA_ROUND) and -1
@@ -55,6 +55,23 @@ class FractionalSum:
         values are round i's evaluations of the layer's sumcheck; with round = LAMBDA there are no values and the answer is
         the layer's batching challenge; with round = None they are the layer's values and the answer is the layer's tau.
         The tables and the trees are not written."""
+        return self._prove(challenge, lambda lp, k: lp.prove(lambda i, evals: challenge(k, i, evals)))
+
+    def prove_device(self, transcript, tail_vars=None):
+        """The same proof with every challenge from `transcript` (algebra_amd.Transcript): each layer's sumcheck is one
+        ListOfProducts.prove_device -- one wait per layer instead of one per round --; lambda (no values), the layer's values
+        and the root's go through transcript.challenge on the host.  One work vector serves every layer.
+        tail_vars: as in ListOfProducts.prove_device, for every layer."""
+        nu = self.den.num_vars
+        work = DeviceVec(self.den.field, sumcheck_prove_plan(nu - 1, 5)[0], _zero=False) if nu >= 2 else None
+        try:
+            return self._prove(lambda k, rnd, values: transcript.challenge(values), lambda lp, k: lp.prove_device(transcript, tail_vars, _work=work))
+        finally:
+            if work is not None:
+                work.free()
+
+    def _prove(self, challenge, sumcheck):
+        """the layers; sumcheck(list of products, layer) -> the layer's SumcheckProof"""
         num, den, nu = self.num, self.den, self.den.num_vars
         n = 1 << nu
         # the trees are this call's own vectors: released on every way out, also when the challenge or a round raises
@@ -88,7 +105,7 @@ class FractionalSum:
                         lp.add_product([eq, d1], one)
                         lp.add_product([eq, d0], one)
                         lp.add_product([eq, d0, d1], lam)
-                        proof = lp.prove(lambda i, evals, k=k: challenge(k, i, evals))
+                        proof = sumcheck(lp, k)
                         values = proof.final_evaluations[[2, 1]].copy()           # tables: eq, d1, d0
                     else:
                         n0 = DenseMultilinearExtension(k, DeviceSegment(nup, 0, h))
@@ -96,7 +113,7 @@ class FractionalSum:
                         lp.add_product([eq, n0, d1], one)
                         lp.add_product([eq, n1, d0], one)
                         lp.add_product([eq, d0, d1], lam)
-                        proof = lp.prove(lambda i, evals, k=k: challenge(k, i, evals))
+                        proof = sumcheck(lp, k)
                         values = proof.final_evaluations[[1, 3, 4, 2]].copy()     # tables: eq, n0, d1, n1, d0
                 finally:
                     lp.free()

@@ -17,7 +17,7 @@ import numpy as np
 from ._lib import check, lib
 from .mle import DenseMultilinearExtension, DeviceSegment, _element
 from .poly import DeviceVec
-from .sumcheck import ListOfProducts
+from .sumcheck import ListOfProducts, sumcheck_prove_plan
 
 
 def _one(field):
@@ -49,6 +49,23 @@ class GrandProduct:
         """`challenge(layer, round, values)` returns the verifier's next element (uint64[4], Montgomery): with round = i the
         values are round i's evaluations of the layer's sumcheck, with round = None they are the layer's pair (left, right)
         and the answer is the layer's tau.  The table and the tree are not written."""
+        return self._prove(challenge, lambda lp, k: lp.prove(lambda i, evals: challenge(k, i, evals)))
+
+    def prove_device(self, transcript, tail_vars=None):
+        """The same proof with every challenge from `transcript` (algebra_amd.Transcript): each layer's sumcheck is one
+        ListOfProducts.prove_device -- one wait per layer instead of one per round --, the layer's pair goes through
+        transcript.challenge on the host.  One work vector serves every layer.
+        tail_vars: as in ListOfProducts.prove_device, for every layer."""
+        nu = self.f.num_vars
+        work = DeviceVec(self.f.field, sumcheck_prove_plan(nu - 1, 3)[0], _zero=False) if nu >= 2 else None
+        try:
+            return self._prove(lambda k, rnd, values: transcript.challenge(values), lambda lp, k: lp.prove_device(transcript, tail_vars, _work=work))
+        finally:
+            if work is not None:
+                work.free()
+
+    def _prove(self, challenge, sumcheck):
+        """the layers; sumcheck(list of products, layer) -> the layer's SumcheckProof"""
         f, nu = self.f, self.f.num_vars
         n = 1 << nu
         # the tree is this call's own vector: released on every way out, also when the challenge or a round raises
@@ -73,7 +90,7 @@ class GrandProduct:
                     left = DenseMultilinearExtension(k, DeviceSegment(up, 0, 1 << k))
                     right = DenseMultilinearExtension(k, DeviceSegment(up, 1 << k, 1 << k))
                     lp.add_product([eq, left, right], one)
-                    proof = lp.prove(lambda i, evals, k=k: challenge(k, i, evals))
+                    proof = sumcheck(lp, k)
                 finally:
                     lp.free()
                     eq.free()

@@ -4,8 +4,10 @@ list of products of shared `DenseMultilinearExtension`s, each with a coefficient
 
     sum_b sum_j c_j prod_{k in term j} f_k(b),
 
-and `round` is one call of ark_hip_sumcheck_round_device on the tables where they lie.  No arithmetic happens here and
-nothing is hashed: the challenges come from the caller, verification is the caller's (the tests carry a verifier)."""
+and `round` is one call of ark_hip_sumcheck_round_device on the tables where they lie.  No arithmetic happens here; with
+`round` and `prove` nothing is hashed either: the challenges come from the caller.  `prove_device` is the whole proof in one
+wait, its challenges derived on the device from a `Transcript` (algebra_amd.transcript).  Verification
+is the caller's (the tests carry a verifier)."""
 import ctypes as C
 
 import numpy as np
@@ -28,6 +30,15 @@ def sumcheck_plan(num_vars, ntables=1, degree=1, fused=False):
     check(lib().ark_hip_sumcheck_plan(num_vars, ntables, degree, 1 if fused else 0, C.byref(b), C.byref(p), C.byref(s)),
           "ark_hip_sumcheck_plan")
     return b.value, p.value, s.value
+
+
+def sumcheck_prove_plan(num_vars, ntables=1, tail_vars=None):
+    """(elements of work vector, kernel launches, variables left when the one-workgroup tail takes over -- 0: no tail) of
+    prove_device over 2^num_vars-element tables; tail_vars None: the library's measured default"""
+    w, l, t = C.c_size_t(), C.c_int(), C.c_int()
+    check(lib().ark_hip_sumcheck_prove_plan(num_vars, ntables, -1 if tail_vars is None else tail_vars, C.byref(w), C.byref(l), C.byref(t)),
+          "ark_hip_sumcheck_prove_plan")
+    return w.value, l.value, t.value
 
 
 class SumcheckProof:
@@ -160,6 +171,43 @@ class ListOfProducts:
             evals = self.round(r, fused=(self._m >= FUSED_FROM_NUM_VARS) if fused is None else fused)
         finals = self.bound_tables()[:, 0, :]
         return SumcheckProof(rounds, np.stack(point), finals, evals[0].copy())
+
+    def prove_device(self, transcript, tail_vars=None, _work=None):
+        """The whole proof in one wait: what prove() returns when its challenge is
+        `transcript.challenge(evals)`, with the challenges derived on the device -- one call of
+        ark_hip_sumcheck_prove_device.  Advances `transcript` by the nu challenges.  The work vector for the bound tables is
+        allocated and freed here (_work: a caller's DeviceVec of at least sumcheck_prove_plan's elements, kept across proofs).
+        tail_vars: see sumcheck_prove_plan; tests move the seam with it."""
+        if self._cur is not None:
+            raise ValueError("rounds have been run on this list")
+        if not self.products:
+            raise ValueError("no products")
+        if self.num_vars == 0:
+            raise ValueError("nothing to sum over: num_vars == 0")
+        if transcript.field != self.field:
+            raise ValueError("the transcript is over another field")
+        nt, nterms, nu, d1 = len(self.tables), len(self.products), self.num_vars, self.degree + 1
+        elems = sumcheck_prove_plan(nu, nt, tail_vars)[0]
+        if _work is not None and _work.len < elems:
+            raise ValueError("the work vector has %d elements, %d are needed" % (_work.len, elems))
+        work = _work if _work is not None else DeviceVec(self.field, elems, _zero=False)
+        try:
+            tabs = (C.c_void_p * nt)(*[t.evaluations.ptr.value for t in self.tables])
+            lens = (C.c_uint * nterms)(*[len(ix) for _, ix in self.products])
+            flat = [i for _, ix in self.products for i in ix]
+            term_tables = (C.c_uint * len(flat))(*flat)
+            coeffs = np.ascontiguousarray(np.stack([c for c, _ in self.products]), dtype=np.uint64)
+            rounds, point = np.zeros((nu, d1, 4), dtype=np.uint64), np.zeros((nu, 4), dtype=np.uint64)
+            finals, value = np.zeros((nt, 4), dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+            check(lib().ark_hip_sumcheck_prove_device(self.field, tabs, nt, nu, lens, term_tables, coeffs.ctypes.data_as(C.c_void_p), nterms,
+                                                      C.cast(transcript._state, C.c_void_p), -1 if tail_vars is None else tail_vars, work.ptr,
+                                                      rounds.ctypes.data_as(C.c_void_p), point.ctypes.data_as(C.c_void_p),
+                                                      finals.ctypes.data_as(C.c_void_p), value.ctypes.data_as(C.c_void_p)),
+                  "ark_hip_sumcheck_prove_device")
+        finally:
+            if _work is None:
+                work.free()
+        return SumcheckProof([rounds[i] for i in range(nu)], point, finals, value)
 
     def free(self):
         """releases the list's own bound tables (not the caller's extensions)"""

@@ -664,6 +664,36 @@ int ark_hip_sumcheck_round_device(int field, const void* const* d_tables, unsign
 int ark_hip_sumcheck_plan(unsigned num_vars, unsigned ntables, unsigned degree, int fused, int* blocks, int* pairs_per_lane,
                           int* stages);
 
+/* ---- the Fiat-Shamir transcript and the whole sumcheck proof in one wait ----------------------
+ * The transcript's state is 32 bytes, initialised by the caller (a label, a statement hash).  Its one operation absorbs
+ * count >= 0 elements and returns a challenge:
+ *   msg   = state | u32_le(count) | le32(e_0) | ... | le32(e_{count-1})    (le32: the canonical value, 32 bytes little-endian)
+ *   out   = SHAKE256(msg, 96 bytes);   state = out[0:32];   challenge = int_le(out[32:96]) mod r, in Montgomery form.
+ * Host only, no device needed; state is updated in place.  elements: count Montgomery elements, canonical residues like
+ * every other entry's -- this is NOT checked.  ARK_HIP_ERR_ARG: an unknown field, a null state or out_challenge, null
+ * elements with count > 0, count > 2^24 (the message is built in host memory: 512 MiB at that count). */
+int ark_hip_transcript_challenge(int field, uint8_t* state, const uint64_t* elements, unsigned count, uint64_t* out_challenge);
+/* The largest number of variables the one-workgroup tail of ark_hip_sumcheck_prove_device takes. */
+#define ARK_HIP_SUMCHECK_TAIL_MAX_VARS 14
+/* The whole proof of the sum of ark_hip_sumcheck_round_device's list of products over 2^num_vars-element tables, the
+ * challenges derived on the device: exactly what num_vars + 1 calls of the round entry give when the challenge after round
+ * i is ark_hip_transcript_challenge(state, evals_i, D + 1).  out_rounds: num_vars x (D + 1) elements; out_point: the
+ * num_vars challenges; out_finals: f_k(point) per table; out_value: sum_j c_j prod_k f_k(point); state (HOST, in/out): the
+ * state after the last challenge -- the final values are not absorbed.  All outputs are HOST; the call queues everything
+ * and waits once.  The caller's tables are never written.  d_work: work_elems elements (ark_hip_sumcheck_prove_plan) for
+ * two alternating sets of bound tables.  tail_vars: once at most that many variables are left one workgroup runs every
+ * remaining round in one launch; 0 disables that, -1 takes the library's measured default.
+ * ARK_HIP_ERR_ARG, before any device is touched: every argument error of the round entry; a null state, output or d_work;
+ * tail_vars outside -1 .. ARK_HIP_SUMCHECK_TAIL_MAX_VARS; d_work overlapping an input table. */
+int ark_hip_sumcheck_prove_device(int field, const void* const* d_tables, unsigned ntables, unsigned num_vars,
+                                  const unsigned* term_len, const unsigned* term_tables, const uint64_t* coeffs, unsigned nterms,
+                                  uint8_t* state, int tail_vars, void* d_work, uint64_t* out_rounds, uint64_t* out_point,
+                                  uint64_t* out_finals, uint64_t* out_value);
+/* Host only: *work_elems = ntables (2^(num_vars-1) + 2^max(num_vars-2, 0)); *launches: kernels the proof queues;
+ * *tail_from: the variables left when the tail takes over (tail_vars resolved and clamped to num_vars; 0: no tail). */
+int ark_hip_sumcheck_prove_plan(unsigned num_vars, unsigned ntables, int tail_vars, size_t* work_elems, int* launches,
+                                int* tail_from);
+
 /* ---- one process per GPU: RCCL inside the library ---------------------------------------------------------------
  * The reference chunks an MSM by base range and sums the chunk results (variable_base/mod.rs:521-557); an FFT shards by
  * coefficient range with ONE transpose between two rounds of local butterflies (the four-step form of the radix-2
@@ -848,6 +878,11 @@ typedef struct ark_hip_scratch_row {
 int ark_hip_test_scratch_poison(uint32_t word);
 int ark_hip_test_scratch_report(uint32_t word, ark_hip_scratch_row* rows, size_t cap_rows, size_t* n_rows);
 int ark_hip_test_scratch_selfcheck(void);
+/* The transcript (csrc/transcript.cuh) piece by piece: the 512-bit reduction of 64 little-endian bytes alone, on the host or
+ * (on_device) in a one-lane kernel; and the whole challenge in a one-lane kernel, the counterpart of
+ * ark_hip_transcript_challenge. */
+int ark_hip_test_transcript_reduce(int field, const uint8_t* bytes64, int on_device, uint64_t* out);
+int ark_hip_test_transcript_challenge_device(int field, uint8_t* state, const uint64_t* elements, unsigned count, uint64_t* out);
 
 #endif /* ARK_HIP_TEST_HOOKS */
 

@@ -1035,6 +1035,25 @@ struct SumcheckProof {
   std::vector<Fr> final_evaluations;     // f_k(point), the tables in the order they were first added
   Fr final_value;                        // sum_j c_j prod_k f_k(point): what the verifier's last check compares
 };
+// The Fiat-Shamir transcript of DESIGN.md section 23: 32 bytes of state the caller initialises; challenge() is one call of
+// the host entry ark_hip_transcript_challenge (state | count | elements through SHAKE256; needs no device).
+template <int FIELD_ID>
+class Transcript {
+ public:
+  explicit Transcript(const std::array<uint8_t, 32>& seed) : state_(seed) {}
+  const std::array<uint8_t, 32>& state() const { return state_; }
+  uint8_t* state_ptr() { return state_.data(); }
+  Fr challenge(const std::vector<Fr>& elements = {}) {
+    Fr out;
+    check(ark_hip_transcript_challenge(FIELD_ID, state_.data(), elements.empty() ? nullptr : (const uint64_t*)elements.data(),
+                                       (unsigned)elements.size(), out.limbs.data()),
+          "ark_hip_transcript_challenge");
+    return out;
+  }
+
+ private:
+  std::array<uint8_t, 32> state_;
+};
 template <int FIELD_ID>
 class ListOfProducts {
  public:
@@ -1103,6 +1122,31 @@ class ListOfProducts {
       out.final_evaluations.push_back(v);
     }
     out.final_value = evals[0];
+    return out;
+  }
+  // The whole proof in one wait: what prove() returns when challenge(i, evals) is transcript.challenge(evals), with the
+  // challenges derived on the device (one call of ark_hip_sumcheck_prove_device).  Advances the transcript; allocates and frees
+  // its own work vector.  tail_vars: -1 the library's default, 0 no one-workgroup tail, else the variables it starts at.
+  SumcheckProof<FIELD_ID> prove_device(Transcript<FIELD_ID>& transcript, int tail_vars = -1) {
+    if (started_ || num_vars_ == 0 || lens_.empty()) throw Error(ARK_HIP_ERR_ARG, "rounds have been run on this list, no products, or num_vars == 0");
+    size_t work_elems = 0;
+    int launches = 0, tail_from = 0;
+    check(ark_hip_sumcheck_prove_plan((unsigned)num_vars_, (unsigned)tables_.size(), tail_vars, &work_elems, &launches, &tail_from),
+          "ark_hip_sumcheck_prove_plan");
+    Vec work = Vec::uninit(work_elems);
+    std::vector<const void*> tables;
+    for (const Mle* m : tables_) tables.push_back(m->evaluations().device_ptr());
+    const size_t d1 = degree_ + 1;
+    std::vector<Fr> rounds(num_vars_ * d1);
+    SumcheckProof<FIELD_ID> out;
+    out.point.resize(num_vars_);
+    out.final_evaluations.resize(tables_.size());
+    check(ark_hip_sumcheck_prove_device(FIELD_ID, tables.data(), (unsigned)tables.size(), (unsigned)num_vars_, lens_.data(), flat_.data(),
+                                        (const uint64_t*)coeffs_.data(), (unsigned)lens_.size(), transcript.state_ptr(), tail_vars,
+                                        work.device_ptr(), (uint64_t*)rounds.data(), (uint64_t*)out.point.data(),
+                                        (uint64_t*)out.final_evaluations.data(), out.final_value.limbs.data()),
+          "ark_hip_sumcheck_prove_device");
+    for (size_t i = 0; i < num_vars_; i++) out.rounds.emplace_back(rounds.begin() + i * d1, rounds.begin() + (i + 1) * d1);
     return out;
   }
 

@@ -262,6 +262,19 @@ extern "C" {
     /// Host only: workgroups, pairs of rows per lane and reduction stages of that round.
     pub fn ark_hip_sumcheck_plan(num_vars: c_uint, ntables: c_uint, degree: c_uint, fused: c_int, blocks: *mut c_int,
                                  pairs_per_lane: *mut c_int, stages: *mut c_int) -> c_int;
+    /// The transcript's one operation (host only): `state | u32_le(count) | le32(elements)` through SHAKE256 to 96 bytes: the new
+    /// `state` (32 bytes, in place) and a challenge reduced mod r, Montgomery.  `elements` must be canonical residues (not checked).
+    pub fn ark_hip_transcript_challenge(field: c_int, state: *mut u8, elements: *const u64, count: c_uint, out_challenge: *mut u64) -> c_int;
+    /// The whole sumcheck proof in one wait, the challenges derived on the device from `state` (HOST, in/out) as
+    /// `ark_hip_transcript_challenge(state, evals_i, D + 1)` would.  Outputs are HOST: `num_vars x (D + 1)`, `num_vars`, `ntables`
+    /// and 1 elements.  `d_work`: `work_elems` elements of `ark_hip_sumcheck_prove_plan`; `tail_vars`: -1 the default, 0 no tail.
+    pub fn ark_hip_sumcheck_prove_device(field: c_int, d_tables: *const *const c_void, ntables: c_uint, num_vars: c_uint,
+                                         term_len: *const c_uint, term_tables: *const c_uint, coeffs: *const u64, nterms: c_uint,
+                                         state: *mut u8, tail_vars: c_int, d_work: *mut c_void, out_rounds: *mut u64,
+                                         out_point: *mut u64, out_finals: *mut u64, out_value: *mut u64) -> c_int;
+    /// Host only: the work vector's elements, the kernel launches and where the one-workgroup tail takes over.
+    pub fn ark_hip_sumcheck_prove_plan(num_vars: c_uint, ntables: c_uint, tail_vars: c_int, work_elems: *mut usize,
+                                       launches: *mut c_int, tail_from: *mut c_int) -> c_int;
     /// `r[i] = a[i] * k`, `k`: one Montgomery element in host memory (read before the call returns).
     pub fn ark_hip_fr_scale_device(field: c_int, d_a: *const c_void, k: *const u64, d_r: *mut c_void, n: usize) -> c_int;
     pub fn ark_hip_fft_in_place_degree_aware_device(field: c_int, dom: *const ark_hip_radix2_domain, d_data: *mut c_void,

@@ -40,7 +40,7 @@ pub use ark_hip_sys::{BLS12_377_G1, BLS12_377_G2, BLS12_381_G1, BLS12_381_G2, BN
 pub use device::{DeviceError, DeviceEvaluations, DeviceVec};
 pub use points::DevicePoints;
 pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension, FractionTree, ProductTree, Quotients};
-pub use sumcheck::{ListOfProducts, SumcheckProof};
+pub use sumcheck::{ListOfProducts, SumcheckProof, Transcript};
 pub use grand_product::{GrandProduct, GrandProductProof};
 pub use fraction_sum::{FractionalSum, FractionalSumProof};
 pub use msm::{check_bases, compress_bases, decompress_bases, serve_group_coefficients, sw_msm, sw_msm_bigint, BaseCheck, HipServed};

@@ -34,6 +34,34 @@ pub struct SumcheckProof<F: FftField> {
     pub final_value: F,
 }
 
+/// The Fiat-Shamir transcript of the device sumcheck: 32 bytes of state the caller initialises; [`Transcript::challenge`] is
+/// one call of the host entry `ark_hip_transcript_challenge` (`state | count | elements` through SHAKE256; needs no device).
+pub struct Transcript<F: FftField> {
+    field: core::ffi::c_int,
+    state: [u8; 32],
+    _f: core::marker::PhantomData<F>,
+}
+
+impl<F: FftField> Transcript<F> {
+    /// `Err(UnsupportedField)` when `F` is not one of the scalar fields the library serves
+    pub fn new(seed: [u8; 32]) -> Result<Self, DeviceError> {
+        let field = sys::fr_field_id::<F>().ok_or(DeviceError::UnsupportedField)?;
+        Ok(Self { field, state: seed, _f: core::marker::PhantomData })
+    }
+    pub fn state(&self) -> &[u8; 32] {
+        &self.state
+    }
+    pub fn challenge(&mut self, elements: &[F]) -> Result<F, DeviceError> {
+        let els: Vec<u64> = elements.iter().flat_map(|e| sys::limbs(e)).collect();
+        let mut out = [0u64; 4];
+        rc(unsafe {
+            sys::ark_hip_transcript_challenge(self.field, self.state.as_mut_ptr(), if els.is_empty() { core::ptr::null() } else { els.as_ptr() },
+                                              elements.len() as c_uint, out.as_mut_ptr())
+        })?;
+        Ok(sys::from_limbs::<F>(&out))
+    }
+}
+
 pub struct ListOfProducts<F: FftField> {
     num_vars: usize,
     tables: Vec<Rc<DenseMultilinearExtension<F>>>,
@@ -162,5 +190,47 @@ impl<F: FftField> ListOfProducts<F> {
             final_evaluations.push(sys::from_limbs::<F>(&out));
         }
         Ok(SumcheckProof { rounds, point, final_evaluations, final_value: evals[0] })
+    }
+
+    /// The whole proof in one wait: what [`ListOfProducts::prove`] returns when `challenge(i, evals)` is
+    /// `transcript.challenge(evals)`, with the challenges derived on the device (one call of `ark_hip_sumcheck_prove_device`).
+    /// Advances the transcript; allocates and frees its own work vector.  `tail_vars`: `-1` the library's default, `0` no
+    /// one-workgroup tail, else the variables it starts at.
+    pub fn prove_device(&mut self, transcript: &mut Transcript<F>, tail_vars: i32) -> Result<SumcheckProof<F>, DeviceError> {
+        if self.bound.is_some() || self.num_vars == 0 || self.products.is_empty() {
+            return Err(DeviceError::Mismatch);
+        }
+        for t in &self.tables {
+            t.evaluations().here()?;
+        }
+        let (mut work_elems, mut launches, mut tail_from) = (0usize, 0, 0);
+        rc(unsafe {
+            sys::ark_hip_sumcheck_prove_plan(self.num_vars as c_uint, self.tables.len() as c_uint, tail_vars, &mut work_elems, &mut launches,
+                                             &mut tail_from)
+        })?;
+        let mut work = DeviceVec::<F>::alloc(work_elems)?;
+        let field = self.tables[0].evaluations().field();
+        let tables: Vec<*const c_void> = self.tables.iter().map(|t| t.evaluations().as_device_ptr()).collect();
+        let lens: Vec<c_uint> = self.products.iter().map(|(_, ix)| ix.len() as c_uint).collect();
+        let flat: Vec<c_uint> = self.products.iter().flat_map(|(_, ix)| ix.iter().map(|&i| i as c_uint)).collect();
+        let coeffs: Vec<u64> = self.products.iter().flat_map(|(c, _)| sys::limbs(c)).collect();
+        let d1 = self.degree + 1;
+        let mut rounds = ark_std::vec![0u64; 4 * d1 * self.num_vars];
+        let mut point = ark_std::vec![0u64; 4 * self.num_vars];
+        let mut finals = ark_std::vec![0u64; 4 * self.tables.len()];
+        let mut value = [0u64; 4];
+        rc(unsafe {
+            sys::ark_hip_sumcheck_prove_device(field, tables.as_ptr(), tables.len() as c_uint, self.num_vars as c_uint, lens.as_ptr(),
+                                               flat.as_ptr(), coeffs.as_ptr(), lens.len() as c_uint, transcript.state.as_mut_ptr(), tail_vars,
+                                               work.as_device_mut_ptr(), rounds.as_mut_ptr(), point.as_mut_ptr(), finals.as_mut_ptr(),
+                                               value.as_mut_ptr())
+        })?;
+        let els = |v: &[u64]| -> Vec<F> { v.chunks(4).map(|c| sys::from_limbs::<F>(&[c[0], c[1], c[2], c[3]])).collect() };
+        Ok(SumcheckProof {
+            rounds: rounds.chunks(4 * d1).map(|g| els(g)).collect(),
+            point: els(&point),
+            final_evaluations: els(&finals),
+            final_value: sys::from_limbs::<F>(&value),
+        })
     }
 }
