@@ -18,6 +18,12 @@
 //
 // "Is this difference zero mod p" is asked of the SQUARE that follows it, as in ec28.cuh: PP = P^2 is a product's output,
 // |PP| < p and its digits are the unique balanced ones, so PP = 0 mod p exactly when every digit is zero.
+//
+// The FULL addition of the reduction, heavy-run and parts-sum kernels (xyzz_add_s, with its doubling xyzz_dbl_s; the formulas and
+// special cases of xyzz_add_lazy) lives on the same digits and the same invariant, so accumulators pass between the two additions
+// freely: 10 products + 2 squares + one two-product sum = 10 * 338 + 2 * 260 + 507 = 4407 multiply-adds (+ 48 for the three
+// differences folded into their products) instead of the 28-bit form's 5110.  Both of its operands are sums, so its bounds are its
+// own: stated at the routine, re-derived exactly by tests/lazy30_add_model.py.
 #pragma once
 #include "ec28.cuh"
 #include "fp30s.cuh"
@@ -136,6 +142,97 @@ ARK_HD bool xyzz_madd_s(XYZZS<P>& acc, const FpS<P>& x2, const FpS<P>& y2) {
   acc.zzz = F::mul(acc.zzz, ppp);                     // < 0.501 (n)
   acc.x = x3;
   return false;
+}
+
+// ---- full addition (the reduction, heavy-run and parts kernels; ARK_REDUCE_S30 in lazyk.cuh) ------------------------------------------
+// a stored point (canonical limbs) as the operand b of xyzz_add_s: values in [0, 64).  Every coordinate of b meets NORMALISED
+// operands only (x2 ZZ1, y2 ZZZ1, X1 zz2, Y1 zzz2, ZZ1 zz2, ZZZ1 zzz2, or the residue 1 when the accumulator is empty) and is
+// read by nothing but products: it stays unsigned, as a gathered base does (the exception at the top of fp30s.cuh).
+template <class P>
+ARK_HD XYZZS<P> s30_operands_of(const XYZZ<Fp<P>>& b) {
+  typedef FpS<P> F;
+  XYZZS<P> r;
+  r.inf = b.is_zero();
+#if ARK_S30_UNSIGNED_GATHER
+  r.x = F::from_canonical_u(b.x.l);
+  r.y = F::from_canonical_u(b.y.l);
+  r.zz = F::from_canonical_u(b.zz.l);
+  r.zzz = F::from_canonical_u(b.zzz.l);
+#else
+  r.x = F::from_canonical_shl(b.x.l);
+  r.y = F::from_canonical_shl(b.y.l);
+  r.zz = F::from_canonical_shl(b.zz.l);
+  r.zzz = F::from_canonical_shl(b.zzz.l);
+#endif
+  return r;
+}
+// acc = 2 acc for an accumulator that is not at infinity (dbl-2008-s-1, a = 0; bucket.rs:112-146), as xyzz_dbl_lazy does it on 28-bit
+// limbs: X3 and Y3 from (X1, Y1) alone, ZZ3 = V ZZ1, ZZZ3 = W ZZZ1.  Rare (equal sums meeting), expanded in place (ARK_COLD_HD), no call
+// frame.  On the digits themselves, NOT through the canonical form and the 28-bit doubling as xyzz_mdbl_s goes: that round trip, inlined
+// with the accumulator and the other operand alive, was the widest point of every kernel that adds (msm_reduce_level_kernel 256 VGPRs
+// instead of 213; msm_heavy_combine_kernel 256 + 2 AGPRs, one wave per SIMD instead of two).  Bounds from the invariant:
+//   U = 2 Y1 < 1.22 (n, swept),  V = U^2 < 0.5025,  W = U V < 0.5011,  S = X1 V < 0.5018,  XX = X1^2 < 0.5066,  M = 3 XX < 1.52 (n, swept)
+//   X3 = M^2 - 2 S < 1.508,  t = S - X3 < 2.01,  Y3 = M t - W Y1 < 0.5055,  ZZ3 = V ZZ1, ZZZ3 = W ZZZ1 < 0.501       (n)
+template <class P>
+ARK_COLD_HD void xyzz_dbl_s(XYZZS<P>& acc) {
+  typedef FpS<P> F;
+  const F u = F::add(acc.y, acc.y);
+  const F v = F::sqr(u);
+  const F w = F::mul(u, v);
+  const F s = F::mul(acc.x, v);
+  const F xx = F::sqr(acc.x);
+  const F m = F::add_2b(xx, xx);                      // digits before the sweep <= 3 2^29
+  const F x3 = F::sqr_sub2(m, F::zero(), s);          // M^2 - 2 S
+  const F t = F::sub(s, x3);
+  acc.y = F::sop2(m, t, F::neg(w), acc.y);            // M (S - X3) - W Y1
+  acc.zz = F::mul(v, acc.zz);
+  acc.zzz = F::mul(w, acc.zzz);
+  acc.x = x3;
+}
+// acc += b: the formulas and special cases of xyzz_add_lazy (ec28.cuh; add-2008-s, bucket.rs:256-337).  b is another accumulator
+// (inside the invariant) or a stored point from s30_operands_of (values in [0, 64), unsigned digits).  Bounds, |value| in units
+// of p, from the invariant |x| < 2.02, |y| < 0.61, |zz|, |zzz| < 1 with b at 64 (re-derived exactly by tests/lazy30_add_model.py):
+//   U1 = X1 ZZ2 < 2.02 * 64 / 629.9 + 0.5001 < 0.706,  S1 = Y1 ZZZ2 < 0.61 * 64 / 629.9 + 0.5001 < 0.563            (n)
+//   P = X2 ZZ1 - U1 < 0.602 + 0.706 < 1.308,  R = Y2 ZZZ1 - S1 < 0.602 + 0.563 < 1.165     (n: the high columns' own digits)
+//   PP < 1.308^2 / 629.9 + 0.5001 < 0.5029,  PPP < 0.5012,  Q = U1 PP < 0.5007,  R^2 / R' < 0.5023                      (n)
+//   X3 = R^2 - PPP - 2 Q < 2.006,  t = Q - X3 < 2.507,  Y3 = R t - S1 PPP < 0.5053                                     (n)
+//   ZZ1 ZZ2, ZZZ1 ZZZ2 < 0.602,  ZZ3, ZZZ3 < 0.5006                                                                  (n)
+// which is the invariant again; an empty accumulator takes b through one product by one per coordinate (< 0.602).  Equal points
+// (P = R = 0 mod p) double the accumulator in place (xyzz_dbl_s), opposite ones leave infinity.
+template <class P>
+ARK_HD void xyzz_add_s(XYZZS<P>& acc, const XYZZS<P>& b) {
+  typedef FpS<P> F;
+  if (b.inf) return;
+  if (acc.inf) {
+    const F one = F::one();
+    acc.x = F::mul(b.x, one);
+    acc.y = F::mul(b.y, one);
+    acc.zz = F::mul(b.zz, one);
+    acc.zzz = F::mul(b.zzz, one);
+    acc.inf = false;
+    return;
+  }
+  const F u1 = F::mul(acc.x, b.zz);
+  const F s1 = F::mul(acc.y, b.zzz);
+  const F pd = F::mul_sub(b.x, acc.zz, u1);           // P = U2 - U1: U2 has no other consumer
+  const F rd = F::mul_sub(b.y, acc.zzz, s1);          // R = S2 - S1
+  const F pp = F::sqr(pd);                            // |PP| < p: the zero test is exact
+  if (pp.is_zero_digits()) {                          // P = 0 mod p: the same x -- doubling or infinity (bucket.rs:279-290)
+    if (F::sqr(rd).is_zero_digits()) {
+      xyzz_dbl_s<P>(acc);
+    } else {
+      acc.inf = true;
+    }
+    return;
+  }
+  const F ppp = F::mul(pd, pp);
+  const F q = F::mul(u1, pp);
+  const F x3 = F::sqr_sub2(rd, ppp, q);               // R^2 - PPP - 2 Q
+  const F t = F::sub(q, x3);                          // Q - X3 (n, swept)
+  acc.y = F::sop2(rd, t, F::neg(s1), ppp);            // R (Q - X3) - S1 PPP: four normalised operands, top digits below 2^23
+  acc.zz = F::mul(F::mul(acc.zz, b.zz), pp);
+  acc.zzz = F::mul(F::mul(acc.zzz, b.zzz), ppp);
+  acc.x = x3;
 }
 
 }  // namespace arkhip

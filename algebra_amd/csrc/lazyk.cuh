@@ -13,6 +13,11 @@
 #ifndef ARK_LAZY_S30
 #define ARK_LAZY_S30 1
 #endif
+// 1 (default): the reduction, heavy-run and parts kernels of those curves sum on the signed 30-bit form as well (ec30s.cuh:
+// xyzz_add_s); 0: on the 28-bit form, as they did (A/B builds).  Everything stored is canonical and the same under both.
+#ifndef ARK_REDUCE_S30
+#define ARK_REDUCE_S30 1
+#endif
 
 namespace arkhip {
 
@@ -73,8 +78,9 @@ struct LazyK<C, 1> {
   }
 };
 
-// The same interface on 13 signed 30-bit digits (ec30s.cuh), for msm_accumulate_lazy_kernel alone: the reduction, heavy-run,
-// parts and prepared kernels keep LazyK.  Buckets enter and leave in the same canonical form, so the two forms mix freely.
+// The same interface on 13 signed 30-bit digits (ec30s.cuh): msm_accumulate_lazy_kernel (AccumK) and the reduction, heavy-run and
+// parts-sum kernels (ReduceK); the parts-accumulate and prepared kernels keep LazyK.  Buckets enter and leave in the same canonical
+// form, so the two forms mix freely.
 template <class C>
 struct LazySK {
   typedef typename C::F FM;
@@ -97,8 +103,12 @@ struct LazySK {
     return xyzz_madd_s<P>(acc, sx, sy);
   }
   ARK_HD static void mdbl(Acc& out, const char* src, bool neg) { xyzz_mdbl_s<P>(out, src, neg); }
-  // the accumulator as 4 x 13 digits + the infinity flag: the layout of the raw-digit test hook (s30test.cuh) -- the accumulate
-  // kernel parks nothing, so no product kernel calls these two
+  ARK_HD static void add(Acc& acc, const XYZZ<FM>& b) { xyzz_add_s<P>(acc, s30_operands_of<P>(b)); }
+  ARK_HD static void add_acc(Acc& acc, const Acc& b) { xyzz_add_s<P>(acc, b); }
+  // the accumulator as 4 x 13 digits + the infinity flag: the layout of the raw-digit test hook (s30test.cuh) and of a parked
+  // accumulator in LDS
+  ARK_HD static void park(const Acc& a, char* slot) { park(a, (i32*)slot); }
+  ARK_HD static Acc unpark(const char* slot) { return unpark((const i32*)slot); }
   ARK_HD static void park(const Acc& a, i32* w) {
 #pragma unroll
     for (int i = 0; i < FL::L; i++) {
@@ -131,6 +141,14 @@ struct AccumK { typedef LazyK<C> T; };
 #if ARK_LAZY_S30
 template <class C>
 struct AccumK<C, 1, std::enable_if_t<HasS30<typename C::F::P>::value>> { typedef LazySK<C> T; };
+#endif
+
+// what the reduction, heavy-run and parts-sum kernels sum on (msm.cuh: AccOps, msm_sum_parts_kernel)
+template <class C, int LANES_ = C::FA::LANES, class = void>
+struct ReduceK { typedef LazyK<C> T; };
+#if ARK_REDUCE_S30
+template <class C>
+struct ReduceK<C, 1, std::enable_if_t<HasS30<typename C::F::P>::value>> { typedef LazySK<C> T; };
 #endif
 
 // G2: a lane pair owns the bucket; every lane holds ONE component of each coordinate

@@ -655,7 +655,7 @@ __global__ void __launch_bounds__(256) msm_sum_parts_kernel(const u32* __restric
                                                             const u32* __restrict__ d_thresh, int HB, int LB, u32 nparts,
                                                             const char* __restrict__ parts, int accum,
                                                             char* __restrict__ buckets) {
-  typedef LazyK<C> K;
+  typedef typename ReduceK<C>::T K;
   typedef typename K::FM F;
   const u32 g = (blockIdx.x * blockDim.x + threadIdx.x) / K::LANES;
   if (g >= nbuckets) return;
@@ -916,12 +916,12 @@ static __global__ void __launch_bounds__(256) msm_find_heavy_kernel(const u32* _
 template <class C>
 struct AccOps {
   static_assert(C::LAZY_A, "the reduction and heavy-run kernels sum on the curve's carry-free form");
-  typedef LazyK<C> K;            // carry-free limbs: ec28.cuh (one lane per point) or ec28x2.cuh (G2: one lane pair)
+  typedef typename ReduceK<C>::T K;   // carry-free limbs: ec28.cuh (one lane per point), ec30s.cuh (BLS12-381 G1) or ec28x2.cuh (G2: one lane pair)
   typedef typename K::FM F;
   typedef XYZZ<F> Pt;
   typedef typename K::Acc Acc;
   static constexpr u32 LANES = K::LANES;
-  static constexpr size_t ACC_BYTES = ((size_t)K::WORDS * 4 + 15) / 16 * 16;   // G1: 4 x 14 limbs + flag = 240 B; G2: 464 B per pair
+  static constexpr size_t ACC_BYTES = ((size_t)K::WORDS * 4 + 15) / 16 * 16;   // G1: 4 x 14 limbs + flag = 240 B (13 digits: 224 B); G2: 464 B per pair
   ARK_DEV static Acc zero() { return K::inf(); }
   ARK_DEV static Acc from_pt(const Pt& p) { return K::from_bucket(p); }
   // acc += (+-) the non-identity base p gathered from `src`; the doubling of equal points RE-READS the base, as the accumulate

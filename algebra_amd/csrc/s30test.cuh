@@ -66,6 +66,35 @@ ARK_HD void s30_raw_apply(int op, const i32* in, i32* out) {
       out[4 * SLOT + 1] = eq ? 1 : 0;
       return;
     }
+    case ADD_FULL:
+    case ADD_FULL_ACC: {
+      auto pt = [&](int j) {
+        XYZZ<FM> b;
+        b.x = canon(j * SLOT);
+        b.y = canon((j + 1) * SLOT);
+        b.zz = canon((j + 2) * SLOT);
+        b.zzz = canon((j + 3) * SLOT);
+        return b;
+      };
+      typename K::Acc acc = K::inf();
+      K::add(acc, pt(0));
+      if (op == ADD_FULL) {
+        K::add(acc, pt(4));
+      } else {
+        typename K::Acc other = K::inf();
+        K::add(other, pt(4));
+        K::add_acc(acc, other);
+      }
+      const XYZZ<FM> o = K::to_bucket(acc);
+#pragma unroll
+      for (int i = 0; i < SLOT; i++) {
+        out[i] = i < FM::N ? (i32)o.x.l[i] : 0;
+        out[SLOT + i] = i < FM::N ? (i32)o.y.l[i] : 0;
+        out[2 * SLOT + i] = i < FM::N ? (i32)o.zz.l[i] : 0;
+        out[3 * SLOT + i] = i < FM::N ? (i32)o.zzz.l[i] : 0;
+      }
+      return;
+    }
     case MUL_SUB: r = F::mul_sub(ld(0), ld(1), ld(2)); break;
     case SQR_SUB2: r = F::sqr_sub2(ld(0), ld(1), ld(2)); break;
     default: break;

@@ -22,15 +22,21 @@ enum Op : int {
                      // accumulate kernel's own entry (LazySK::madd)
   MUL_SUB = 10,   // 3 -> 1: a b - s inside the product's high columns
   SQR_SUB2 = 11,  // 3 -> 1: a^2 - s - 2 d
-  OPS = 12
+  ADD_FULL = 12,      // two stored points A | B (x, y, zz, zzz: 12 canonical words of a slot each) -> A + B as a stored point (4 slots):
+                      // the reduction kernels' full addition (xyzz_add_s), A taken up by an empty accumulator, B from memory
+  ADD_FULL_ACC = 13,  // the same with B taken up by an accumulator of its own first: accumulator + accumulator
+  OPS = 14
 };
 constexpr int SLOT = 13;
 constexpr int in_words(int op) {
   return op == MADD       ? 4 * SLOT + 1 + 2 * SLOT
        : op == MADD_ENTRY ? 4 * SLOT + 1 + 2 * SLOT + 1
+       : op == ADD_FULL || op == ADD_FULL_ACC ? 8 * SLOT
                           : SLOT * (op == MUL || op == SUB || op == ADD_2B ? 2 : op == SOP2 ? 4 : op == MUL_SUB || op == SQR_SUB2 ? 3 : 1);
 }
-constexpr int out_words(int op) { return op == MADD || op == MADD_ENTRY ? 4 * SLOT + 2 : SLOT; }
+constexpr int out_words(int op) {
+  return op == MADD || op == MADD_ENTRY ? 4 * SLOT + 2 : op == ADD_FULL || op == ADD_FULL_ACC ? 4 * SLOT : SLOT;
+}
 
 }  // namespace s30test
 }  // namespace arkhip
