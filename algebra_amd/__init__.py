@@ -20,6 +20,7 @@ from .msm import (BatchMulPreprocessing, batch_mul, ChunkedPippenger, HashMapPip
                   BaseCheck, check_bases, BaseDecode, compressed_size, decompress_bases, compress_bases)
 from .domain import Radix2EvaluationDomain  # noqa: F401
 from .poly import DeviceVec, poly_mul, poly_mul_host, prefix_scan_plan  # noqa: F401
+from .sparse import CsrMatrix, csr_plan  # noqa: F401
 from .points import DevicePoints  # noqa: F401
 from .mle import (DenseMultilinearExtension, DeviceSegment, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_fraction_tree_launches,  # noqa: F401
                   mle_fraction_tree_plan, mle_product_tree_launches, mle_product_tree_plan, mle_quotients_plan)

@@ -6,6 +6,7 @@
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "capi_cache.hpp"
+#include "capi_csr.hpp"
 #include "msm_piece_dump.cuh"
 #include "pointcheck.cuh"
 #include "pointcodec.cuh"
@@ -741,5 +742,26 @@ int ark_hip_test_scratch_selfcheck(void) {
     }
   }
   return hits == 1 ? 0 : 6;
+}
+// One side of a CSR handle read back array by array: what the host-side stable transposition left on the device.  Waits.
+int ark_hip_test_csr_dump(const ark_hip_fr_csr* m, int transpose, size_t* dims, uint32_t* row_ptr, size_t row_ptr_cap, uint32_t* col_idx,
+                          uint64_t* vals, size_t nnz_cap) {
+  const CsrHandle* h = (const CsrHandle*)m;
+  if (!h || !dims || (transpose != 0 && transpose != 1) || (transpose && !h->has_t)) return ARK_HIP_ERR_ARG;
+  const CsrSide& s = h->side[transpose];
+  dims[0] = s.rows;
+  dims[1] = s.cols;
+  dims[2] = s.nnz;
+  if (!row_ptr && !col_idx && !vals) return 0;   // the sizes only
+  if (!row_ptr || row_ptr_cap < s.rows + 1 || nnz_cap < s.nnz || (s.nnz && (!col_idx || !vals))) return ARK_HIP_ERR_SIZE;
+  Scope sc;
+  if (int rc = sc.enter(h->logical)) return rc;
+  if (int rc = sync_compute(sc.c)) return rc;
+  ARK_HIP_TRY(hipMemcpy(row_ptr, s.csr_ptr.p, (s.rows + 1) * 4, hipMemcpyDeviceToHost));
+  if (s.nnz) {
+    ARK_HIP_TRY(hipMemcpy(col_idx, s.csr_idx.p, s.nnz * 4, hipMemcpyDeviceToHost));
+    ARK_HIP_TRY(hipMemcpy(vals, s.csr_val.p, s.nnz * 32, hipMemcpyDeviceToHost));
+  }
+  return 0;
 }
 }  // extern "C"

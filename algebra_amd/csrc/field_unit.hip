@@ -5,6 +5,7 @@
 #include "devops.cuh"
 #include "polyops.cuh"
 #include "prefixscan.cuh"
+#include "spmv.cuh"
 #include "mle.cuh"
 #include "mle_open.cuh"
 #include "grand_product.cuh"
@@ -96,6 +97,10 @@ struct FieldOpsOf final : FieldOps {
   int ratio_tile(const void* num, const void* den, size_t n, const void* cn, const void* cdi, const void* icd, void* out, void* last,
                  hipStream_t s) const override {
     return ratio_tile_launch<Fp<F>>(num, den, n, cn, cdi, icd, out, last, s);
+  }
+  int csr_stream(const CsrView& m, const void* x, void* y, hipStream_t s) const override { return csr_stream_launch<Fp<F>>(m, x, y, s); }
+  int csr_long(const CsrView& m, const void* x, void* partials, void* y, hipStream_t s) const override {
+    return csr_long_launch<Fp<F>>(m, x, partials, y, s);
   }
   int fft_axis(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4,
                hipStream_t s) const override {

@@ -16,6 +16,7 @@
 //   cache: FftWorkspace::axis_pw  the G-point cross transform's root powers, keyed by FftWorkspace::axis_root (and G)
 //   cache: BaseCacheEntry::dev  per (curve, host address, length), validated by a hash of the slice's full content on every call
 //   cache: PreparedBases::table  a handle the caller owns (ark_hip_msm_bases_prepare .. _free): per-window multiples of its bases
+//   cache: CsrSide::csr_ptr, CsrSide::csr_idx, CsrSide::csr_val, CsrSide::csr_work  a handle the caller owns (ark_hip_fr_csr_create .. _free): row_ptr, col_idx, vals and the row plan of M and, when asked for, of M^T
 //   cache: BatchMulTable::table  a handle the caller owns (ark_hip_batch_mul_table_new .. _free): multiples of its one base
 // Locals that live inside one call and are released, or moved into a cache, before it returns (or that only name a buffer
 // listed elsewhere):

@@ -632,6 +632,46 @@ int ark_hip_mle_fraction_tree_plan(unsigned num_vars, int has_num, int* passes, 
  * table_len > 2^58, or d_out overlapping the indices.  Asynchronous. */
 int ark_hip_fr_count_indices_device(int field, const uint32_t* d_indices, size_t n, void* d_out, size_t table_len);
 
+/* ---- sparse constraint matrices on the device ---------------------------------------------------
+ * The matrices of an R1CS / CCS instance in CSR form, resident on the device, and their products with device vectors:
+ * A z, B z, C z in front of a quotient or a sumcheck, M^T eq(rx) for the second sumcheck of a Spartan-style prover, and with
+ * an inner product the value of the sparse multilinear extension, eq(rx)^T M eq(ry).  Elements follow the conventions of the
+ * ark_hip_fr_*_device block: 4 x u64 canonical Montgomery residues, not checked; ARK_HIP_ERR_ARG comes before any device is
+ * looked for; work runs on the context stream.
+ *
+ * ark_hip_fr_csr_create takes HOST arrays (a circuit's matrices come from a host compiler once per circuit): row_ptr
+ * (rows + 1 entries), col_idx (nnz), vals (nnz elements).  Everything a kernel will index with is validated here, on the host:
+ * row_ptr[0] = 0, row_ptr non-decreasing, row_ptr[rows] = nnz, every col_idx < cols, rows, cols and nnz < 2^32, non-null
+ * pointers wherever a count is non-zero (row_ptr may be NULL only when rows = 0 and nnz = 0), a scalar field this build
+ * serves, no flag bit other than ARK_HIP_CSR_WITH_TRANSPOSE, a non-null out.  Any violation is ARK_HIP_ERR_ARG with nothing
+ * allocated and *out untouched.  Duplicate column indices inside a row are legal and add; rows = 0, cols = 0 and nnz = 0 are
+ * legal; zero values are values.  With ARK_HIP_CSR_WITH_TRANSPOSE the handle also holds M^T in the same form, built on the host
+ * by a STABLE counting sort over the columns: inside a row of M^T the entries keep ascending original row order.  The call
+ * returns when the handle is complete; the host arrays are not referenced afterwards.  The handle belongs to the caller,
+ * like a prepared base set, and to the device that was current when it was created.
+ *
+ * ark_hip_fr_csr_free waits for work that may still read the handle; NULL is fine.
+ *
+ * ark_hip_fr_csr_mul_device: transpose = 0 computes y = M x with x_len = cols, y_len = rows; transpose = 1 computes
+ * y = M^T x with x_len = rows, y_len = cols and needs a handle created with ARK_HIP_CSR_WITH_TRANSPOSE.  Exactly y_len
+ * elements are written; empty rows give zero.  ARK_HIP_ERR_ARG: a null handle, transpose not 0 or 1 or 1 without the flag, a
+ * wrong length, a null vector with a non-zero length, any overlap of d_x and d_y.  Asynchronous.  No atomics on field elements:
+ * the result is canonical and bit-exact.  Scratch: one partial per chunk of a long row, all written by the same call.
+ *
+ * ark_hip_csr_plan is host only and needs no device: how create cuts `rows` rows with these row_ptr (the same validation:
+ * row_ptr[0] = 0, non-decreasing, else ARK_HIP_ERR_ARG; NULL only with rows = 0) into work.  *tile (at most 2^16): nonzeros per
+ * workgroup; *max_rows: rows per stream block; *blocks: stream blocks -- runs of consecutive rows with at most `tile`
+ * nonzeros and `max_rows` rows, empty rows counting; *long_rows: rows with more than `tile` nonzeros, each alone;
+ * *long_chunks: the sum of ceil(nnz / tile) over the long rows.  Every output pointer may be NULL. */
+typedef struct ark_hip_fr_csr ark_hip_fr_csr;
+#define ARK_HIP_CSR_WITH_TRANSPOSE 1u
+int ark_hip_fr_csr_create(int field, size_t rows, size_t cols, const uint32_t* row_ptr, const uint32_t* col_idx,
+                          const uint64_t* vals, size_t nnz, unsigned flags, ark_hip_fr_csr** out);
+int ark_hip_fr_csr_free(ark_hip_fr_csr* m);
+int ark_hip_fr_csr_mul_device(const ark_hip_fr_csr* m, int transpose, const void* d_x, size_t x_len, void* d_y, size_t y_len);
+int ark_hip_csr_plan(size_t rows, const uint32_t* row_ptr, int* tile, int* max_rows, size_t* blocks, size_t* long_rows,
+                     size_t* long_chunks);
+
 /* ---- the sumcheck prover's round on device tables --------------------------------------------
  * The sum is a list of products of multilinear tables, each with a coefficient (ListOfProductsOfPolynomials of
  * ark-linear-sumcheck): sum_j c_j prod_{k in term j} f_k.  Tables follow the conventions above: 2^num_vars Montgomery
@@ -883,6 +923,12 @@ int ark_hip_test_scratch_selfcheck(void);
  * ark_hip_transcript_challenge. */
 int ark_hip_test_transcript_reduce(int field, const uint8_t* bytes64, int on_device, uint64_t* out);
 int ark_hip_test_transcript_challenge_device(int field, uint8_t* state, const uint64_t* elements, unsigned count, uint64_t* out);
+/* One side of a CSR handle read back array by array (transpose = 1: the M^T that ark_hip_fr_csr_create built, ARK_HIP_ERR_ARG
+ * without the flag): dims = {rows, cols, nnz} of that side, always written; row_ptr (rows + 1), col_idx (nnz) and vals (nnz
+ * elements) into HOST arrays of the given capacities, ARK_HIP_ERR_SIZE when one is too small; all three NULL: the sizes only.
+ * Waits for the device. */
+int ark_hip_test_csr_dump(const ark_hip_fr_csr* m, int transpose, size_t* dims, uint32_t* row_ptr, size_t row_ptr_cap,
+                          uint32_t* col_idx, uint64_t* vals, size_t nnz_cap);
 
 #endif /* ARK_HIP_TEST_HOOKS */
 

@@ -772,6 +772,69 @@ DeviceEvaluations<FIELD_ID> evaluate_over_domain(DeviceVec<FIELD_ID>&& coeffs, c
   return DeviceEvaluations<FIELD_ID>{std::move(coeffs), domain};
 }
 
+// A rows x cols matrix over Fr in CSR form, resident on the device: the constraint matrices of an R1CS /
+// CCS instance.  Built once per circuit from host arrays, which are validated there and copied; with_transpose also keeps
+// M^T (stable order), which mul_t needs.  Products are asynchronous on the library's stream; bilinear waits.
+struct CsrPlan { int tile, max_rows; size_t blocks, long_rows, long_chunks; };
+// how a handle with these row_ptr (rows + 1 entries) is cut into work; host only
+inline CsrPlan csr_plan(size_t rows, const uint32_t* row_ptr) {
+  CsrPlan p{};
+  check(ark_hip_csr_plan(rows, row_ptr, &p.tile, &p.max_rows, &p.blocks, &p.long_rows, &p.long_chunks), "ark_hip_csr_plan");
+  return p;
+}
+template <int FIELD_ID>
+class CsrMatrix {
+ public:
+  CsrMatrix(size_t rows, size_t cols, const uint32_t* row_ptr, const uint32_t* col_idx, const Fr* vals, size_t nnz,
+            bool with_transpose = false)
+      : rows_(rows), cols_(cols), nnz_(nnz), has_t_(with_transpose) {
+    check(ark_hip_fr_csr_create(FIELD_ID, rows, cols, row_ptr, col_idx, nnz ? vals->limbs.data() : nullptr, nnz,
+                                with_transpose ? ARK_HIP_CSR_WITH_TRANSPOSE : 0u, &h_), "ark_hip_fr_csr_create");
+  }
+  CsrMatrix(size_t rows, size_t cols, const std::vector<uint32_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+            const std::vector<Fr>& vals, bool with_transpose = false)
+      : CsrMatrix(rows, cols, row_ptr.data(), col_idx.data(), vals.data(), vals.size(), with_transpose) {
+    if (row_ptr.size() != rows + 1 || col_idx.size() != vals.size()) { free(); throw Error(ARK_HIP_ERR_ARG, "row_ptr: rows + 1 entries; one value per column index"); }
+  }
+  CsrMatrix(CsrMatrix&& o) noexcept : h_(o.h_), rows_(o.rows_), cols_(o.cols_), nnz_(o.nnz_), has_t_(o.has_t_) { o.h_ = nullptr; }
+  CsrMatrix(const CsrMatrix&) = delete;
+  CsrMatrix& operator=(const CsrMatrix&) = delete;
+  ~CsrMatrix() { free(); }
+  void free() {
+    if (h_) (void)ark_hip_fr_csr_free(h_);
+    h_ = nullptr;
+  }
+  size_t rows() const { return rows_; }
+  size_t cols() const { return cols_; }
+  size_t nnz() const { return nnz_; }
+  bool has_transpose() const { return has_t_; }
+  // y = M x: x has cols elements, y rows
+  DeviceVec<FIELD_ID> mul(const DeviceVec<FIELD_ID>& x) const {
+    DeviceVec<FIELD_ID> y = DeviceVec<FIELD_ID>::uninit(rows_);
+    mul(x, y);
+    return y;
+  }
+  void mul(const DeviceVec<FIELD_ID>& x, DeviceVec<FIELD_ID>& out) const {
+    check(ark_hip_fr_csr_mul_device(h_, 0, x.device_ptr(), x.len(), out.device_ptr(), out.len()), "ark_hip_fr_csr_mul_device");
+  }
+  // y = M^T x: x has rows elements, y cols; needs with_transpose
+  DeviceVec<FIELD_ID> mul_t(const DeviceVec<FIELD_ID>& x) const {
+    DeviceVec<FIELD_ID> y = DeviceVec<FIELD_ID>::uninit(cols_);
+    mul_t(x, y);
+    return y;
+  }
+  void mul_t(const DeviceVec<FIELD_ID>& x, DeviceVec<FIELD_ID>& out) const {
+    check(ark_hip_fr_csr_mul_device(h_, 1, x.device_ptr(), x.len(), out.device_ptr(), out.len()), "ark_hip_fr_csr_mul_device");
+  }
+  // u^T M v; with u = eq(rx, .), v = eq(ry, .) the value of the matrix's sparse multilinear extension at (rx, ry); waits for it
+  Fr bilinear(const DeviceVec<FIELD_ID>& u, const DeviceVec<FIELD_ID>& v) const { return u.inner_product(mul(v)); }
+
+ private:
+  ark_hip_fr_csr* h_ = nullptr;
+  size_t rows_ = 0, cols_ = 0, nnz_ = 0;
+  bool has_t_ = false;
+};
+
 // DenseMultilinearExtension<F> resident on the device (poly/src/evaluations/multivariate/multilinear/dense.rs): 2^num_vars
 // evaluations over the boolean hypercube, index bit 0 being the first variable.  Committing to it is an MSM with Montgomery
 // scalars on evaluations().device_ptr(); fix_variables and evaluate bind its variables where the table lies.

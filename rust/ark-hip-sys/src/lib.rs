@@ -51,6 +51,12 @@ pub struct ark_hip_msm_job {
 pub struct ark_hip_batch_mul_table {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct ark_hip_fr_csr {
+    _private: [u8; 0],
+}
+/// `ark_hip_fr_csr_create`: also keep `M^T`.
+pub const ARK_HIP_CSR_WITH_TRANSPOSE: c_uint = 1;
 
 extern "C" {
     pub fn ark_hip_device_count() -> c_int;
@@ -253,6 +259,18 @@ extern "C" {
     /// `d_out[j] = #{i < n : d_indices[i] = j}` for `j < table_len` as Montgomery elements; an index `>= table_len` is
     /// skipped and not reported, so the counts sum to `n` exactly when none was skipped.  Asynchronous.
     pub fn ark_hip_fr_count_indices_device(field: c_int, d_indices: *const u32, n: usize, d_out: *mut c_void, table_len: usize) -> c_int;
+    /// A CSR matrix onto the device from HOST arrays (`row_ptr`: `rows + 1`, `col_idx` / `vals`: `nnz`), every index validated on
+    /// the host first; `flags`: `ARK_HIP_CSR_WITH_TRANSPOSE` also keeps `M^T` (stable order).
+    pub fn ark_hip_fr_csr_create(field: c_int, rows: usize, cols: usize, row_ptr: *const u32, col_idx: *const u32, vals: *const u64,
+                                 nnz: usize, flags: c_uint, out: *mut *mut ark_hip_fr_csr) -> c_int;
+    /// Waits for work that may still read the handle; null is fine.
+    pub fn ark_hip_fr_csr_free(m: *mut ark_hip_fr_csr) -> c_int;
+    /// `y = M x` (`transpose = 0`: `x_len = cols`, `y_len = rows`) or `y = M^T x` (`transpose = 1`, lengths swapped).  Asynchronous.
+    pub fn ark_hip_fr_csr_mul_device(m: *const ark_hip_fr_csr, transpose: c_int, d_x: *const c_void, x_len: usize, d_y: *mut c_void,
+                                     y_len: usize) -> c_int;
+    /// Host only: tile, rows per stream block, stream blocks, long rows and their chunks for these `row_ptr`.
+    pub fn ark_hip_csr_plan(rows: usize, row_ptr: *const u32, tile: *mut c_int, max_rows: *mut c_int, blocks: *mut usize,
+                            long_rows: *mut usize, long_chunks: *mut usize) -> c_int;
     /// One sumcheck round over `ntables` device tables of `2^num_vars` elements: `out_evals[t]`, `t = 0 ..= D`, of
     /// `sum_b sum_j c_j prod_k (T_k[2b] + t (T_k[2b+1] - T_k[2b]))`; with `r_prev` (host element) the first variable is bound
     /// to it first, into `d_out_tables`, in the same launch.  `term_tables`: the factors' table indices, term after term.

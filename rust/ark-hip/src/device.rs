@@ -305,6 +305,76 @@ fn raw_domain<F: FftField>(d: &Radix2EvaluationDomain<F>) -> sys::ark_hip_radix2
     }
 }
 
+/// A `rows x cols` matrix over `F` in CSR form, resident on the device: a constraint matrix of an
+/// R1CS / CCS instance.  Built once per circuit from host slices, which the library validates and copies; `with_transpose`
+/// also keeps `M^T` (stable order), which [`CsrMatrix::mul_t`] needs.
+pub struct CsrMatrix<F: FftField> {
+    handle: *mut sys::ark_hip_fr_csr,
+    rows: usize,
+    cols: usize,
+    _f: PhantomData<F>,
+}
+unsafe impl<F: FftField> Send for CsrMatrix<F> {}
+/// `ark_hip_csr_plan`: how a handle with this `row_ptr` is cut into work (host only).
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct CsrPlan {
+    pub tile: c_int,
+    pub max_rows: c_int,
+    pub blocks: usize,
+    pub long_rows: usize,
+    pub long_chunks: usize,
+}
+pub fn csr_plan(row_ptr: &[u32]) -> Result<CsrPlan, DeviceError> {
+    if row_ptr.is_empty() {
+        return Err(DeviceError::Mismatch);
+    }
+    let mut p = CsrPlan { tile: 0, max_rows: 0, blocks: 0, long_rows: 0, long_chunks: 0 };
+    rc(unsafe { sys::ark_hip_csr_plan(row_ptr.len() - 1, row_ptr.as_ptr(), &mut p.tile, &mut p.max_rows, &mut p.blocks, &mut p.long_rows, &mut p.long_chunks) })?;
+    Ok(p)
+}
+impl<F: FftField> CsrMatrix<F> {
+    /// `row_ptr`: `rows + 1` entries; `col_idx` and `vals`: one per nonzero.  Every index is checked by the library on the host.
+    pub fn new(rows: usize, cols: usize, row_ptr: &[u32], col_idx: &[u32], vals: &[F], with_transpose: bool) -> Result<Self, DeviceError> {
+        let field = DeviceVec::<F>::field_id()?;
+        if row_ptr.len() != rows + 1 || col_idx.len() != vals.len() {
+            return Err(DeviceError::Mismatch);
+        }
+        let mut handle: *mut sys::ark_hip_fr_csr = core::ptr::null_mut();
+        let flags = if with_transpose { sys::ARK_HIP_CSR_WITH_TRANSPOSE } else { 0 };
+        rc(unsafe { sys::ark_hip_fr_csr_create(field, rows, cols, row_ptr.as_ptr(), col_idx.as_ptr(), vals.as_ptr() as *const u64, vals.len(), flags, &mut handle) })?;
+        Ok(Self { handle, rows, cols, _f: PhantomData })
+    }
+    pub fn rows(&self) -> usize {
+        self.rows
+    }
+    pub fn cols(&self) -> usize {
+        self.cols
+    }
+    fn product(&self, transpose: c_int, x: &DeviceVec<F>, n_out: usize) -> Result<DeviceVec<F>, DeviceError> {
+        x.here()?;
+        let out = DeviceVec::<F>::alloc(n_out)?;
+        rc(unsafe { sys::ark_hip_fr_csr_mul_device(self.handle, transpose, x.ptr, x.len, out.ptr, out.len) })?;
+        Ok(out)
+    }
+    /// `y = M x` (`x`: `cols` elements, `y`: `rows`); asynchronous.
+    pub fn mul(&self, x: &DeviceVec<F>) -> Result<DeviceVec<F>, DeviceError> {
+        self.product(0, x, self.rows)
+    }
+    /// `y = M^T x` (`x`: `rows` elements, `y`: `cols`); needs `with_transpose`.
+    pub fn mul_t(&self, x: &DeviceVec<F>) -> Result<DeviceVec<F>, DeviceError> {
+        self.product(1, x, self.cols)
+    }
+    /// `u^T M v`; with `u = eq(rx, .)`, `v = eq(ry, .)` the value of the matrix's sparse multilinear extension at `(rx, ry)`.
+    pub fn bilinear(&self, u: &DeviceVec<F>, v: &DeviceVec<F>) -> Result<F, DeviceError> {
+        u.inner_product(&self.mul(v)?)
+    }
+}
+impl<F: FftField> Drop for CsrMatrix<F> {
+    fn drop(&mut self) {
+        unsafe { sys::ark_hip_fr_csr_free(self.handle) };
+    }
+}
+
 /// `Evaluations<F, Radix2EvaluationDomain<F>>` resident on the device (evaluations/univariate/mod.rs:18-29).
 pub struct DeviceEvaluations<F: FftField> {
     pub evals: DeviceVec<F>,
