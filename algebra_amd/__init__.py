@@ -25,6 +25,7 @@ from .points import DevicePoints  # noqa: F401
 from .mle import (DenseMultilinearExtension, DeviceSegment, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_fraction_tree_launches,  # noqa: F401
                   mle_fraction_tree_plan, mle_product_tree_launches, mle_product_tree_plan, mle_quotients_plan)
 from .sumcheck import ListOfProducts, SumcheckProof, sumcheck_plan, sumcheck_prove_plan  # noqa: F401
+from .gates import SumOfProducts, sum_of_products_plan  # noqa: F401
 from .transcript import Transcript  # noqa: F401
 from .grand_product import GrandProduct, GrandProductProof  # noqa: F401
 from .fraction_sum import FractionalSum, FractionalSumProof  # noqa: F401

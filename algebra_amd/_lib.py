@@ -151,6 +151,10 @@ SYMBOLS = {
     "ark_hip_fr_prefix_sum_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "ark_hip_fr_prefix_ratio_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "ark_hip_prefix_scan_plan": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ark_hip_fr_sum_of_products_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_uint, C.c_size_t, C.POINTER(C.c_uint),
+                                                    C.POINTER(C.c_uint), C.POINTER(C.c_int64), C.c_void_p, C.c_uint, C.c_void_p,
+                                                    C.c_void_p]),
+    "ark_hip_fr_sum_of_products_plan": (C.c_int, [C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ark_hip_mle_fix_variables_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p]),
     "ark_hip_mle_evaluate_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]),
     "ark_hip_mle_relabel_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]),

@@ -3,8 +3,9 @@
 // prefix sums and ratio accumulators (prefixscan.cuh) -- and dense
 // multilinear extensions: fix_variables, evaluate, relabel, a + k x, the eq table and an opening's quotients -- and the
 // sumcheck prover's round over such tables, the product tree of a grand product and its fingerprints, the fraction tree and the
-// multiplicities of a lookup, the Fiat-Shamir transcript and the whole sumcheck proof in one wait (see include/ark_hip.h;
-// kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh, transcript.cuh, grand_product.cuh, fraction_sum.cuh).
+// multiplicities of a lookup, the Fiat-Shamir transcript and the whole sumcheck proof in one wait, and the gate expression of a
+// univariate prover: sums of products of columns read at rotations (see include/ark_hip.h;
+// kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh, transcript.cuh, grand_product.cuh, fraction_sum.cuh, gateexpr.cuh).
 #include "capi_core.hpp"
 #include "capi_hostmath.hpp"
 #include "polyops.cuh"
@@ -14,6 +15,7 @@
 #include "grand_product.cuh"
 #include "fraction_sum.cuh"
 #include "sumcheck.cuh"
+#include "gateexpr.cuh"
 using namespace arkhip;
 using namespace arkhip::capi;
 
@@ -808,6 +810,61 @@ int ark_hip_sumcheck_prove_device(int field, const void* const* d_tables, unsign
   ARK_HIP_TRY(hipMemcpyAsync(state, pv.state, 32, hipMemcpyDeviceToHost, c->stream));
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+// ---- gate expressions: sums of products of columns read at rotations ----
+int ark_hip_fr_sum_of_products_plan(size_t n, int* blocks, int* rows_per_lane) {
+  if (!blocks || !rows_per_lane) return ARK_HIP_ERR_ARG;
+  unsigned b;
+  size_t rpl;
+  gate_geometry(n, &b, &rpl);
+  *blocks = (int)b;
+  *rows_per_lane = rpl > 0x7fffffffu ? 0x7fffffff : (int)rpl;
+  return 0;
+}
+
+int ark_hip_fr_sum_of_products_device(int field, const void* const* d_columns, unsigned ncolumns, size_t n, const unsigned* term_len,
+                                      const unsigned* term_columns, const int64_t* term_rotations, const uint64_t* coeffs,
+                                      unsigned nterms, const uint64_t* c0, void* d_out) {
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_columns || !term_len || !term_columns || !coeffs || !d_out) return ARK_HIP_ERR_ARG;
+  if (ncolumns == 0 || ncolumns > (unsigned)GATE_MAX_COLUMNS || nterms == 0 || nterms > (unsigned)GATE_MAX_TERMS) return ARK_HIP_ERR_ARG;
+  if (n > ((size_t)1 << 58)) return ARK_HIP_ERR_ARG;   // a column's bytes must fit a size_t, and i + rot a u64
+  GateTerms tm = {};
+  tm.nterms = nterms;
+  tm.has_c0 = c0 ? 1 : 0;
+  bool rotated[GATE_MAX_COLUMNS] = {};   // some factor reads the column at a rotation that is not 0 mod n
+  for (unsigned j = 0, at = 0; j < nterms; j++) {
+    const unsigned len = term_len[j];
+    if (len == 0 || len > (unsigned)GATE_MAX_DEGREE) return ARK_HIP_ERR_ARG;
+    tm.len[j] = len;
+    for (unsigned q = 0; q < len; q++, at++) {
+      const unsigned k = term_columns[at];
+      if (k >= ncolumns) return ARK_HIP_ERR_ARG;
+      tm.tab[j] |= k << (4 * q);
+      if (n && term_rotations) {   // the mathematical mod: INT64_MIN % n is representable, n <= 2^58
+        int64_t r = term_rotations[at] % (int64_t)n;
+        if (r < 0) r += (int64_t)n;
+        tm.rot[j][q] = (unsigned long long)r;
+        if (r) rotated[k] = true;
+      }
+    }
+    for (int q = 0; q < 4; q++) { tm.coeff[j].l[2 * q] = (u32)coeffs[4 * j + q]; tm.coeff[j].l[2 * q + 1] = (u32)(coeffs[4 * j + q] >> 32); }
+    if (field_is_one(field, coeffs + 4 * j)) tm.unit |= 1u << j;
+  }
+  if (c0)
+    for (int q = 0; q < 4; q++) { tm.c0.l[2 * q] = (u32)c0[q]; tm.c0.l[2 * q + 1] = (u32)(c0[q] >> 32); }
+  for (unsigned k = 0; n && k < ncolumns; k++) {
+    if (!d_columns[k]) return ARK_HIP_ERR_ARG;
+    // in place only where a lane reads the row it writes: with a rotation one workgroup would write what another still reads
+    if (d_columns[k] == d_out ? rotated[k] : ranges_overlap(d_columns[k], n * 32, d_out, n * 32)) return ARK_HIP_ERR_ARG;
+    tm.col[k] = (const char*)d_columns[k];
+  }
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  if (n == 0) return 0;
+  if (int rc = ops->gate_sum_of_products(tm, d_out, n, c->stream)) return rc;
+  return mark_producer(c);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Instantiation of the radix-2 FFT, the pointwise field kernels and the polynomial, multilinear and sumcheck kernels for one
+// Instantiation of the radix-2 FFT, the pointwise field kernels and the polynomial, multilinear, sumcheck and gate-expression kernels for one
 // scalar field: compiled once per field with -DARK_UNIT_FIELD=<name>.  FieldOpsOf is the one implementation of FieldOps
 // (internal.hpp).
 #include "fft.cuh"
@@ -11,6 +11,7 @@
 #include "grand_product.cuh"
 #include "fraction_sum.cuh"
 #include "sumcheck.cuh"
+#include "gateexpr.cuh"
 #include "internal.hpp"
 #ifndef ARK_UNIT_FIELD
 #error "compile with -DARK_UNIT_FIELD=BLS12_381_FR (or another scalar field of params.hpp)"
@@ -97,6 +98,9 @@ struct FieldOpsOf final : FieldOps {
   int ratio_tile(const void* num, const void* den, size_t n, const void* cn, const void* cdi, const void* icd, void* out, void* last,
                  hipStream_t s) const override {
     return ratio_tile_launch<Fp<F>>(num, den, n, cn, cdi, icd, out, last, s);
+  }
+  int gate_sum_of_products(const GateTerms& tm, void* out, size_t n, hipStream_t s) const override {
+    return gate_sum_of_products_launch<Fp<F>>(tm, out, n, s);
   }
   int csr_stream(const CsrView& m, const void* x, void* y, hipStream_t s) const override { return csr_stream_launch<Fp<F>>(m, x, y, s); }
   int csr_long(const CsrView& m, const void* x, void* partials, void* y, hipStream_t s) const override {

@@ -22,6 +22,7 @@ struct SumcheckRound;
 struct SumcheckProve;
 struct FrLincomb;
 struct CsrView;
+struct GateTerms;
 
 // The device operations of one curve.  curve_unit.hip implements every member once, as a template over the curve; a member that
 // is missing there, or whose signature differs, does not compile.  capi_core.hpp: curve_ops(id).
@@ -94,6 +95,7 @@ struct FieldOps {
                         hipStream_t s) const = 0;
   virtual int ratio_tile(const void* d_num, const void* d_den, size_t n, const void* d_cn, const void* d_cdi, const void* d_icd,
                          void* d_out, void* d_last, hipStream_t s) const = 0;
+  virtual int gate_sum_of_products(const GateTerms& tm, void* d_out, size_t n, hipStream_t s) const = 0;
   virtual int csr_stream(const CsrView& m, const void* d_x, void* d_y, hipStream_t s) const = 0;
   virtual int csr_long(const CsrView& m, const void* d_x, void* d_partials, void* d_y, hipStream_t s) const = 0;
   virtual int fft_roots(FftWorkspace& ws, int k, const uint64_t* root4, hipStream_t s, const uint32_t** out) const = 0;

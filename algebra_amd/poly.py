@@ -265,3 +265,11 @@ class DeviceVec:
         check(lib().ark_hip_fr_prefix_ratio_device(self.field, self.ptr, den.ptr, self.len, out.ptr, last.ctypes.data_as(C.c_void_p)),
               "ark_hip_fr_prefix_ratio_device")
         return out, last
+
+    # ---- the rotated copy: the one-term case of a gate expression (algebra_amd.gates) ---------------------------------
+    def rotate(self, k, out=None):
+        """out[i] = self[(i + k) mod len] as a DeviceVec, k any integer an int64 holds: one unit term of one factor of
+        ark_hip_fr_sum_of_products_device, a product-free copy.  out: the vector to write (self only if k is 0 mod len); a
+        new one otherwise."""
+        from .gates import SumOfProducts
+        return SumOfProducts(self.field, self.len).add_product([(self, k)]).evaluate(out)

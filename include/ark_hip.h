@@ -511,6 +511,37 @@ int ark_hip_fr_prefix_ratio_device(int field, const void* d_num, const void* d_d
  * factor `tile`. */
 int ark_hip_prefix_scan_plan(int op, size_t n, int* tile, int* levels);
 
+/* ---- gate expressions on device vectors: sums of products with rotations ----------------------
+ * The row-by-row constraint expression of a univariate (Plonk-style) prover over a domain or an extended coset: for ncolumns
+ * device vectors of n elements each and nterms terms,
+ *   out[i] = c0 + sum_{j < nterms} c_j prod_{q < term_len[j]} col[ tc_{j,q} ][ (i + rot_{j,q}) mod n ],    0 <= i < n.
+ * n is any size.  A rotation is any int64_t (negative, |rot| >= n, INT64_MIN): it is reduced to [0, n) on the host with the
+ * mathematical mod; on a coset of blow-up k "the next row" is rotation k.  A column may appear in several terms and several
+ * times in one term, and the same pointer may be passed as two columns.  The univariate counterpart of the list of products
+ * of ark_hip_sumcheck_round_device: one pass instead of a composition of ark_hip_fr_mul_device, ark_hip_fr_axpy_device,
+ * ark_hip_fr_lincomb_device and copies. */
+#define ARK_HIP_SOP_MAX_COLUMNS 16
+#define ARK_HIP_SOP_MAX_TERMS   16
+#define ARK_HIP_SOP_MAX_DEGREE   8
+/* term_len, term_columns and coeffs are laid out as ark_hip_sumcheck_round_device lays out term_len, term_tables and coeffs:
+ * term j has term_len[j] factors (1 .. ARK_HIP_SOP_MAX_DEGREE), term_columns holds their column indices term after term,
+ * coeffs holds nterms elements.  term_rotations runs parallel to term_columns; NULL: every rotation is zero.  c0: a HOST
+ * element, NULL for zero.  A coefficient equal to one costs no product; one unit term of one factor without c0 is a rotated
+ * copy.  Host pointers are read before the call returns; the call is asynchronous on the context stream; exactly n elements
+ * are written, canonical residues.  n = 0 validates its arguments, launches nothing and succeeds (column pointers may be NULL).
+ * d_out may be the SAME pointer as a column only if every factor that reads that column has rotation 0 after reduction (with
+ * a rotation one workgroup would write what another still reads); any other overlap of d_out with a column is
+ * ARK_HIP_ERR_ARG.  ARK_HIP_ERR_ARG, before any device is looked for: an unknown or unserved field; a null d_columns,
+ * term_len, term_columns, coeffs or d_out; a null column pointer when n > 0; ncolumns, nterms or a term_len that is 0 or above
+ * its limit; a column index >= ncolumns; n > 2^58; the aliasing violations above. */
+int ark_hip_fr_sum_of_products_device(int field, const void* const* d_columns, unsigned ncolumns, size_t n,
+                                      const unsigned* term_len, const unsigned* term_columns,
+                                      const int64_t* term_rotations, const uint64_t* coeffs, unsigned nterms,
+                                      const uint64_t* c0, void* d_out);
+/* Host only, no device needed: the launch geometry of that call for n rows.  *blocks: workgroups of 256 lanes (0 for n = 0);
+ * *rows_per_lane: rows one lane walks -- 1 until the grid's cap is reached (0 for n = 0; saturates at INT_MAX). */
+int ark_hip_fr_sum_of_products_plan(size_t n, int* blocks, int* rows_per_lane);
+
 /* ---- dense multilinear extensions on device-resident evaluation tables ---------------------------------------------
  * DenseMultilinearExtension (poly/src/evaluations/multivariate/multilinear/dense.rs): a table of 2^num_vars evaluations over
  * the boolean hypercube, index bit 0 being the FIRST variable (index 0b1011 is P(1,1,0,1)).  Committing to such a table is

@@ -701,6 +701,24 @@ class DeviceVec {
     check(ark_hip_fr_prefix_ratio_device(FIELD_ID, p_, den.p_, len_, out.p_, last.limbs.data()), "ark_hip_fr_prefix_ratio_device");
     return {std::move(out), last};
   }
+  // ---- the rotated copy: the one-term case of a gate expression (SumOfProducts below) ----
+  // out[i] = self[(i + k) mod len], k any int64_t: one unit term of one factor, a product-free copy
+  DeviceVec rotate(int64_t k) const {
+    DeviceVec out = uninit(len_);
+    rotate(k, out);
+    return out;
+  }
+  // the same into `out` (not this vector unless k is 0 mod len)
+  void rotate(int64_t k, DeviceVec& out) const {
+    same(out);
+    if (!len_) return;
+    Fr one, any{};
+    check(ark_hip_fr_pow(FIELD_ID, any.limbs.data(), 0, one.limbs.data()), "ark_hip_fr_pow");
+    const void* col = p_;
+    const unsigned len = 1, idx = 0;
+    check(ark_hip_fr_sum_of_products_device(FIELD_ID, &col, 1, len_, &len, &idx, &k, one.limbs.data(), 1, nullptr, out.p_),
+          "ark_hip_fr_sum_of_products_device");
+  }
 
  private:
   void* p_ = nullptr;
@@ -833,6 +851,89 @@ class CsrMatrix {
   ark_hip_fr_csr* h_ = nullptr;
   size_t rows_ = 0, cols_ = 0, nnz_ = 0;
   bool has_t_ = false;
+};
+
+// The gate expression of a univariate (Plonk-style) prover on device vectors: a sum of products of
+// columns, each factor read at a rotation,
+//   out[i] = c0 + sum_j c_j prod_q col_{j,q}[(i + rot_{j,q}) mod n],
+// in one call of ark_hip_fr_sum_of_products_device -- the univariate counterpart of ListOfProducts, shaped like it.  The columns
+// are the caller's and must outlive the calls; evaluate is asynchronous on the library's stream.
+struct SumOfProductsPlan { int blocks, rows_per_lane; };
+// the launch geometry of evaluate over n rows; host only
+inline SumOfProductsPlan sum_of_products_plan(size_t n) {
+  SumOfProductsPlan p{};
+  check(ark_hip_fr_sum_of_products_plan(n, &p.blocks, &p.rows_per_lane), "ark_hip_fr_sum_of_products_plan");
+  return p;
+}
+template <int FIELD_ID>
+class SumOfProducts {
+ public:
+  using Vec = DeviceVec<FIELD_ID>;
+  struct Factor {
+    const Vec* column;
+    int64_t rotation;
+    Factor(const Vec* c, int64_t r = 0) : column(c), rotation(r) {}
+    Factor(const Vec& c, int64_t r = 0) : column(&c), rotation(r) {}
+  };
+  explicit SumOfProducts(size_t n) : n_(n) {}
+  size_t len() const { return n_; }
+  size_t num_columns() const { return columns_.size(); }
+  size_t num_products() const { return lens_.size(); }
+  // adds coefficient * prod factors (coefficient nullptr: one, which costs no product); a vector used in several products, or
+  // several times in one, is one shared column (by device pointer)
+  void add_product(const std::vector<Factor>& factors, const Fr* coefficient = nullptr) {
+    if (factors.empty() || factors.size() > ARK_HIP_SOP_MAX_DEGREE) throw Error(ARK_HIP_ERR_ARG, "a product has 1 to 8 factors");
+    if (lens_.size() >= ARK_HIP_SOP_MAX_TERMS) throw Error(ARK_HIP_ERR_ARG, "too many products");
+    std::vector<const void*> columns = columns_;
+    std::vector<unsigned> idx;
+    for (const Factor& f : factors) {
+      if (f.column->len() != n_) throw Error(ARK_HIP_ERR_ARG, "the factor's length differs from the expression's");
+      size_t i = 0;
+      while (i < columns.size() && columns[i] != f.column->device_ptr()) i++;
+      if (i == columns.size()) columns.push_back(f.column->device_ptr());
+      idx.push_back((unsigned)i);
+    }
+    if (columns.size() > ARK_HIP_SOP_MAX_COLUMNS) throw Error(ARK_HIP_ERR_ARG, "too many distinct columns");
+    Fr c;
+    if (coefficient) {
+      c = *coefficient;
+    } else {
+      Fr any{};
+      check(ark_hip_fr_pow(FIELD_ID, any.limbs.data(), 0, c.limbs.data()), "ark_hip_fr_pow");
+    }
+    columns_ = columns;
+    lens_.push_back((unsigned)idx.size());
+    flat_.insert(flat_.end(), idx.begin(), idx.end());
+    for (const Factor& f : factors) rots_.push_back(f.rotation);
+    coeffs_.push_back(c);
+  }
+  void set_constant(const Fr& c0) { c0_ = c0; has_c0_ = true; }
+  void clear_constant() { has_c0_ = false; }
+  // the expression's n rows
+  Vec evaluate() const {
+    Vec out = Vec::uninit(n_);
+    evaluate(out);
+    return out;
+  }
+  // the same into `out`: one of the columns only if every factor reads that column at a rotation that is 0 mod n
+  void evaluate(Vec& out) const {
+    if (lens_.empty()) throw Error(ARK_HIP_ERR_ARG, "no products");
+    if (out.len() != n_) throw Error(ARK_HIP_ERR_ARG, "the output's length differs from the expression's");
+    if (!n_) return;
+    check(ark_hip_fr_sum_of_products_device(FIELD_ID, columns_.data(), (unsigned)columns_.size(), n_, lens_.data(), flat_.data(),
+                                            rots_.data(), coeffs_[0].limbs.data(), (unsigned)lens_.size(),
+                                            has_c0_ ? c0_.limbs.data() : nullptr, out.device_ptr()),
+          "ark_hip_fr_sum_of_products_device");
+  }
+
+ private:
+  size_t n_;
+  std::vector<const void*> columns_;
+  std::vector<unsigned> lens_, flat_;
+  std::vector<int64_t> rots_;
+  std::vector<Fr> coeffs_;
+  Fr c0_{};
+  bool has_c0_ = false;
 };
 
 // DenseMultilinearExtension<F> resident on the device (poly/src/evaluations/multivariate/multilinear/dense.rs): 2^num_vars

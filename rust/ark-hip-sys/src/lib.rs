@@ -57,6 +57,10 @@ pub struct ark_hip_fr_csr {
 }
 /// `ark_hip_fr_csr_create`: also keep `M^T`.
 pub const ARK_HIP_CSR_WITH_TRANSPOSE: c_uint = 1;
+/// Limits of `ark_hip_fr_sum_of_products_device`: distinct columns, terms, factors of a term.
+pub const ARK_HIP_SOP_MAX_COLUMNS: c_uint = 16;
+pub const ARK_HIP_SOP_MAX_TERMS: c_uint = 16;
+pub const ARK_HIP_SOP_MAX_DEGREE: c_uint = 8;
 
 extern "C" {
     pub fn ark_hip_device_count() -> c_int;
@@ -211,6 +215,15 @@ extern "C" {
                                           out_last: *mut u64) -> c_int;
     /// Host only: tile length and scan levels of the three entries above; `op` 0 / 1 / 2 = product / sum / ratio.
     pub fn ark_hip_prefix_scan_plan(op: c_int, n: usize, tile: *mut c_int, levels: *mut c_int) -> c_int;
+    /// The gate expression of a univariate prover over `ncolumns` device vectors of `n` elements:
+    /// `out[i] = c0 + sum_j c_j prod_q col[tc_jq][(i + rot_jq) mod n]`.  `term_len` / `term_columns` / `coeffs` are laid out as
+    /// the sumcheck round lays out its terms; `term_rotations` runs parallel to `term_columns` (null: all zero; any `i64`, reduced
+    /// on the host); `c0`: host element or null.  Asynchronous.  `d_out` may be a column that is read at rotation 0 only.
+    pub fn ark_hip_fr_sum_of_products_device(field: c_int, d_columns: *const *const c_void, ncolumns: c_uint, n: usize,
+                                             term_len: *const c_uint, term_columns: *const c_uint, term_rotations: *const i64,
+                                             coeffs: *const u64, nterms: c_uint, c0: *const u64, d_out: *mut c_void) -> c_int;
+    /// Host only: workgroups of 256 lanes and rows one lane walks (1 until the grid's cap is reached) for `n` rows.
+    pub fn ark_hip_fr_sum_of_products_plan(n: usize, blocks: *mut c_int, rows_per_lane: *mut c_int) -> c_int;
     /// `DenseMultilinearExtension::fix_variables` (multilinear/dense.rs:224-257) on a device table of `2^num_vars` elements:
     /// binds the first `dim` variables, writes `2^(num_vars - dim)` elements; `d_out` must not overlap `d_evals`.
     pub fn ark_hip_mle_fix_variables_device(field: c_int, d_evals: *const c_void, num_vars: c_uint, partial_point: *const u64,

@@ -18,7 +18,7 @@ use ark_ff::FftField;
 use ark_hip_sys as sys;
 use ark_poly::domain::{EvaluationDomain, Radix2EvaluationDomain};
 use ark_std::vec::Vec;
-use core::ffi::{c_int, c_void};
+use core::ffi::{c_int, c_uint, c_void};
 use core::marker::PhantomData;
 use core::ops::{AddAssign, DivAssign, MulAssign, SubAssign};
 
@@ -269,6 +269,12 @@ impl<F: FftField> DeviceVec<F> {
         rc(unsafe { sys::ark_hip_domain_lagrange_coefficients_device(v.field, &d, t.as_ptr(), v.ptr) })?;
         Ok(v)
     }
+    /// `out[i] = self[(i + k) mod len]`, `k` any `i64`: the one-term case of [`SumOfProducts`], a product-free copy.
+    pub fn rotate(&self, k: i64) -> Result<Self, DeviceError> {
+        let mut s = SumOfProducts::new(self.len);
+        s.add_product(&[(self, k)], None)?;
+        s.evaluate()
+    }
 }
 impl<F: FftField> Drop for DeviceVec<F> {
     fn drop(&mut self) {
@@ -372,6 +378,100 @@ impl<F: FftField> CsrMatrix<F> {
 impl<F: FftField> Drop for CsrMatrix<F> {
     fn drop(&mut self) {
         unsafe { sys::ark_hip_fr_csr_free(self.handle) };
+    }
+}
+
+/// `ARK_HIP_SOP_MAX_COLUMNS`, `_MAX_TERMS`, `_MAX_DEGREE` of include/ark_hip.h
+pub const SOP_MAX_COLUMNS: usize = sys::ARK_HIP_SOP_MAX_COLUMNS as usize;
+pub const SOP_MAX_TERMS: usize = sys::ARK_HIP_SOP_MAX_TERMS as usize;
+pub const SOP_MAX_DEGREE: usize = sys::ARK_HIP_SOP_MAX_DEGREE as usize;
+/// `ark_hip_fr_sum_of_products_plan`: workgroups of 256 lanes and the rows one lane walks for `n` rows (host only).
+pub fn sum_of_products_plan(n: usize) -> Result<(c_int, c_int), DeviceError> {
+    let (mut blocks, mut rows_per_lane) = (0, 0);
+    rc(unsafe { sys::ark_hip_fr_sum_of_products_plan(n, &mut blocks, &mut rows_per_lane) })?;
+    Ok((blocks, rows_per_lane))
+}
+/// The gate expression of a univariate (Plonk-style) prover on device vectors: a sum of products of
+/// columns, each factor read at a rotation, `out[i] = c0 + sum_j c_j prod_q col_jq[(i + rot_jq) mod n]`, in one call of
+/// `ark_hip_fr_sum_of_products_device` -- the univariate counterpart of `ListOfProducts`.  The columns are borrowed for the
+/// expression's lifetime; a vector used in several products, or several times in one, is one shared column.
+pub struct SumOfProducts<'a, F: FftField> {
+    n: usize,
+    columns: Vec<&'a DeviceVec<F>>,
+    lens: Vec<c_uint>,
+    flat: Vec<c_uint>,
+    rotations: Vec<i64>,
+    coeffs: Vec<F>,
+    constant: Option<F>,
+}
+impl<'a, F: FftField> SumOfProducts<'a, F> {
+    pub fn new(n: usize) -> Self {
+        Self { n, columns: Vec::new(), lens: Vec::new(), flat: Vec::new(), rotations: Vec::new(), coeffs: Vec::new(), constant: None }
+    }
+    /// Adds `coefficient * prod factors` (`None`: one, which costs no product); a factor is a column and its rotation.
+    /// `Err(Mismatch)` for a length that differs from the expression's or a limit exceeded; nothing is added then.
+    pub fn add_product(&mut self, factors: &[(&'a DeviceVec<F>, i64)], coefficient: Option<F>) -> Result<(), DeviceError> {
+        if factors.is_empty() || factors.len() > SOP_MAX_DEGREE || self.lens.len() >= SOP_MAX_TERMS {
+            return Err(DeviceError::Mismatch);
+        }
+        let mut columns = self.columns.clone();
+        let mut idx = Vec::with_capacity(factors.len());
+        for (v, _) in factors {
+            v.here()?;
+            if v.len != self.n {
+                return Err(DeviceError::Mismatch);
+            }
+            let at = match columns.iter().position(|c| c.ptr == v.ptr) {
+                Some(i) => i,
+                None => {
+                    columns.push(v);
+                    columns.len() - 1
+                }
+            };
+            idx.push(at as c_uint);
+        }
+        if columns.len() > SOP_MAX_COLUMNS {
+            return Err(DeviceError::Mismatch);
+        }
+        self.columns = columns;
+        self.lens.push(idx.len() as c_uint);
+        self.flat.extend(idx);
+        self.rotations.extend(factors.iter().map(|(_, r)| *r));
+        self.coeffs.push(coefficient.unwrap_or(F::ONE));
+        Ok(())
+    }
+    pub fn set_constant(&mut self, c0: Option<F>) {
+        self.constant = c0;
+    }
+    /// The expression's `n` rows; asynchronous.
+    pub fn evaluate(&self) -> Result<DeviceVec<F>, DeviceError> {
+        let out = DeviceVec::<F>::alloc(self.n)?;
+        self.run(out.ptr)?;
+        Ok(out)
+    }
+    /// The same over `out`, which may be one of the columns if every factor reads that column at a rotation that is 0 mod
+    /// `n` -- by raw pointer, since the column is borrowed: `out` must hold `n` elements of this device.
+    ///
+    /// # Safety
+    /// `out` is device memory of `n` elements owned by the caller.
+    pub unsafe fn evaluate_into(&self, out: *mut c_void) -> Result<(), DeviceError> {
+        self.run(out)
+    }
+    fn run(&self, out: *mut c_void) -> Result<(), DeviceError> {
+        if self.lens.is_empty() {
+            return Err(DeviceError::Mismatch);
+        }
+        if self.n == 0 {
+            return Ok(());
+        }
+        let field = DeviceVec::<F>::field_id()?;
+        let ptrs: Vec<*const c_void> = self.columns.iter().map(|c| c.ptr as *const c_void).collect();
+        let c0 = self.constant.as_ref().map(sys::limbs);
+        rc(unsafe {
+            sys::ark_hip_fr_sum_of_products_device(field, ptrs.as_ptr(), ptrs.len() as c_uint, self.n, self.lens.as_ptr(), self.flat.as_ptr(),
+                                                   self.rotations.as_ptr(), self.coeffs.as_ptr() as *const u64, self.lens.len() as c_uint,
+                                                   c0.as_ref().map_or(core::ptr::null(), |c| c.as_ptr()), out)
+        })
     }
 }
 

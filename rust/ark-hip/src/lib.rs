@@ -37,7 +37,7 @@ pub mod points;
 pub mod sumcheck;
 pub use ark_hip_sys as sys;
 pub use ark_hip_sys::{BLS12_377_G1, BLS12_377_G2, BLS12_381_G1, BLS12_381_G2, BN254_G1};
-pub use device::{csr_plan, CsrMatrix, CsrPlan, DeviceError, DeviceEvaluations, DeviceVec};
+pub use device::{csr_plan, sum_of_products_plan, CsrMatrix, CsrPlan, DeviceError, DeviceEvaluations, DeviceVec, SumOfProducts};
 pub use points::DevicePoints;
 pub use mle::{DenseMultilinearExtension, DeviceMultilinearExtension, FractionTree, ProductTree, Quotients};
 pub use sumcheck::{ListOfProducts, SumcheckProof, Transcript};
