@@ -22,7 +22,7 @@ from .domain import Radix2EvaluationDomain  # noqa: F401
 from .poly import DeviceVec, poly_mul, poly_mul_host, prefix_scan_plan  # noqa: F401
 from .sparse import CsrMatrix, csr_plan  # noqa: F401
 from .points import DevicePoints  # noqa: F401
-from .mle import (DenseMultilinearExtension, DeviceSegment, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_fraction_tree_launches,  # noqa: F401
+from .mle import (DenseMultilinearExtension, DeviceSegment, lookup_plan, mle_eq_plan, mle_fold_plan, mle_fold_tiles, mle_fraction_tree_launches,  # noqa: F401
                   mle_fraction_tree_plan, mle_product_tree_launches, mle_product_tree_plan, mle_quotients_plan)
 from .sumcheck import ListOfProducts, SumcheckProof, sumcheck_plan, sumcheck_prove_plan  # noqa: F401
 from .gates import SumOfProducts, sum_of_products_plan  # noqa: F401

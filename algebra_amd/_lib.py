@@ -172,6 +172,9 @@ SYMBOLS = {
     "ark_hip_mle_fraction_tree_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ark_hip_mle_fraction_tree_plan": (C.c_int, [C.c_uint, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ark_hip_fr_count_indices_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "ark_hip_fr_lookup_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_uint64)]),
+    "ark_hip_fr_lookup_plan": (C.c_int, [C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]),
     "ark_hip_fr_csr_create": (C.c_int, [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint,
                                         C.POINTER(C.c_void_p)]),
     "ark_hip_fr_csr_free": (C.c_int, [C.c_void_p]),
@@ -244,6 +247,7 @@ TEST_SYMBOLS.update({
     "ark_hip_test_transcript_challenge_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]),
     "ark_hip_test_csr_dump": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                         C.c_size_t]),
+    "ark_hip_test_lookup_slot": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.POINTER(C.c_uint32)]),
 })
 TEST_LIB_PATH = os.path.join(_HERE, "libark_hip_test.so")
 

@@ -3,7 +3,7 @@
 // prefix sums and ratio accumulators (prefixscan.cuh) -- and dense
 // multilinear extensions: fix_variables, evaluate, relabel, a + k x, the eq table and an opening's quotients -- and the
 // sumcheck prover's round over such tables, the product tree of a grand product and its fingerprints, the fraction tree and the
-// multiplicities of a lookup, the Fiat-Shamir transcript and the whole sumcheck proof in one wait, and the gate expression of a
+// multiplicities of a lookup (from indices, and from the values themselves: lookup.cuh), the Fiat-Shamir transcript and the whole sumcheck proof in one wait, and the gate expression of a
 // univariate prover: sums of products of columns read at rotations (see include/ark_hip.h;
 // kernels: polyops.cuh, mle.cuh, mle_open.cuh, sumcheck.cuh, transcript.cuh, grand_product.cuh, fraction_sum.cuh, gateexpr.cuh).
 #include "capi_core.hpp"
@@ -14,6 +14,7 @@
 #include "mle_open.cuh"
 #include "grand_product.cuh"
 #include "fraction_sum.cuh"
+#include "lookup.cuh"
 #include "sumcheck.cuh"
 #include "gateexpr.cuh"
 using namespace arkhip;
@@ -681,6 +682,47 @@ int ark_hip_fr_count_indices_device(int field, const uint32_t* d_indices, size_t
   Context* c = sc.c;
   if (int rc = ops->fr_count(d_indices, n, d_out, table_len, c->stream)) return rc;
   return mark_producer(c);
+}
+
+// ---- lookup by value ----
+static_assert(LOOKUP_EMPTY == ARK_HIP_LOOKUP_MISSING, "the header publishes the index of a cell that is not in the table");
+int ark_hip_fr_lookup_plan(size_t table_len, unsigned* capacity_log, size_t* scratch_bytes) {
+  if (!capacity_log || !scratch_bytes || table_len == 0 || table_len > ((size_t)1 << LOOKUP_MAX_TABLE_LOG)) return ARK_HIP_ERR_ARG;
+  *capacity_log = lookup_capacity_log(table_len);
+  *scratch_bytes = lookup_scratch_bytes(*capacity_log);
+  return 0;
+}
+
+int ark_hip_fr_lookup_device(int field, const void* d_table, size_t table_len, const void* d_values, size_t n, uint32_t* d_indices,
+                             void* d_mult, uint64_t* out_missing) {
+  const FieldOps* ops = field_ops(field);
+  if (!ops || !d_table || (n && !d_values) || table_len == 0 || table_len > ((size_t)1 << LOOKUP_MAX_TABLE_LOG)) return ARK_HIP_ERR_ARG;
+  if ((uint64_t)n >> 32 || (!d_indices && !d_mult && !out_missing)) return ARK_HIP_ERR_ARG;
+  const size_t tb = table_len * 32;
+  if (d_mult && (ranges_overlap(d_mult, tb, d_table, tb) || (n && ranges_overlap(d_mult, tb, d_values, n * 32)))) return ARK_HIP_ERR_ARG;
+  if (d_indices && n &&
+      (ranges_overlap(d_indices, n * 4, d_table, tb) || ranges_overlap(d_indices, n * 4, d_values, n * 32) ||
+       (d_mult && ranges_overlap(d_indices, n * 4, d_mult, tb))))
+    return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  Context* c = sc.c;
+  FrLookup lk = {};
+  lk.capacity_log = lookup_capacity_log(table_len);
+  // [result slot | miss counter | slots]
+  if (int rc = poly_scratch(c, lookup_scratch_bytes(lk.capacity_log) / 32)) return rc;
+  lk.table = d_table;
+  lk.table_len = table_len;
+  lk.values = d_values;
+  lk.n = n;
+  lk.indices = d_indices;
+  lk.mult = d_mult;
+  lk.missing = (unsigned long long*)((char*)c->poly_work.p + 32);
+  lk.slots = (u32*)((char*)c->poly_work.p + 64);
+  if (int rc = ops->fr_lookup(lk, c->stream)) return rc;
+  if (!out_missing) return mark_producer(c);
+  ARK_HIP_TRY(hipMemcpyAsync(out_missing, lk.missing, 8, hipMemcpyDeviceToHost, c->stream));
+  ARK_HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 int ark_hip_sumcheck_plan(unsigned num_vars, unsigned ntables, unsigned degree, int fused, int* blocks, int* pairs_per_lane,

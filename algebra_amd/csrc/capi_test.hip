@@ -518,6 +518,15 @@ int ark_hip_test_transcript_challenge_device(int field, uint8_t* state, const ui
   ARK_HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
+// the home slot the lookup kernels give an element: host only, no device
+int ark_hip_test_lookup_slot(int field, const uint64_t* element, unsigned capacity_log, uint32_t* slot) {
+  const TestFieldOps* ops = test_field_ops(field);
+  if (!ops || !element || !slot || capacity_log < 1 || capacity_log > 29) return ARK_HIP_ERR_ARG;
+  u32 w[8];
+  for (int q = 0; q < 4; q++) { w[2 * q] = (u32)element[q]; w[2 * q + 1] = (u32)(element[q] >> 32); }
+  *slot = ops->lookup_slot(w, capacity_log);
+  return 0;
+}
 
 int ark_hip_test_relaxed_acc_op(int curve, int kind, const void* acc, const void* other, void* out, size_t n) {
   using namespace arkhip::relaxtest;

@@ -1,4 +1,4 @@
-// Instantiation of the radix-2 FFT, the pointwise field kernels and the polynomial, multilinear, sumcheck and gate-expression kernels for one
+// Instantiation of the radix-2 FFT, the pointwise field kernels and the polynomial, multilinear, sumcheck, lookup and gate-expression kernels for one
 // scalar field: compiled once per field with -DARK_UNIT_FIELD=<name>.  FieldOpsOf is the one implementation of FieldOps
 // (internal.hpp).
 #include "fft.cuh"
@@ -10,6 +10,7 @@
 #include "mle_open.cuh"
 #include "grand_product.cuh"
 #include "fraction_sum.cuh"
+#include "lookup.cuh"
 #include "sumcheck.cuh"
 #include "gateexpr.cuh"
 #include "internal.hpp"
@@ -86,6 +87,7 @@ struct FieldOpsOf final : FieldOps {
   int fr_count(const void* indices, size_t n, void* out, size_t table_len, hipStream_t s) const override {
     return fr_count_launch<Fp<F>>(indices, n, out, table_len, s);
   }
+  int fr_lookup(const FrLookup& lk, hipStream_t s) const override { return fr_lookup_launch<Fp<F>>(lk, s); }
   int sumcheck_round(const SumcheckRound& rd, hipStream_t s) const override { return sumcheck_round_launch<Fp<F>>(rd, s); }
   int sumcheck_prove(const SumcheckProve& pv, hipStream_t s) const override { return sumcheck_prove_run<Fp<F>>(pv, s); }
   int scan_tile_total(int op, const void* src, size_t n, void* totals, hipStream_t s) const override {

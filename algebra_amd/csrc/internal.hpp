@@ -22,6 +22,7 @@ struct SumcheckRound;
 struct SumcheckProve;
 struct FrLincomb;
 struct CsrView;
+struct FrLookup;
 struct GateTerms;
 
 // The device operations of one curve.  curve_unit.hip implements every member once, as a template over the curve; a member that
@@ -88,6 +89,7 @@ struct FieldOps {
   virtual int frac_tree(const void* d_nsrc, const void* d_dsrc, int log_n, int w, void* d_ndst, void* d_ddst,
                         hipStream_t s) const = 0;
   virtual int fr_count(const void* d_indices, size_t n, void* d_out, size_t table_len, hipStream_t s) const = 0;
+  virtual int fr_lookup(const FrLookup& lk, hipStream_t s) const = 0;
   virtual int sumcheck_round(const SumcheckRound& rd, hipStream_t s) const = 0;
   virtual int sumcheck_prove(const SumcheckProve& pv, hipStream_t s) const = 0;
   virtual int scan_tile_total(int op, const void* d_src, size_t n, void* d_totals, hipStream_t s) const = 0;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 namespace arkhip {
 // raw-limb hooks (lazytest.cuh, relaxtest.cuh): a scalar field's unit serves its FpL / Fft29 / relaxed Fp ops; a G1 unit serves
@@ -17,6 +18,8 @@ struct TestFieldOps : TestRawOps {
   // d_out: the element; the new state replaces d_msg's first eight words)
   virtual int transcript_reduce(const void* d_words16, void* d_out, hipStream_t s) const = 0;
   virtual int transcript_challenge(void* d_msg, const void* d_elements, unsigned count, void* d_out, hipStream_t s) const = 0;
+  // host only: the home slot of one element (eight 32-bit words) in a lookup table of 2^capacity_log slots (lookup_hash.hpp)
+  virtual uint32_t lookup_slot(const uint32_t* words8, unsigned capacity_log) const = 0;
 };
 struct TestCurveOps : TestRawOps {
   virtual int basefield_op(int op, const void* d_a, const void* d_b, void* d_r, size_t n, hipStream_t s) const = 0;

@@ -5,6 +5,7 @@
 #include "lazytest.cuh"
 #include "relaxtest.cuh"
 #include "transcript.cuh"
+#include "lookup_hash.hpp"
 #include "testops_api.hpp"
 #ifndef ARK_TEST_FIELD
 #error "compile with -DARK_TEST_FIELD=BLS12_381_FR (or another scalar field of params.hpp)"
@@ -38,6 +39,10 @@ struct TestFieldOpsOf final : TestFieldOps {
   int transcript_challenge(void* msg, const void* elements, unsigned count, void* out, hipStream_t s) const override {
     hipLaunchKernelGGL((transcript_challenge_test_kernel<Fp<F>>), dim3(1), dim3(64), 0, s, (u32*)msg, (const char*)elements, count, (char*)out);
     return hipGetLastError() == hipSuccess ? 0 : -1000;
+  }
+  uint32_t lookup_slot(const uint32_t* words8, unsigned capacity_log) const override {
+    static_assert(Fp<F>::N == 8, "the hash takes the element's eight words");
+    return lookup_home_slot(words8, capacity_log);
   }
 };
 }  // namespace

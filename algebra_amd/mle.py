@@ -87,6 +87,17 @@ def mle_fraction_tree_launches(num_vars, has_num=True):
     return [(w, bool(has_num) or i > 0) for i, w in enumerate(out)]
 
 
+LOOKUP_MISSING = 0xFFFFFFFF     # ARK_HIP_LOOKUP_MISSING of include/ark_hip.h: the index of a witness cell that is not in the table
+
+
+def lookup_plan(table_len):
+    """(capacity_log, scratch_bytes) of `lookup` against a table of table_len values, as ark_hip_fr_lookup_plan reports them:
+    2^capacity_log >= 2 table_len slots are hashed into per call, in scratch_bytes of the context's scratch"""
+    c, b = C.c_uint(), C.c_size_t()
+    check(lib().ark_hip_fr_lookup_plan(int(table_len), C.byref(c), C.byref(b)), "ark_hip_fr_lookup_plan")
+    return c.value, b.value
+
+
 class DeviceSegment:
     """`len` elements inside a DeviceVec, from element `offset` on: a view, no copy.  `ptr` is a device pointer that the
     MSM's device entries accept as a scalar vector; the view keeps its owner alive."""
@@ -316,6 +327,53 @@ class DenseMultilinearExtension:
         if table_len & (table_len - 1) == 0:
             return DenseMultilinearExtension(table_len.bit_length() - 1, out)
         return out
+
+    # ---- lookup by value ------------------------------------------------------------------
+    @staticmethod
+    def lookup(table, values, indices=False, multiplicities=True, wait=True):
+        """the join of a lookup on the device, from the values: `table` and `values` are device vectors of one field (a
+        DeviceVec, an extension or a DeviceSegment).  -> (m, missing, idx):
+          m        m[j] = #{i : values[i] is found at j}, j the FIRST occurrence of the value in the table (a repeated table
+                   value keeps zero in its later cells): a new DenseMultilinearExtension when len(table) is a power of two,
+                   else a DeviceVec; None with multiplicities=False;
+          missing  the number of cells of `values` that are not in the table; None with wait=False, which leaves the call
+                   asynchronous;
+          idx      numpy uint32 [len(values)], LOOKUP_MISSING where not found; downloaded only with indices=True, else None.
+        At least one of the three must be asked for."""
+        table = getattr(table, "evaluations", table)
+        values = getattr(values, "evaluations", values)
+        if table.field != values.field:
+            raise ValueError("vectors over different fields")
+        table_len, n = len(table), len(values)
+        if table_len < 1:
+            raise ValueError("the table is empty")
+        if not (indices or multiplicities or wait):
+            raise ValueError("nothing is asked for")
+        out = DeviceVec(table.field, table_len, _zero=False) if multiplicities else None
+        d_idx = C.c_void_p(0)
+        missing = C.c_uint64(0)
+        idx = None
+        try:
+            if indices and n:
+                check(lib().ark_hip_malloc(4 * n, C.byref(d_idx)), "ark_hip_malloc")
+            check(lib().ark_hip_fr_lookup_device(table.field, _device_pointer(table), table_len, _device_pointer(values) if n else None, n,
+                                                 d_idx if d_idx.value else None, out.ptr if multiplicities else None,
+                                                 C.byref(missing) if wait or not (d_idx.value or multiplicities) else None),
+                  "ark_hip_fr_lookup_device")
+            if indices:
+                idx = np.empty(n, dtype=np.uint32)
+                if n:
+                    check(lib().ark_hip_memcpy_d2h(idx.ctypes.data_as(C.c_void_p), d_idx, idx.nbytes), "ark_hip_memcpy_d2h")
+        except Exception:
+            if out is not None:
+                out.free()
+            raise
+        finally:
+            if d_idx.value:
+                check(lib().ark_hip_free(d_idx), "ark_hip_free")
+        if out is not None and table_len & (table_len - 1) == 0:
+            out = DenseMultilinearExtension(table_len.bit_length() - 1, out)
+        return out, (missing.value if wait else None), idx
 
     # ---- relabel ------------------------------------------------------------------------------------------------
     def _relabel(self, a, b, k, dst):

@@ -663,6 +663,34 @@ int ark_hip_mle_fraction_tree_plan(unsigned num_vars, int has_num, int* passes, 
  * table_len > 2^58, or d_out overlapping the indices.  Asynchronous. */
 int ark_hip_fr_count_indices_device(int field, const uint32_t* d_indices, size_t n, void* d_out, size_t table_len);
 
+/* ---- lookup by value on device vectors ----------------------------------------------------------
+ * The join of a lookup argument, from the VALUES: for a table t of table_len elements and a witness w of n elements, both
+ * device-resident (a column, or tuples that ark_hip_fr_lincomb_device has compressed with theta), the index of every witness
+ * cell in the table and the multiplicities m_j = #{i : w_i = t_j}, without an index array from the host.  Elements are
+ * 4 x u64 canonical Montgomery residues as in the rest of the ark_hip_fr_*_device block; they are not checked, and two
+ * elements are equal exactly when their eight 32-bit words are equal.
+ *   d_indices (n uint32_t, or NULL): d_indices[i] = the SMALLEST j with d_table[j] == d_values[i], or
+ *     ARK_HIP_LOOKUP_MISSING when there is none.
+ *   d_mult (table_len elements, or NULL): d_mult[j] = #{i : d_indices[i] = j} as a Montgomery element.  When a table value is
+ *     repeated, its FIRST occurrence receives all the counts and the later ones receive zero: sum_j m_j / (gamma + t_j) is then
+ *     still sum over the found cells of 1 / (gamma + w_i), which is what the fractional sum of a lookup needs.  d_mult may hold
+ *     anything beforehand; n = 0 writes zeros.
+ *   out_missing (HOST, or NULL): the number of witness cells that were not found; the call waits for it.  NULL makes the
+ *     call asynchronous on the context stream.
+ * At least one of the three outputs must be non-NULL; out_missing alone is a membership check.  The two inputs may overlap or be
+ * the same pointer: looking a table up in itself yields each entry's first occurrence.  The inputs are left untouched.
+ * The table is hashed per call into 2^capacity_log four-byte slots (open addressing, load factor at most 1/2) in the
+ * context's scratch, see ark_hip_fr_lookup_plan; nothing is kept between calls.  The result does not depend on scheduling.
+ * ARK_HIP_ERR_ARG comes before any device is touched for an unknown field, table_len = 0, table_len > 2^28, n >= 2^32, a
+ * null input with a non-zero length, all three outputs NULL, or an output that overlaps an input or the other output. */
+#define ARK_HIP_LOOKUP_MISSING 0xFFFFFFFFu
+int ark_hip_fr_lookup_device(int field, const void* d_table, size_t table_len, const void* d_values, size_t n,
+                             uint32_t* d_indices, void* d_mult, uint64_t* out_missing);
+/* Host only, no device needed: capacity_log = the smallest c >= 1 with 2^c >= 2 * table_len, and scratch_bytes = what that
+ * call asks of the context's scratch buffer (a result slot, the miss counter and the slots).  ARK_HIP_ERR_ARG for a null
+ * pointer, table_len = 0 or table_len > 2^28. */
+int ark_hip_fr_lookup_plan(size_t table_len, unsigned* capacity_log, size_t* scratch_bytes);
+
 /* ---- sparse constraint matrices on the device ---------------------------------------------------
  * The matrices of an R1CS / CCS instance in CSR form, resident on the device, and their products with device vectors:
  * A z, B z, C z in front of a quotient or a sumcheck, M^T eq(rx) for the second sumcheck of a Spartan-style prover, and with
@@ -960,6 +988,10 @@ int ark_hip_test_transcript_challenge_device(int field, uint8_t* state, const ui
  * Waits for the device. */
 int ark_hip_test_csr_dump(const ark_hip_fr_csr* m, int transpose, size_t* dims, uint32_t* row_ptr, size_t row_ptr_cap,
                           uint32_t* col_idx, uint64_t* vals, size_t nnz_cap);
+/* Host only, no device needed: the home slot of `element` (4 x u64) in a lookup table of 2^capacity_log slots, from the one hash
+ * function the kernels of ark_hip_fr_lookup_device use (csrc/lookup_hash.hpp), so that a test can construct colliding tables
+ * instead of hoping for them.  ARK_HIP_ERR_ARG for an unknown field, a null pointer or capacity_log outside 1 .. 29. */
+int ark_hip_test_lookup_slot(int field, const uint64_t* element, unsigned capacity_log, uint32_t* slot);
 
 #endif /* ARK_HIP_TEST_HOOKS */
 

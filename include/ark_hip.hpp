@@ -1110,6 +1110,41 @@ class DenseMultilinearExtension {
     check(ark_hip_fr_count_indices_device(FIELD_ID, d_indices, n, out.device_ptr(), table_len), "ark_hip_fr_count_indices_device");
     return out;
   }
+  // ---- lookup by value ----
+  // The join of a lookup from the values, on the device: mult[j] = #{i : values[i] is found at j} with j the FIRST occurrence of
+  // the value in the table (a repeated table value keeps zero in its later cells), the number of cells of `values` that are not
+  // in the table, and with want_indices the index of every cell (ARK_HIP_LOOKUP_MISSING where not found), downloaded.
+  struct Lookup {
+    Vec mult;
+    uint64_t missing = 0;
+    std::vector<uint32_t> indices;
+  };
+  static Lookup lookup(const Vec& table, const Vec& values, bool want_indices = false) {
+    Lookup r;
+    const size_t n = values.len();
+    r.mult = Vec::uninit(table.len());
+    void* d_idx = nullptr;
+    if (want_indices && n) check(ark_hip_malloc(n * 4, &d_idx), "ark_hip_malloc");
+    const int rc = ark_hip_fr_lookup_device(FIELD_ID, table.device_ptr(), table.len(), n ? values.device_ptr() : nullptr, n,
+                                            static_cast<uint32_t*>(d_idx), r.mult.device_ptr(), &r.missing);
+    if (rc == 0 && d_idx) {
+      r.indices.resize(n);
+      const int rc2 = ark_hip_memcpy_d2h(r.indices.data(), d_idx, n * 4);
+      ark_hip_free(d_idx);
+      check(rc2, "ark_hip_memcpy_d2h");
+    } else if (d_idx) {
+      ark_hip_free(d_idx);
+    }
+    check(rc, "ark_hip_fr_lookup_device");
+    return r;
+  }
+  // (capacity_log, scratch_bytes) of lookup against a table of table_len values, as ark_hip_fr_lookup_plan reports them
+  static std::pair<unsigned, size_t> lookup_plan(size_t table_len) {
+    unsigned c = 0;
+    size_t b = 0;
+    check(ark_hip_fr_lookup_plan(table_len, &c, &b), "ark_hip_fr_lookup_plan");
+    return {c, b};
+  }
   // exchanges the k variables from position a with those from position b (dense.rs:76-92, :195-199)
   DenseMultilinearExtension relabel(size_t a, size_t b, size_t k) const {
     Vec out = Vec::uninit(evals_.len());

@@ -61,6 +61,8 @@ pub const ARK_HIP_CSR_WITH_TRANSPOSE: c_uint = 1;
 pub const ARK_HIP_SOP_MAX_COLUMNS: c_uint = 16;
 pub const ARK_HIP_SOP_MAX_TERMS: c_uint = 16;
 pub const ARK_HIP_SOP_MAX_DEGREE: c_uint = 8;
+/// the index `ark_hip_fr_lookup_device` writes for a witness cell that is not in the table
+pub const ARK_HIP_LOOKUP_MISSING: u32 = 0xFFFF_FFFF;
 
 extern "C" {
     pub fn ark_hip_device_count() -> c_int;
@@ -272,6 +274,13 @@ extern "C" {
     /// `d_out[j] = #{i < n : d_indices[i] = j}` for `j < table_len` as Montgomery elements; an index `>= table_len` is
     /// skipped and not reported, so the counts sum to `n` exactly when none was skipped.  Asynchronous.
     pub fn ark_hip_fr_count_indices_device(field: c_int, d_indices: *const u32, n: usize, d_out: *mut c_void, table_len: usize) -> c_int;
+    /// The join of a lookup from the values: `d_indices[i]` (null: not wanted) = the smallest `j` with `d_table[j] == d_values[i]`
+    /// or `ARK_HIP_LOOKUP_MISSING`; `d_mult[j]` (null: not wanted) = the number of cells found at `j`, as Montgomery elements, a
+    /// repeated table value counted on its first occurrence; `out_missing` (host, may be null: asynchronous) = the cells not found.
+    pub fn ark_hip_fr_lookup_device(field: c_int, d_table: *const c_void, table_len: usize, d_values: *const c_void, n: usize,
+                                    d_indices: *mut u32, d_mult: *mut c_void, out_missing: *mut u64) -> c_int;
+    /// Host only: the slots (`2^capacity_log >= 2 table_len`) and the scratch bytes of that call.
+    pub fn ark_hip_fr_lookup_plan(table_len: usize, capacity_log: *mut c_uint, scratch_bytes: *mut usize) -> c_int;
     /// A CSR matrix onto the device from HOST arrays (`row_ptr`: `rows + 1`, `col_idx` / `vals`: `nnz`), every index validated on
     /// the host first; `flags`: `ARK_HIP_CSR_WITH_TRANSPOSE` also keeps `M^T` (stable order).
     pub fn ark_hip_fr_csr_create(field: c_int, rows: usize, cols: usize, row_ptr: *const u32, col_idx: *const u32, vals: *const u64,

@@ -19,7 +19,8 @@
 //!   with the previous challenge bound in the same pass.  `DenseMultilinearExtension::eq` builds the table of `eq(r, .)` on the
 //!   device, `quotients` / `open` the quotients of a multilinear opening and their commitments, `product_tree` /
 //!   `linear_combination` the product tree and the fingerprints of a grand product, and [`grand_product::GrandProduct`] runs
-//!   its layered proof; `fraction_tree` / `count_indices` the fraction tree and the multiplicities of a lookup, and
+//!   its layered proof; `fraction_tree` / `count_indices` the fraction tree and the multiplicities of a lookup, `lookup` the
+//!   multiplicities and indices from the witness VALUES themselves, and
 //!   [`fraction_sum::FractionalSum`] runs the layered proof of a sum of fractions (logUp).
 //!
 //! Beyond the reference's surface: [`msm::PreparedBases`] (a fixed SRS resident on the GPU with its per-window

@@ -335,6 +335,29 @@ impl<F: FftField> DeviceMultilinearExtension<F> {
         rc(sys::ark_hip_fr_count_indices_device(out.field(), d_indices, n, out.as_device_mut_ptr(), table_len))?;
         Ok(out)
     }
+    /// The join of a lookup from the values, on the device: `(m, missing)` with
+    /// `m[j] = #{i : values[i] is found at j}`, `j` the FIRST occurrence of the value in `table` (a repeated table value keeps
+    /// zero in its later cells), and `missing` the number of cells of `values` that are not in the table.  Waits for `missing`.
+    /// `d_indices`: null, or room for `values.len()` device `u32` that receive each cell's index
+    /// (`sys::ARK_HIP_LOOKUP_MISSING` where not found).
+    ///
+    /// # Safety
+    /// `d_indices` must be null or point to `values.len()` `u32` in device memory of the current device.
+    pub unsafe fn lookup(table: &DeviceVec<F>, values: &DeviceVec<F>, d_indices: *mut u32) -> Result<(DeviceVec<F>, u64), DeviceError> {
+        table.here()?;
+        values.here()?;
+        let mut out = DeviceVec::<F>::alloc(table.len())?;
+        let mut missing = 0u64;
+        rc(sys::ark_hip_fr_lookup_device(out.field(), table.as_device_ptr(), table.len(), values.as_device_ptr(), values.len(),
+                                         d_indices, out.as_device_mut_ptr(), &mut missing))?;
+        Ok((out, missing))
+    }
+    /// `(capacity_log, scratch_bytes)` of `lookup` against a table of `table_len` values: host only.
+    pub fn lookup_plan(table_len: usize) -> Result<(u32, usize), DeviceError> {
+        let (mut c, mut b): (c_uint, usize) = (0, 0);
+        rc(unsafe { sys::ark_hip_fr_lookup_plan(table_len, &mut c, &mut b) })?;
+        Ok((c as u32, b))
+    }
     /// `relabel` (dense.rs:195-199): a new polynomial with the `k` variables from `a` and from `b` exchanged.
     pub fn relabel(&self, a: usize, b: usize, k: usize) -> Result<Self, DeviceError> {
         self.evals.here()?;
