@@ -29,3 +29,5 @@ from .gates import SumOfProducts, sum_of_products_plan  # noqa: F401
 from .transcript import Transcript  # noqa: F401
 from .grand_product import GrandProduct, GrandProductProof  # noqa: F401
 from .fraction_sum import FractionalSum, FractionalSumProof  # noqa: F401
+from .smallfp import (SMALL_FIELDS, SmallDeviceMatrix, SmallDeviceVec, SmallRadix2EvaluationDomain, small_fft_plan,  # noqa: F401
+                      small_field_info, small_field_pow)

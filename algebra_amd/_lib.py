@@ -35,6 +35,22 @@ class Radix2DomainStruct(C.Structure):
     ]
 
 
+class SmallRadix2DomainStruct(C.Structure):
+    """``ark_hip_sfp_radix2_domain``: Radix2EvaluationDomain<SmallFp<P>>, every element one word (zero-extended)."""
+    _fields_ = [
+        ("size", C.c_uint64),
+        ("log_size_of_group", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("size_as_field_element", C.c_uint64),
+        ("size_inv", C.c_uint64),
+        ("group_gen", C.c_uint64),
+        ("group_gen_inv", C.c_uint64),
+        ("offset", C.c_uint64),
+        ("offset_inv", C.c_uint64),
+        ("offset_pow_size", C.c_uint64),
+    ]
+
+
 # symbol -> (restype, argtypes); must list every function include/ark_hip.h declares
 SYMBOLS = {
     "ark_hip_device_count": (C.c_int, []),
@@ -193,6 +209,23 @@ SYMBOLS = {
     "ark_hip_fft_set_kernel": (C.c_int, [C.c_int]),
     "ark_hip_fft_set_timing": (C.c_int, [C.c_int]),
     "ark_hip_fft_last_timing": (C.c_int, [C.POINTER(C.c_double)]),
+    "ark_hip_sfp_info": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "ark_hip_sfp_pow": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ark_hip_sfp_radix2_domain_new": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(SmallRadix2DomainStruct)]),
+    "ark_hip_sfp_radix2_domain_get_coset": (C.c_int, [C.c_int, C.POINTER(SmallRadix2DomainStruct), C.c_uint64,
+                                                      C.POINTER(SmallRadix2DomainStruct)]),
+    "ark_hip_sfp_fft_in_place": (C.c_int, [C.c_int, C.POINTER(SmallRadix2DomainStruct), C.c_void_p, C.c_int]),
+    "ark_hip_sfp_fft_batch_device": (C.c_int, [C.c_int, C.POINTER(SmallRadix2DomainStruct), C.c_void_p, C.c_size_t, C.c_size_t,
+                                               C.c_size_t, C.c_int]),
+    "ark_hip_sfp_fft_plan": (C.c_int, [C.c_int, C.c_uint, C.POINTER(C.c_int)]),
+    "ark_hip_sfp_add_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_sfp_sub_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_sfp_mul_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_sfp_neg_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_sfp_inverse_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_sfp_scale_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
+    "ark_hip_sfp_from_canonical_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_sfp_into_canonical_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
 }
 
 # the test hooks: exported by libark_hip_test.so only (the same objects as libark_hip.so + csrc/capi_test.hip); declared in

@@ -12,7 +12,9 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <map>
 #include <mutex>
+#include <tuple>
 #include <thread>
 #include <chrono>
 #include <unistd.h>
@@ -209,6 +211,20 @@ struct BaseCacheStats {
 // context's lock for its whole body, so the library can be called from any number of host threads (rayon workers,
 // Python threads): calls on one device serialise, calls on different devices run concurrently.
 constexpr int COMM_MAX_SLICES = 16;
+// the one-word fields' transforms (capi_sfp.hip): caches per (field, log n, direction) and per (field, log n, base, constant), and
+// the buffer the last two passes of a multi-pass transform go through
+struct SfpWorkspace {
+  std::map<std::tuple<int, int, int>, DevBuf> sfp_twiddles;
+  std::map<std::tuple<int, int, uint64_t, uint64_t>, DevBuf> sfp_powers;
+  DevBuf sfp_ping;
+  void release() {
+    for (auto& kv : sfp_twiddles) kv.second.release();
+    for (auto& kv : sfp_powers) kv.second.release();
+    sfp_twiddles.clear();
+    sfp_powers.clear();
+    sfp_ping.release();
+  }
+};
 struct Context {
   int logical = -1, physical = -1;
   hipStream_t stream = nullptr;        // compute
@@ -222,6 +238,7 @@ struct Context {
   // touch lane 0 (and its memory).
   MsmWorkspace msm[2];
   FftWorkspace fft;
+  SfpWorkspace sfp;
   DevBuf stage_a, stage_b, stage_c;    // host-pointer entry points: device copies
   DevBuf gfft_work, gfft_scal;         // transform over group elements: XYZZ scratch, per-position scalars
   DevBuf check_work;                   // base-set check / decompression: the summary words

@@ -44,6 +44,7 @@ void ark_hip_shutdown(void) {
       c->msm[0].release();
       c->msm[1].release();
       c->fft.release();
+      c->sfp.release();
       c->stage_a.release();
       c->stage_b.release();
       c->stage_c.release();

@@ -17,6 +17,8 @@
 //   cache: BaseCacheEntry::dev  per (curve, host address, length), validated by a hash of the slice's full content on every call
 //   cache: PreparedBases::table  a handle the caller owns (ark_hip_msm_bases_prepare .. _free): per-window multiples of its bases
 //   cache: CsrSide::csr_ptr, CsrSide::csr_idx, CsrSide::csr_val, CsrSide::csr_work  a handle the caller owns (ark_hip_fr_csr_create .. _free): row_ptr, col_idx, vals and the row plan of M and, when asked for, of M^T
+//   cache: SfpWorkspace::sfp_twiddles  the one-word fields' per-stage twiddle tables, per (field, log n, direction)
+//   cache: SfpWorkspace::sfp_powers  their two-level coset power tables, per (field, log n, base, folded constant)
 //   cache: BatchMulTable::table  a handle the caller owns (ark_hip_batch_mul_table_new .. _free): multiples of its one base
 // Locals that live inside one call and are released, or moved into a cache, before it returns (or that only name a buffer
 // listed elsewhere):
@@ -64,6 +66,7 @@ void for_each_scratch(Context& c, Fn&& fn) {
   ARK_SCRATCH_CTX(piece_buckets);
   ARK_SCRATCH_CTX(comm_tmp); ARK_SCRATCH_CTX(comm_small); ARK_SCRATCH_CTX(comm_sums);
   ARK_SCRATCH_CTX(fft.stage); ARK_SCRATCH_CTX(fft.pw);
+  ARK_SCRATCH_CTX(sfp.sfp_ping);
 #undef ARK_SCRATCH_CTX
   int i = 0;
   for (auto& kv : c.fft.tmps) {   // one ping buffer per stream, in the map's (stable) order

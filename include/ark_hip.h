@@ -841,6 +841,53 @@ int ark_hip_fft_set_timing(int enable);
 /* [total_ms, npass, pass0_ms, pass1_ms, ...] of the last timed device transform */
 int ark_hip_fft_last_timing(double out[10]);
 
+/* ---- one-word prime fields: the reference's SmallFp<P> (ff/src/fields/models/small_fp/) for Goldilocks, BabyBear and
+ * KoalaBear.  A family of its own: these ids are NOT field ids, and every `field` argument above keeps answering
+ * ARK_HIP_ERR_ARG to anything but the three four-limb scalar fields.
+ * An element in memory is SmallFp::value, the canonical Montgomery residue x * R mod p in the field's own word: uint64_t with
+ * R = 2^64 for Goldilocks, uint32_t with R = 2^32 (not 2^31) for the two 31-bit fields.  Vectors are arrays of that word; single
+ * elements cross this interface as uint64_t, zero-extended.  Every output is canonical (< p) and equals the reference's bit for
+ * bit.  Argument errors (an unknown sfield, a null pointer -- of a vector only with n > 0 --, stride < size, num_coeffs out of range, a domain whose size is not
+ * 2^log_size_of_group, an element >= p) are ARK_HIP_ERR_ARG before any device is touched; ARK_HIP_ERR_NO_DEVICE without a GPU. */
+enum { ARK_HIP_SFP_GOLDILOCKS = 0, ARK_HIP_SFP_BABYBEAR = 1, ARK_HIP_SFP_KOALABEAR = 2 };
+typedef struct {
+  uint64_t size;
+  uint32_t log_size_of_group, _pad;
+  uint64_t size_as_field_element, size_inv, group_gen, group_gen_inv, offset, offset_inv, offset_pow_size;
+} ark_hip_sfp_radix2_domain;
+/* out = { element bytes, p, k_bits, R mod p, R^2 mod p, generator, two-adicity, two-adic root of unity }, the last three
+ * element values as stored.  Host only. */
+int ark_hip_sfp_info(int sfield, uint64_t out[8]);
+/* base^exp; host only */
+int ark_hip_sfp_pow(int sfield, uint64_t base, uint64_t exp, uint64_t* out);
+/* Radix2EvaluationDomain::new / get_coset (poly/src/domain/radix2/mod.rs:55-92): ARK_HIP_ERR_SIZE beyond the two-adicity,
+ * ARK_HIP_ERR_ARG for a zero offset or one >= p.  Host only. */
+int ark_hip_sfp_radix2_domain_new(int sfield, size_t num_coeffs, ark_hip_sfp_radix2_domain* out);
+int ark_hip_sfp_radix2_domain_get_coset(int sfield, const ark_hip_sfp_radix2_domain* dom, uint64_t offset,
+                                        ark_hip_sfp_radix2_domain* out);
+/* fft_in_place / ifft_in_place of dom->size elements in HOST memory: one upload, the transform, one download */
+int ark_hip_sfp_fft_in_place(int sfield, const ark_hip_sfp_radix2_domain* dom, void* host_data, int inverse);
+/* count transforms, the j-th in place at element offset j * stride of d_data (stride >= dom->size); asynchronous on the context
+ * stream.  Forward: only the first num_coeffs (1 .. size) elements of a column are read, the rest counts as zero (the reference's
+ * resize).  Inverse: num_coeffs must equal size.  count = 0 does nothing.  Exactly size elements per column are written; the gaps
+ * between columns are untouched. */
+int ark_hip_sfp_fft_batch_device(int sfield, const ark_hip_sfp_radix2_domain* dom, void* d_data, size_t count, size_t stride,
+                                 size_t num_coeffs, int inverse);
+/* The pass plan of a transform of 2^log_n elements, host only: out = { largest log n one workgroup transforms alone, tile log,
+ * segment log (elements per 128 bytes), passes, stages of pass 0, 1, 2, 3 }.  ARK_HIP_ERR_SIZE beyond the two-adicity. */
+int ark_hip_sfp_fft_plan(int sfield, unsigned log_n, int out[8]);
+/* Pointwise on device vectors of n elements (any n, 0 included); d_r may be d_a or d_b.  Asynchronous.  inverse: a zero stays
+ * zero.  from_canonical takes integers of the word's whole range and reduces values >= p first (SmallFpConfig::new);
+ * into_canonical gives the integer < p. */
+int ark_hip_sfp_add_device(int sfield, const void* d_a, const void* d_b, void* d_r, size_t n);
+int ark_hip_sfp_sub_device(int sfield, const void* d_a, const void* d_b, void* d_r, size_t n);
+int ark_hip_sfp_mul_device(int sfield, const void* d_a, const void* d_b, void* d_r, size_t n);
+int ark_hip_sfp_neg_device(int sfield, const void* d_a, void* d_r, size_t n);
+int ark_hip_sfp_inverse_device(int sfield, const void* d_a, void* d_r, size_t n);
+int ark_hip_sfp_scale_device(int sfield, const void* d_a, uint64_t k, void* d_r, size_t n);
+int ark_hip_sfp_from_canonical_device(int sfield, const void* d_a, void* d_r, size_t n);
+int ark_hip_sfp_into_canonical_device(int sfield, const void* d_a, void* d_r, size_t n);
+
 #ifdef ARK_HIP_TEST_HOOKS
 /* ---- device-arithmetic test hooks (used by tests/ to check the kernels' field and point
  * arithmetic against the oracle; host pointers) ----

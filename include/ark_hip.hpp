@@ -1637,5 +1637,157 @@ inline std::vector<typename Curve::ProjectiveT> sw_mul(const std::vector<typenam
   return out;
 }
 
+// ---- one-word prime fields: SmallFp<P> for Goldilocks, BabyBear, KoalaBear (ark_hip_sfp_*) ---------------------------------
+// An element is SmallFp::value, the canonical Montgomery residue in the field's own word; single elements are uint64_t.
+template <int SFIELD_ID>
+struct SmallWord { using type = uint32_t; };
+template <>
+struct SmallWord<ARK_HIP_SFP_GOLDILOCKS> { using type = uint64_t; };
+
+struct SmallFieldInfo { uint64_t bytes, p, k_bits, r, r2, generator, two_adicity, two_adic_root; };
+template <int SFIELD_ID>
+inline SmallFieldInfo small_field_info() {
+  uint64_t o[8];
+  check(ark_hip_sfp_info(SFIELD_ID, o), "ark_hip_sfp_info");
+  return SmallFieldInfo{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]};
+}
+template <int SFIELD_ID>
+inline uint64_t small_field_pow(uint64_t base, uint64_t exp) {
+  uint64_t out = 0;
+  check(ark_hip_sfp_pow(SFIELD_ID, base, exp, &out), "ark_hip_sfp_pow");
+  return out;
+}
+struct SmallFftPlan { int single_log, tile_log, seg_log; std::vector<int> stages; };
+template <int SFIELD_ID>
+inline SmallFftPlan small_fft_plan(unsigned log_n) {
+  int o[8];
+  check(ark_hip_sfp_fft_plan(SFIELD_ID, log_n, o), "ark_hip_sfp_fft_plan");
+  return SmallFftPlan{o[0], o[1], o[2], std::vector<int>(o + 4, o + 4 + o[3])};
+}
+
+template <int SFIELD_ID>
+class SmallRadix2EvaluationDomain {
+ public:
+  using Word = typename SmallWord<SFIELD_ID>::type;
+  // Radix2EvaluationDomain::new: nullopt beyond the field's two-adicity
+  static std::optional<SmallRadix2EvaluationDomain> create(size_t num_coeffs) {
+    SmallRadix2EvaluationDomain d;
+    const int rc = ark_hip_sfp_radix2_domain_new(SFIELD_ID, num_coeffs, &d.s_);
+    if (rc == ARK_HIP_ERR_SIZE) return std::nullopt;
+    check(rc, "ark_hip_sfp_radix2_domain_new");
+    return d;
+  }
+  std::optional<SmallRadix2EvaluationDomain> get_coset(uint64_t offset) const {
+    if (offset == 0) return std::nullopt;
+    SmallRadix2EvaluationDomain d;
+    check(ark_hip_sfp_radix2_domain_get_coset(SFIELD_ID, &s_, offset, &d.s_), "ark_hip_sfp_radix2_domain_get_coset");
+    return d;
+  }
+  size_t size() const { return (size_t)s_.size; }
+  uint32_t log_size_of_group() const { return s_.log_size_of_group; }
+  uint64_t size_inv() const { return s_.size_inv; }
+  uint64_t group_gen() const { return s_.group_gen; }
+  uint64_t group_gen_inv() const { return s_.group_gen_inv; }
+  uint64_t coset_offset() const { return s_.offset; }
+  uint64_t coset_offset_inv() const { return s_.offset_inv; }
+  uint64_t coset_offset_pow_size() const { return s_.offset_pow_size; }
+  const ark_hip_sfp_radix2_domain& raw() const { return s_; }
+  // host slices: zero-extended to the domain, one upload and one download
+  void fft_in_place(std::vector<Word>& x) const { host(x, 0); }
+  void ifft_in_place(std::vector<Word>& x) const { host(x, 1); }
+  // count columns on the device, `stride` elements apart; num_coeffs = 0: the whole column
+  void fft_batch_in_place(void* d_data, size_t count, size_t stride, size_t num_coeffs = 0, bool inverse = false) const {
+    check(ark_hip_sfp_fft_batch_device(SFIELD_ID, &s_, d_data, count, stride, num_coeffs ? num_coeffs : size(), inverse ? 1 : 0),
+          "ark_hip_sfp_fft_batch_device");
+  }
+
+ private:
+  void host(std::vector<Word>& x, int inverse) const {
+    if (x.size() > size()) throw Error(ARK_HIP_ERR_ARG, "more elements than the domain holds");
+    x.resize(size(), 0);
+    check(ark_hip_sfp_fft_in_place(SFIELD_ID, &s_, x.data(), inverse), "ark_hip_sfp_fft_in_place");
+  }
+  ark_hip_sfp_radix2_domain s_{};
+};
+
+template <int SFIELD_ID>
+class SmallDeviceVec {
+ public:
+  using Word = typename SmallWord<SFIELD_ID>::type;
+  using Domain = SmallRadix2EvaluationDomain<SFIELD_ID>;
+  SmallDeviceVec() = default;
+  explicit SmallDeviceVec(size_t len) {   // vec![F::zero(); len]
+    alloc(len);
+    if (len) check(ark_hip_memset_device(p_, 0, len * sizeof(Word)), "ark_hip_memset_device");
+  }
+  static SmallDeviceVec from_vec(const std::vector<Word>& x) {
+    SmallDeviceVec v;
+    v.alloc(x.size());
+    if (!x.empty()) check(ark_hip_memcpy_h2d(v.p_, x.data(), x.size() * sizeof(Word)), "ark_hip_memcpy_h2d");
+    return v;
+  }
+  SmallDeviceVec(SmallDeviceVec&& o) noexcept : p_(o.p_), len_(o.len_) { o.p_ = nullptr; o.len_ = 0; }
+  SmallDeviceVec& operator=(SmallDeviceVec&& o) noexcept {
+    if (this != &o) { release(); p_ = o.p_; len_ = o.len_; o.p_ = nullptr; o.len_ = 0; }
+    return *this;
+  }
+  SmallDeviceVec(const SmallDeviceVec&) = delete;
+  SmallDeviceVec& operator=(const SmallDeviceVec&) = delete;
+  ~SmallDeviceVec() { release(); }
+  SmallDeviceVec clone() const {
+    SmallDeviceVec v;
+    v.alloc(len_);
+    if (len_) check(ark_hip_memcpy_d2d(v.p_, p_, len_ * sizeof(Word)), "ark_hip_memcpy_d2d");
+    return v;
+  }
+  std::vector<Word> to_vec() const {
+    std::vector<Word> out(len_);
+    if (len_) check(ark_hip_memcpy_d2h(out.data(), p_, len_ * sizeof(Word)), "ark_hip_memcpy_d2h");
+    return out;
+  }
+  size_t len() const { return len_; }
+  void* device_ptr() { return p_; }
+  const void* device_ptr() const { return p_; }
+  SmallDeviceVec& operator+=(const SmallDeviceVec& o) { same(o); check(ark_hip_sfp_add_device(SFIELD_ID, p_, o.p_, p_, len_), "ark_hip_sfp_add_device"); return *this; }
+  SmallDeviceVec& operator-=(const SmallDeviceVec& o) { same(o); check(ark_hip_sfp_sub_device(SFIELD_ID, p_, o.p_, p_, len_), "ark_hip_sfp_sub_device"); return *this; }
+  SmallDeviceVec& operator*=(const SmallDeviceVec& o) { same(o); check(ark_hip_sfp_mul_device(SFIELD_ID, p_, o.p_, p_, len_), "ark_hip_sfp_mul_device"); return *this; }
+  SmallDeviceVec& scale(uint64_t k) { check(ark_hip_sfp_scale_device(SFIELD_ID, p_, k, p_, len_), "ark_hip_sfp_scale_device"); return *this; }
+  SmallDeviceVec& negate() { check(ark_hip_sfp_neg_device(SFIELD_ID, p_, p_, len_), "ark_hip_sfp_neg_device"); return *this; }
+  SmallDeviceVec& batch_inverse() { check(ark_hip_sfp_inverse_device(SFIELD_ID, p_, p_, len_), "ark_hip_sfp_inverse_device"); return *this; }
+  SmallDeviceVec& from_canonical() { check(ark_hip_sfp_from_canonical_device(SFIELD_ID, p_, p_, len_), "ark_hip_sfp_from_canonical_device"); return *this; }
+  SmallDeviceVec& into_canonical() { check(ark_hip_sfp_into_canonical_device(SFIELD_ID, p_, p_, len_), "ark_hip_sfp_into_canonical_device"); return *this; }
+  // DensePolynomial::evaluate_over_domain: domain.size() evaluations of these 1 .. size coefficients
+  SmallDeviceVec evaluate_over_domain(const Domain& d) const {
+    if (len_ == 0 || len_ > d.size()) throw Error(ARK_HIP_ERR_ARG, "1 .. domain.size() coefficients");
+    SmallDeviceVec out;
+    out.alloc(d.size());
+    check(ark_hip_memcpy_d2d(out.p_, p_, len_ * sizeof(Word)), "ark_hip_memcpy_d2d");
+    d.fft_batch_in_place(out.p_, 1, d.size(), len_, false);
+    return out;
+  }
+  // Evaluations::interpolate
+  SmallDeviceVec interpolate(const Domain& d) const {
+    if (len_ != d.size()) throw Error(ARK_HIP_ERR_ARG, "one evaluation per element of the domain");
+    SmallDeviceVec out = clone();
+    d.fft_batch_in_place(out.p_, 1, d.size(), 0, true);
+    return out;
+  }
+
+ private:
+  void alloc(size_t len) {
+    check(ark_hip_malloc((len ? len : 1) * sizeof(Word), &p_), "ark_hip_malloc");
+    len_ = len;
+  }
+  void release() {
+    if (p_) (void)ark_hip_free(p_);
+    p_ = nullptr;
+    len_ = 0;
+  }
+  void same(const SmallDeviceVec& o) const {
+    if (o.len_ != len_) throw Error(ARK_HIP_ERR_ARG, "vectors of one length are combined");
+  }
+  void* p_ = nullptr;
+  size_t len_ = 0;
+};
 
 }  // namespace ark_hip
