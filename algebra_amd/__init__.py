@@ -7,6 +7,7 @@ HIP library replaces:
     ark_poly::Radix2EvaluationDomain   -> algebra_amd.domain.Radix2EvaluationDomain
     ark_poly::DenseMultilinearExtension -> algebra_amd.mle.DenseMultilinearExtension
     ark_linear_sumcheck's ListOfProductsOfPolynomials and its prover's rounds -> algebra_amd.sumcheck.ListOfProducts
+    (no reference counterpart) SHA3-256 Merkle trees over column batches -> algebra_amd.merkle.MerkleTree
 
 All arithmetic runs in libark_hip.so (hand-written HIP for gfx950) through the C ABI of
 include/ark_hip.h; this package holds no arithmetic and no CPU fallback.
@@ -31,3 +32,4 @@ from .grand_product import GrandProduct, GrandProductProof  # noqa: F401
 from .fraction_sum import FractionalSum, FractionalSumProof  # noqa: F401
 from .smallfp import (SMALL_FIELDS, SmallDeviceMatrix, SmallDeviceVec, SmallRadix2EvaluationDomain, small_fft_plan,  # noqa: F401
                       small_field_info, small_field_pow)
+from .merkle import MerkleTree, merkle_leaf_fr, merkle_leaf_small, merkle_node, merkle_plan  # noqa: F401

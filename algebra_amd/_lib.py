@@ -226,6 +226,18 @@ SYMBOLS = {
     "ark_hip_sfp_scale_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
     "ark_hip_sfp_from_canonical_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ark_hip_sfp_into_canonical_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ark_hip_merkle_commit_sfp_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ark_hip_merkle_commit_fr_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ark_hip_merkle_open_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p]),
+    "ark_hip_merkle_leaf_sfp": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ark_hip_merkle_leaf_fr": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ark_hip_merkle_node": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ark_hip_merkle_verify_sfp": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.POINTER(C.c_int)]),
+    "ark_hip_merkle_verify_fr": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.POINTER(C.c_int)]),
+    "ark_hip_merkle_plan": (C.c_int, [C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(C.c_uint64)]),
 }
 
 # the test hooks: exported by libark_hip_test.so only (the same objects as libark_hip.so + csrc/capi_test.hip); declared in

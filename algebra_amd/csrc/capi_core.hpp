@@ -244,6 +244,7 @@ struct Context {
   DevBuf check_work;                   // base-set check / decompression: the summary words
   DevBuf pointvec_work;                // point vectors: the window tables of one launch (pointvec.cuh)
   DevBuf poly_work;                    // polynomial ops: result slot, tile values / carries of every scan level, partial sums
+  DevBuf merkle_stage;                 // Merkle openings: paths | rows | indices of one call (capi_merkle.hip)
   DevBuf ring_s[2], ring_b[2];         // double-buffered scalar / base uploads of the streaming entry points
   hipEvent_t ring_free[2] = {nullptr, nullptr}, ring_up[2] = {nullptr, nullptr};
   int ring_next = 0;

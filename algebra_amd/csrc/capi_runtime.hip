@@ -49,6 +49,7 @@ void ark_hip_shutdown(void) {
       c->stage_b.release();
       c->stage_c.release();
       c->poly_work.release();
+      c->merkle_stage.release();
       c->check_work.release();
       c->pointvec_work.release();
       for (int j = 0; j < 2; j++) {

@@ -1,4 +1,4 @@
-// Instantiation of the radix-2 FFT, the pointwise field kernels and the polynomial, multilinear, sumcheck, lookup and gate-expression kernels for one
+// Instantiation of the radix-2 FFT, the pointwise field kernels and the polynomial, multilinear, sumcheck, lookup, gate-expression and Merkle-leaf kernels for one
 // scalar field: compiled once per field with -DARK_UNIT_FIELD=<name>.  FieldOpsOf is the one implementation of FieldOps
 // (internal.hpp).
 #include "fft.cuh"
@@ -13,6 +13,7 @@
 #include "lookup.cuh"
 #include "sumcheck.cuh"
 #include "gateexpr.cuh"
+#include "merkle.cuh"
 #include "internal.hpp"
 #ifndef ARK_UNIT_FIELD
 #error "compile with -DARK_UNIT_FIELD=BLS12_381_FR (or another scalar field of params.hpp)"
@@ -107,6 +108,9 @@ struct FieldOpsOf final : FieldOps {
   int csr_stream(const CsrView& m, const void* x, void* y, hipStream_t s) const override { return csr_stream_launch<Fp<F>>(m, x, y, s); }
   int csr_long(const CsrView& m, const void* x, void* partials, void* y, hipStream_t s) const override {
     return csr_long_launch<Fp<F>>(m, x, partials, y, s);
+  }
+  int merkle_leaves(const void* data, uint64_t count, size_t stride, size_t n, void* tree, int perm, hipStream_t s) const override {
+    return merkle_leaves_fr_launch<Fp<F>>(data, count, stride, n, tree, perm, s);
   }
   int fft_axis(FftWorkspace& ws, const void* d_src, void* d_dst, unsigned G, size_t cols, const uint64_t* root4,
                hipStream_t s) const override {

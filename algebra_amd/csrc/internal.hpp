@@ -100,6 +100,8 @@ struct FieldOps {
   virtual int gate_sum_of_products(const GateTerms& tm, void* d_out, size_t n, hipStream_t s) const = 0;
   virtual int csr_stream(const CsrView& m, const void* d_x, void* d_y, hipStream_t s) const = 0;
   virtual int csr_long(const CsrView& m, const void* d_x, void* d_partials, void* d_y, hipStream_t s) const = 0;
+  virtual int merkle_leaves(const void* d_data, uint64_t count, size_t stride, size_t n, void* d_tree, int perm,
+                            hipStream_t s) const = 0;
   virtual int fft_roots(FftWorkspace& ws, int k, const uint64_t* root4, hipStream_t s, const uint32_t** out) const = 0;
   virtual int fft_scalars(FftWorkspace& ws, const uint64_t* base4, const uint64_t* mul4, size_t count, void* d_out,
                           hipStream_t s) const = 0;

@@ -61,7 +61,7 @@ void for_each_scratch(Context& c, Fn&& fn) {
 #define ARK_SCRATCH_CTX(M) fn(#M, c.M)
   ARK_SCRATCH_CTX(stage_a); ARK_SCRATCH_CTX(stage_b); ARK_SCRATCH_CTX(stage_c);
   ARK_SCRATCH_CTX(gfft_work); ARK_SCRATCH_CTX(gfft_scal); ARK_SCRATCH_CTX(check_work); ARK_SCRATCH_CTX(pointvec_work);
-  ARK_SCRATCH_CTX(poly_work);
+  ARK_SCRATCH_CTX(poly_work); ARK_SCRATCH_CTX(merkle_stage);
   ARK_SCRATCH_CTX(ring_s[0]); ARK_SCRATCH_CTX(ring_s[1]); ARK_SCRATCH_CTX(ring_b[0]); ARK_SCRATCH_CTX(ring_b[1]);
   ARK_SCRATCH_CTX(piece_buckets);
   ARK_SCRATCH_CTX(comm_tmp); ARK_SCRATCH_CTX(comm_small); ARK_SCRATCH_CTX(comm_sums);

@@ -176,6 +176,10 @@ class DenseMultilinearExtension:
     def __len__(self):
         return len(self.evaluations)
 
+    def commit(self, wait=True):
+        """MerkleTree.commit_fr of the evaluation table as one column (merkle.py)"""
+        return self.evaluations.commit(wait=wait)
+
     # ---- binding variables --------------------------------------------------------------------------------------
     def fix_variables(self, partial_point):
         """binds the first len(partial_point) variables (dense.rs:224-257); a new polynomial, self is left as it is"""

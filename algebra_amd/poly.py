@@ -120,6 +120,11 @@ class DeviceVec:
     def __len__(self):
         return self.len
 
+    def commit(self, wait=True):
+        """MerkleTree.commit_fr of this vector as one column (merkle.py)"""
+        from .merkle import MerkleTree
+        return MerkleTree.commit_fr(self.field, self, wait=wait)
+
     def resize_zeroed(self, new_len):
         """Vec::resize(new_len, F::zero()) (also truncates)"""
         L = lib()

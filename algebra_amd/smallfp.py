@@ -239,6 +239,11 @@ class SmallDeviceVec:
         check(lib().ark_hip_sfp_into_canonical_device(self.field, self._p, self._p, self.len), "ark_hip_sfp_into_canonical_device")
         return self
 
+    def commit(self, wait=True):
+        """MerkleTree.commit_small of this vector as one column (merkle.py)"""
+        from .merkle import MerkleTree
+        return MerkleTree.commit_small(self, wait=wait)
+
     def evaluate_over_domain(self, domain):
         """DensePolynomial::evaluate_over_domain: a new vector of domain.size() evaluations of these coefficients."""
         if self.len == 0 or self.len > domain.size() or domain.field != self.field:
@@ -280,6 +285,11 @@ class SmallDeviceMatrix:
     def to_host(self, length=None):
         a = self.vec.to_host().reshape(self.count, self.stride)
         return a if length is None else a[:, :length].copy()
+
+    def commit(self, n=None, wait=True):
+        """MerkleTree.commit_small over the first n elements of every column (merkle.py); n = None: the whole stride"""
+        from .merkle import MerkleTree
+        return MerkleTree.commit_small(self, n=n, wait=wait)
 
     def fft_in_place(self, domain, num_coeffs=None, inverse=False):
         domain.fft_batch_in_place(self.vec._p, self.count, self.stride, num_coeffs, inverse)

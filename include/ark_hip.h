@@ -888,6 +888,56 @@ int ark_hip_sfp_scale_device(int sfield, const void* d_a, uint64_t k, void* d_r,
 int ark_hip_sfp_from_canonical_device(int sfield, const void* d_a, void* d_r, size_t n);
 int ark_hip_sfp_into_canonical_device(int sfield, const void* d_a, void* d_r, size_t n);
 
+/* ---- Merkle commitments: SHA3-256 trees over the rows of a column batch.  An extension: the reference has no Merkle tree; the
+ * leaf encoding is pinned on it (a leaf hashes the bytes CanonicalSerialize::serialize_compressed writes for the row's elements).
+ * H = SHA3-256 (FIPS 202: rate 136 bytes, suffix 0x06); a digest is 32 bytes.
+ *   matrix  count >= 1 columns of n = 2^k elements (k >= 0); column j starts at element offset j * stride of d_data, stride >= n:
+ *           the layout of ark_hip_sfp_fft_batch_device.  count <= 2^32 - 2.
+ *   leaf(i) = H( u32_le(count) | u32_le(elem_bytes) | ser(col_0[i]) | .. | ser(col_{count-1}[i]) )
+ *           one-word fields: ser = the stored word, little-endian, 4 or 8 bytes (small_fp/serialize.rs:23-31);
+ *           Fr fields: ser = the canonical value out of Montgomery form, 32 bytes little-endian (fp/mod.rs:551-628).
+ *   node    = H( u32_le(0xFFFFFFFF) | u32_le(0) | left | right ): 72 bytes, one permutation; no leaf header equals the node's.
+ *           The 8-byte headers keep every message a whole number of 32-bit words and 8- and 32-byte elements on 64-bit lanes.
+ *   tree    2n - 1 digests in d_tree: node t at byte 32 t, the root t = 0, children 2t + 1 and 2t + 2, leaf i at t = n - 1 + i;
+ *           n = 1: the root is the leaf.
+ *   path    of index i: the k siblings from the leaf level upwards, 32 bytes each.
+ * Elements are in memory form (Montgomery) everywhere; elements >= p are not checked.
+ * ARK_HIP_ERR_ARG, before any device is touched: an unknown sfield / field; n zero or not a power of two; count = 0 or
+ * > 2^32 - 2; stride < n; elem_bytes not 4, 8 or 32; a null pointer where one is needed; d_data not aligned to its element
+ * (32-byte elements: 16 bytes) or d_tree not aligned to 16 bytes; d_tree overlapping the matrix's extent
+ * ((count - 1) * stride + n elements from d_data); an index >= n; out_rows without d_data or d_data without out_rows.
+ * ARK_HIP_ERR_SIZE: n > 2^40, or an extent beyond size_t.  ARK_HIP_ERR_NO_DEVICE from the device entries without a GPU. */
+#define ARK_HIP_MERKLE_DIGEST_BYTES 32
+/* The tree of a matrix of one-word (sfield: ARK_HIP_SFP_*) or Fr (field: a scalar-field id) elements.  out_root NULL: asynchronous
+ * on the context stream, the root is then the first 32 bytes of d_tree; out_root (HOST, 32 bytes) set: one wait.  d_data is
+ * never written; exactly (2n - 1) * 32 bytes of d_tree are written. */
+int ark_hip_merkle_commit_sfp_device(int sfield, const void* d_data, size_t count, size_t stride, size_t n, void* d_tree,
+                                     uint8_t* out_root);
+int ark_hip_merkle_commit_fr_device(int field, const void* d_data, size_t count, size_t stride, size_t n, void* d_tree,
+                                    uint8_t* out_root);
+/* Openings of q >= 0 indices (HOST, any order, repeats allowed) of a committed tree: out_paths (HOST) receives q * log2 n * 32
+ * bytes, query by query (may be NULL when n = 1 or q = 0); out_rows (HOST) receives q * count elements of elem_bytes bytes in
+ * memory form, query by query, read from d_data (the matrix the tree was built from: count, stride as then).  d_data and out_rows
+ * may both be NULL for paths only (count and stride are then ignored).  One gather launch into staged device memory, one copy,
+ * one wait. */
+int ark_hip_merkle_open_device(const void* d_tree, size_t n, const void* d_data, unsigned elem_bytes, size_t count, size_t stride,
+                               const uint64_t* indices, size_t q, void* out_rows, uint8_t* out_paths);
+/* Host only, no GPU needed.  row: the count elements of one row, contiguous, in memory form (one-word fields: the field's own
+ * word; Fr: 4 x uint64_t each).  verify: path holds log2 n digests (may be NULL when n = 1); *ok = 1 when the row at `index`
+ * with this path hashes to root, else 0 -- ARK_HIP_OK either way. */
+int ark_hip_merkle_leaf_sfp(int sfield, const void* row, size_t count, uint8_t out[32]);
+int ark_hip_merkle_leaf_fr(int field, const uint64_t* row, size_t count, uint8_t out[32]);
+int ark_hip_merkle_node(const uint8_t left[32], const uint8_t right[32], uint8_t out[32]);
+int ark_hip_merkle_verify_sfp(int sfield, const uint8_t root[32], size_t n, uint64_t index, const void* row, size_t count,
+                              const uint8_t* path, int* ok);
+int ark_hip_merkle_verify_fr(int field, const uint8_t root[32], size_t n, uint64_t index, const uint64_t* row, size_t count,
+                             const uint8_t* path, int* ok);
+/* How a commit of (n, count, elem_bytes) runs, host only: out = { tree bytes, permutations per leaf, launches of a commit,
+ * the level T from which one workgroup finishes the tree (it computes levels min(T, log2 n - 1) .. 0; level l holds 2^l nodes),
+ * workgroups of the leaf launch, workgroups of the first multi-level node launch (0 without one), node levels per multi-level
+ * launch, the permutation variant in force (0: the transcript's, 1: the one shaped for these kernels) }. */
+int ark_hip_merkle_plan(size_t n, size_t count, unsigned elem_bytes, uint64_t out[8]);
+
 #ifdef ARK_HIP_TEST_HOOKS
 /* ---- device-arithmetic test hooks (used by tests/ to check the kernels' field and point
  * arithmetic against the oracle; host pointers) ----

@@ -1790,4 +1790,120 @@ class SmallDeviceVec {
   size_t len_ = 0;
 };
 
+// ---- Merkle commitments: SHA3-256 trees over column batches (ark_hip_merkle_*) ------------------------------------------------
+// An extension (the reference has no Merkle tree); a leaf hashes the bytes serialize_compressed writes for the row's elements.
+using Digest = std::array<uint8_t, ARK_HIP_MERKLE_DIGEST_BYTES>;
+struct MerklePlan { uint64_t tree_bytes, leaf_permutations, launches, tail_level, leaf_blocks, node_blocks, levels_per_launch, permutation; };
+inline MerklePlan merkle_plan(size_t n, size_t count, unsigned elem_bytes) {
+  uint64_t o[8];
+  check(ark_hip_merkle_plan(n, count, elem_bytes, o), "ark_hip_merkle_plan");
+  return MerklePlan{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]};
+}
+inline Digest merkle_node(const Digest& left, const Digest& right) {
+  Digest d;
+  check(ark_hip_merkle_node(left.data(), right.data(), d.data()), "ark_hip_merkle_node");
+  return d;
+}
+template <int SFIELD_ID>
+inline Digest merkle_leaf_small(const std::vector<typename SmallWord<SFIELD_ID>::type>& row) {
+  Digest d;
+  check(ark_hip_merkle_leaf_sfp(SFIELD_ID, row.data(), row.size(), d.data()), "ark_hip_merkle_leaf_sfp");
+  return d;
+}
+template <int FIELD_ID>
+inline Digest merkle_leaf_fr(const std::vector<Fr>& row) {
+  Digest d;
+  check(ark_hip_merkle_leaf_fr(FIELD_ID, (const uint64_t*)row.data(), row.size(), d.data()), "ark_hip_merkle_leaf_fr");
+  return d;
+}
+
+// The tree of a committed matrix, in device memory.  The matrix stays the caller's: it must outlive every open() that asks for rows.
+class MerkleTree {
+ public:
+  MerkleTree() = default;
+  // count columns of n = 2^k one-word elements, column j at element offset j * stride of `data`
+  template <int SFIELD_ID>
+  static MerkleTree commit_small(const SmallDeviceVec<SFIELD_ID>& data, size_t count, size_t stride, size_t n, bool wait = true) {
+    if (count == 0 || stride < n || (count - 1) * stride + n > data.len()) throw Error(ARK_HIP_ERR_ARG, "the matrix lies inside the vector");
+    MerkleTree t(data.device_ptr(), sizeof(typename SmallWord<SFIELD_ID>::type), count, stride, n);
+    check(ark_hip_merkle_commit_sfp_device(SFIELD_ID, t.data_, count, stride, n, t.tree_, wait ? t.root_.data() : nullptr),
+          "ark_hip_merkle_commit_sfp_device");
+    t.have_root_ = wait;
+    return t;
+  }
+  // count columns of data.len() / count Fr elements each, one after the other
+  template <int FIELD_ID>
+  static MerkleTree commit_fr(const DeviceVec<FIELD_ID>& data, size_t count = 1, bool wait = true) {
+    if (count == 0 || data.len() == 0 || data.len() % count) throw Error(ARK_HIP_ERR_ARG, "count columns of one length");
+    const size_t n = data.len() / count;
+    MerkleTree t(data.device_ptr(), 32, count, n, n);
+    check(ark_hip_merkle_commit_fr_device(FIELD_ID, t.data_, count, n, n, t.tree_, wait ? t.root_.data() : nullptr),
+          "ark_hip_merkle_commit_fr_device");
+    t.have_root_ = wait;
+    return t;
+  }
+  MerkleTree(MerkleTree&& o) noexcept { *this = std::move(o); }
+  MerkleTree& operator=(MerkleTree&& o) noexcept {
+    if (this != &o) {
+      release();
+      tree_ = o.tree_; data_ = o.data_; elem_bytes_ = o.elem_bytes_; count_ = o.count_; stride_ = o.stride_; n_ = o.n_;
+      root_ = o.root_; have_root_ = o.have_root_;
+      o.tree_ = nullptr;
+    }
+    return *this;
+  }
+  MerkleTree(const MerkleTree&) = delete;
+  MerkleTree& operator=(const MerkleTree&) = delete;
+  ~MerkleTree() { release(); }
+  size_t size() const { return n_; }
+  size_t log_size() const { size_t k = 0; while (((size_t)1 << k) < n_) k++; return k; }
+  const void* device_ptr() const { return tree_; }
+  // after an asynchronous commit: a waiting 32-byte download
+  const Digest& root() {
+    if (!have_root_) check(ark_hip_memcpy_d2h(root_.data(), tree_, root_.size()), "ark_hip_memcpy_d2h");
+    have_root_ = true;
+    return root_;
+  }
+  // rows: q * count elements in memory form, as bytes; paths: q * log n digests, siblings from the leaf level upwards
+  struct Opening { std::vector<uint8_t> rows, paths; };
+  Opening open(const std::vector<uint64_t>& indices, bool rows = true) const {
+    Opening o;
+    o.paths.resize(indices.size() * log_size() * ARK_HIP_MERKLE_DIGEST_BYTES);
+    if (rows) o.rows.resize(indices.size() * count_ * elem_bytes_);
+    check(ark_hip_merkle_open_device(tree_, n_, rows ? data_ : nullptr, elem_bytes_, count_, stride_, indices.data(), indices.size(),
+                                     rows ? o.rows.data() : nullptr, o.paths.data()), "ark_hip_merkle_open_device");
+    return o;
+  }
+  // one opening against a root, on the host; row: the count elements in memory form
+  template <int SFIELD_ID>
+  static bool verify_small(const Digest& root, size_t n, uint64_t index, const void* row, size_t count, const uint8_t* path) {
+    int ok = 0;
+    check(ark_hip_merkle_verify_sfp(SFIELD_ID, root.data(), n, index, row, count, path, &ok), "ark_hip_merkle_verify_sfp");
+    return ok != 0;
+  }
+  template <int FIELD_ID>
+  static bool verify_fr(const Digest& root, size_t n, uint64_t index, const void* row, size_t count, const uint8_t* path) {
+    int ok = 0;
+    check(ark_hip_merkle_verify_fr(FIELD_ID, root.data(), n, index, (const uint64_t*)row, count, path, &ok), "ark_hip_merkle_verify_fr");
+    return ok != 0;
+  }
+
+ private:
+  MerkleTree(const void* data, unsigned elem_bytes, size_t count, size_t stride, size_t n)
+      : data_(data), elem_bytes_(elem_bytes), count_(count), stride_(stride), n_(n) {
+    if (n == 0 || (n & (n - 1))) throw Error(ARK_HIP_ERR_ARG, "a column holds 2^k elements");
+    check(ark_hip_malloc((2 * n - 1) * ARK_HIP_MERKLE_DIGEST_BYTES, &tree_), "ark_hip_malloc");
+  }
+  void release() {
+    if (tree_) (void)ark_hip_free(tree_);
+    tree_ = nullptr;
+  }
+  void* tree_ = nullptr;
+  const void* data_ = nullptr;
+  unsigned elem_bytes_ = 0;
+  size_t count_ = 0, stride_ = 0, n_ = 0;
+  Digest root_{};
+  bool have_root_ = false;
+};
+
 }  // namespace ark_hip
