@@ -293,6 +293,9 @@ TEST_SYMBOLS.update({
     "ark_hip_test_csr_dump": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                         C.c_size_t]),
     "ark_hip_test_lookup_slot": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.POINTER(C.c_uint32)]),
+    "ark_hip_test_context_busy": (C.c_int, [C.POINTER(C.c_int)]),
+    "ark_hip_test_job_lane": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "ark_hip_test_producer_marks": (C.c_int, [C.c_int]),
 })
 TEST_LIB_PATH = os.path.join(_HERE, "libark_hip_test.so")
 

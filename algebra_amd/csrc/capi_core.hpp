@@ -438,8 +438,12 @@ inline int sync_compute(Context* c) {  // both MSM lanes idle
   if (c->stream_b) ARK_HIP_TRY(hipStreamSynchronize(c->stream_b));
   return 0;
 }
+// TEST ONLY: off makes mark_producer record nothing (ark_hip_test_producer_marks of libark_hip_test.so is the only setter; the
+// negative control of tests/test_gpu_async_contract.py: without the event the second lane must be seen to run ahead)
+inline std::atomic<bool> g_producer_marks{true};
 // called by every entry point that leaves work running on the context stream whose OUTPUT a caller may hand to an MSM
 inline int mark_producer(Context* c) {
+  if (!g_producer_marks.load(std::memory_order_relaxed)) return 0;
   if (!c->lane_ev) ARK_HIP_TRY(hipEventCreateWithFlags(&c->lane_ev, hipEventDisableTiming));
   ARK_HIP_TRY(hipEventRecord(c->lane_ev, c->stream));
   c->lane_ev_set = true;

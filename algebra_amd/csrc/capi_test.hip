@@ -773,4 +773,29 @@ int ark_hip_test_csr_dump(const ark_hip_fr_csr* m, int transpose, size_t* dims, 
   }
   return 0;
 }
+// ---- the asynchrony contract (tests/test_gpu_async_contract.py) ----
+// *busy = 1 while work enqueued on the context stream has not finished: the non-vacuity check of every case (the blocker was
+// still running when the host side of the case was done).  Waits for nothing.
+int ark_hip_test_context_busy(int* busy) {
+  if (!busy) return ARK_HIP_ERR_ARG;
+  ARK_SCOPE(sc);
+  const hipError_t e = hipStreamQuery(sc.c->stream);
+  if (e != hipSuccess && e != hipErrorNotReady) return -1000 - (int)e;
+  if (e == hipErrorNotReady) (void)hipGetLastError();   // "not ready" is the answer, not an error to leave behind
+  *busy = e == hipErrorNotReady ? 1 : 0;
+  return 0;
+}
+// the MSM lane (0 or 1) an asynchronous job was enqueued on; host only
+int ark_hip_test_job_lane(const ark_hip_msm_job* job, int* lane) {
+  const MsmJobHandle* h = (const MsmJobHandle*)job;
+  if (!h || !lane || h->slot < 0 || h->slot >= 2 * MSM_JOBS) return ARK_HIP_ERR_ARG;
+  *lane = h->slot / MSM_JOBS;
+  return 0;
+}
+// on = 0: mark_producer records no event from here on (process-wide; default on).  The negative control: what a forgotten
+// mark looks like.  Host only.
+int ark_hip_test_producer_marks(int on) {
+  g_producer_marks.store(on != 0, std::memory_order_relaxed);
+  return 0;
+}
 }  // extern "C"

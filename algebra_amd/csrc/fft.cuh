@@ -960,8 +960,7 @@ struct FftWorkspace {
   std::map<FftPwKey, DevBuf> powers;   // per (field, log n, offset[, constant]): [lo (1024) | hi (n >> 10)]
   std::map<hipStream_t, DevBuf> tmps;  // ping buffer of the multi-pass transform, one per stream (transforms in flight)
   DevBuf pw;                           // coset power tables + constants
-  DevBuf axis_pw;                      // G-point cross transform: root and its first G/2 powers
-  uint64_t axis_root[4] = {0, 0, 0, 0};
+  DevBuf axis_pw;                      // G-point cross transform: the first G/2 powers of the root (rebuilt by every call)
   DevBuf stage;                        // host-pointer entry: device copy of the data
   hipEvent_t ev[10] = {};              // pass timing (created on first use, reused)
   int kernel_variant = -1;             // -1: environment (ARK_HIP_FFT_LAZY), 0: saturated pass kernel, 1: carry-free
@@ -993,20 +992,20 @@ static inline bool fft_compact_env() {
 }
 struct FftTimings { float total = 0; float pass[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int npass = 0; };
 
-// root^k, k < G/2, for fft_axis_launch: built into the workspace's own small buffer (stream-ordered; `root4` is host
-// memory and is consumed before the call returns only if the caller synchronises -- pass memory that outlives the stream
-// work, e.g. a field of the domain struct copied into the workspace, as fft_axis_prepare does)
+// root^k, k < G/2, for fft_axis_launch: built into the workspace's own small buffer (stream-ordered).  `root4` is host
+// memory; it travels as a kernel argument, so it has been read when this returns and nothing of the workspace's host side
+// is in flight: the next call may bring another root at once (forward then inverse cross transform) -- no staging copy, no
+// wait, the sharded transform's pipeline stays as it was.
 template <class FP>
 int fft_axis_prepare(FftWorkspace& ws, unsigned G, const uint64_t* root4, hipStream_t stream, const u32** out_pw) {
   typedef Fp<FP> F;
   if (G != 2 && G != 4 && G != 8 && G != 16) return -2;
-  if (ws.axis_pw.ensure((1 + 16) * F::BYTES)) return -3;
-  u32* d_root = (u32*)ws.axis_pw.p;
-  u32* d_pw = d_root + F::N;
-  memcpy(ws.axis_root, root4, 32);  // stable host copy for the asynchronous upload
-  ARK_HIP_TRY(hipMemcpyAsync(d_root, ws.axis_root, F::BYTES, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL((fft_pow_table_kernel<FP>), dim3(1), dim3(256), 0, stream, d_root, (u64)1, (u32)(G / 2),
-                     (const u32*)nullptr, d_pw);
+  if (ws.axis_pw.ensure(16 * F::BYTES)) return -3;
+  u32* d_pw = (u32*)ws.axis_pw.p;
+  FftElemArg b, m;
+  memcpy(b.w, root4, 32);
+  memset(m.w, 0, 32);
+  hipLaunchKernelGGL((fft_pow_table_val_kernel<FP>), dim3(1), dim3(256), 0, stream, b, m, 0, (u32)(G / 2), d_pw);
   *out_pw = d_pw;
   return 0;
 }

@@ -13,7 +13,7 @@
 //          the entry is built
 //   cache: FftWorkspace::tables  (the map of the above)
 //   cache: FftWorkspace::powers  per (field, log n, offset, folded constant, form): coset power tables and single constants
-//   cache: FftWorkspace::axis_pw  the G-point cross transform's root powers, keyed by FftWorkspace::axis_root (and G)
+//   cache: FftWorkspace::axis_pw  the G-point cross transform's root powers: rebuilt, stream-ordered, by every call from the root it brings
 //   cache: BaseCacheEntry::dev  per (curve, host address, length), validated by a hash of the slice's full content on every call
 //   cache: PreparedBases::table  a handle the caller owns (ark_hip_msm_bases_prepare .. _free): per-window multiples of its bases
 //   cache: CsrSide::csr_ptr, CsrSide::csr_idx, CsrSide::csr_val, CsrSide::csr_work  a handle the caller owns (ark_hip_fr_csr_create .. _free): row_ptr, col_idx, vals and the row plan of M and, when asked for, of M^T

@@ -1089,6 +1089,14 @@ int ark_hip_test_csr_dump(const ark_hip_fr_csr* m, int transpose, size_t* dims, 
  * function the kernels of ark_hip_fr_lookup_device use (csrc/lookup_hash.hpp), so that a test can construct colliding tables
  * instead of hoping for them.  ARK_HIP_ERR_ARG for an unknown field, a null pointer or capacity_log outside 1 .. 29. */
 int ark_hip_test_lookup_slot(int field, const uint64_t* element, unsigned capacity_log, uint32_t* slot);
+/* ---- the asynchrony contract under a busy context stream (tests/test_gpu_async_contract.py) ----
+ * ark_hip_test_context_busy: *busy = 1 while work enqueued on the calling thread's context stream has not finished
+ * (hipStreamQuery; waits for nothing).  ark_hip_test_job_lane: the MSM lane (0 or 1) an *_async entry put the job on; host only.
+ * ark_hip_test_producer_marks(0): from here on no entry records the event that orders the second MSM lane behind the context
+ * stream's producers (process-wide, default on; (1) restores it) -- what a forgotten mark looks like, for the negative control. */
+int ark_hip_test_context_busy(int* busy);
+int ark_hip_test_job_lane(const ark_hip_msm_job* job, int* lane);
+int ark_hip_test_producer_marks(int on);
 
 #endif /* ARK_HIP_TEST_HOOKS */
 

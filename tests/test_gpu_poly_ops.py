@@ -15,6 +15,7 @@ import algebra_amd as A
 from algebra_amd._lib import lib
 import oracle_lib as O
 import pyref
+from poly_ops_ref import lagrange_reference, mont_list, synthetic_division, vanishing_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -69,17 +70,6 @@ def points(fname, seed):
     assert pow(w, T, p) == 1 and pow(w, T // 2, p) != 1
     return [("0", enc(0, p)), ("1", enc(1, p)), ("p-1", enc(p - 1, p)), ("random", O.gen_scalars(fid, seed, 1, montgomery=True)[0]),
             ("root of unity", enc(w, p))]
-
-
-def synthetic_division(cm, zc, p):
-    """coefficients as integers (Montgomery residues), canonical point -> (quotient list, remainder), same form"""
-    q = [0] * max(len(cm) - 1, 0)
-    s = 0
-    for i in range(len(cm) - 1, -1, -1):
-        if i < len(q):
-            q[i] = s
-        s = (cm[i] + zc * s) % p
-    return q, s
 
 
 SEAMS = sorted({n for lv in (2, 3) for n in (T ** (lv - 1), T ** (lv - 1) + 1, T ** (lv - 1) + 2)})   # first n of each further level, +- 1
@@ -137,23 +127,6 @@ def test_evaluate_and_divide_by_linear(fname, n):
     dp.free()
 
 
-def vanishing_reference(fid, a, m):
-    """dense.rs:168-211 restated on numpy arrays with the oracle's additions"""
-    n = a.shape[0]
-    if n < m:
-        return np.zeros((0, 4), dtype=np.uint64), a.copy()
-    q = a[m:].copy()
-    for i in range(1, n // m):
-        seg = a[m * (i + 1):]
-        if seg.shape[0]:
-            q[:seg.shape[0]] = O.field_op(fid, "add", q[:seg.shape[0]], seg).reshape(-1, 4)
-    r = a[:m].copy()
-    k = min(m, q.shape[0])
-    if k:
-        r[:k] = O.field_op(fid, "add", r[:k], q[:k]).reshape(-1, 4)
-    return q, r
-
-
 @pytest.mark.parametrize("fname", FR)
 @pytest.mark.parametrize("m", [1, 2, 1 << 10, 1 << 16])
 def test_divide_by_vanishing_poly(fname, m):
@@ -174,39 +147,6 @@ def test_divide_by_vanishing_poly(fname, m):
             r.free()
         assert np.array_equal(dp.to_host(), a)
         dp.free()
-
-
-def lagrange_reference(fname, log_n, h, tau):
-    """L_i(tau) = Z_H(tau) v_i / (tau - h g^i), v_i = g^i / (m h^(m-1)) (domain/mod.rs:157-222), canonical integers; one batch
-    inversion for all the denominators"""
-    p = pyref.MODULI[fname][0]
-    m = 1 << log_n
-    g = pyref.root_of_unity(fname, log_n)
-    zh = (pow(tau, m, p) - pow(h, m, p)) % p
-    assert zh, "tau lies in the domain"
-    den, pw = [0] * m, 1
-    for i in range(m):
-        den[i] = (tau - h * pw) % p
-        pw = pw * g % p
-    pre, run = [0] * m, 1
-    for i in range(m):
-        pre[i] = run
-        run = run * den[i] % p
-    inv = pow(run, -1, p)
-    out = [0] * m
-    k = zh * pow(m * pow(h, m - 1, p), -1, p) % p
-    gp = pow(g, m - 1, p) if m > 1 else 1
-    gi = pow(g, -1, p)
-    for i in range(m - 1, -1, -1):
-        out[i] = k * gp % p * (inv * pre[i] % p) % p
-        inv = inv * den[i] % p
-        gp = gp * gi % p
-    return out
-
-
-def mont_list(xs, p):
-    r = pyref.R_of(p)
-    return limbs([x * r % p for x in xs])
 
 
 @pytest.mark.parametrize("fname", FR)
