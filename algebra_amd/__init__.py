@@ -8,6 +8,7 @@ HIP library replaces:
     ark_poly::DenseMultilinearExtension -> algebra_amd.mle.DenseMultilinearExtension
     ark_linear_sumcheck's ListOfProductsOfPolynomials and its prover's rounds -> algebra_amd.sumcheck.ListOfProducts
     (no reference counterpart) SHA3-256 Merkle trees over column batches -> algebra_amd.merkle.MerkleTree
+    ark_ff's Fp2 / Fp4 over SmallFp, and (no reference counterpart) the FRI commit phase -> algebra_amd.fri
 
 All arithmetic runs in libark_hip.so (hand-written HIP for gfx950) through the C ABI of
 include/ark_hip.h; this package holds no arithmetic and no CPU fallback.
@@ -33,3 +34,5 @@ from .fraction_sum import FractionalSum, FractionalSumProof  # noqa: F401
 from .smallfp import (SMALL_FIELDS, SmallDeviceMatrix, SmallDeviceVec, SmallRadix2EvaluationDomain, small_fft_plan,  # noqa: F401
                       small_field_info, small_field_pow)
 from .merkle import MerkleTree, merkle_leaf_fr, merkle_leaf_small, merkle_node, merkle_plan  # noqa: F401
+from .fri import (FriProver, SmallExtVec, combine_columns, ext_inverse, ext_mul, ext_pow, fri_fold, fri_fold_row,  # noqa: F401
+                  fri_folded_domain, fri_plan, fri_verify_query, small_ext_degree, small_ext_info)

@@ -238,7 +238,26 @@ SYMBOLS = {
     "ark_hip_merkle_verify_fr": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.POINTER(C.c_int)]),
     "ark_hip_merkle_plan": (C.c_int, [C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(C.c_uint64)]),
+    "ark_hip_xfp_info": (C.c_int, [C.c_int, u64p]),
+    "ark_hip_xfp_mul": (C.c_int, [C.c_int, u64p, u64p, u64p]),
+    "ark_hip_xfp_inverse": (C.c_int, [C.c_int, u64p, u64p]),
+    "ark_hip_xfp_pow": (C.c_int, [C.c_int, u64p, C.c_uint64, u64p]),
+    "ark_hip_xfp_vec_mul": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "ark_hip_xfp_vec_inverse": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "ark_hip_xfp_vec_mul_const": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "ark_hip_xfp_vec_mul_base": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "ark_hip_xfp_combine_columns": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, u64p, C.c_uint64, C.c_void_p,
+                                              C.c_size_t, C.c_int]),
+    "ark_hip_fri_fold_row": (C.c_int, [C.c_int, C.POINTER(SmallRadix2DomainStruct), C.c_uint, C.c_uint64, u64p, u64p, u64p]),
+    "ark_hip_fri_folded_domain": (C.c_int, [C.c_int, C.POINTER(SmallRadix2DomainStruct), C.c_uint, C.POINTER(SmallRadix2DomainStruct)]),
+    "ark_hip_fri_plan": (C.c_int, [C.c_int, C.c_uint, C.c_uint, C.c_uint, u64p]),
+    "ark_hip_fri_fold": (C.c_int, [C.c_int, C.POINTER(SmallRadix2DomainStruct), C.c_uint, u64p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                   C.c_size_t]),
+    "ark_hip_fri_commit_phase": (C.c_int, [C.c_int, C.POINTER(SmallRadix2DomainStruct), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+# int (*ark_hip_fri_next_beta)(void* user, const uint8_t root[32], uint64_t beta_out[4])
+FriNextBeta = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64))
 
 # the test hooks: exported by libark_hip_test.so only (the same objects as libark_hip.so + csrc/capi_test.hip); declared in
 # include/ark_hip.h under ARK_HIP_TEST_HOOKS

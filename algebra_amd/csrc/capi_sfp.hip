@@ -1,15 +1,14 @@
 // C ABI of the one-word prime fields (ark_hip_sfp_*): host arithmetic, domains and the pass plan as pure host code, the
 // transforms and pointwise vectors through SmallFieldOps (sfp_internal.hpp).  DESIGN.md section 27.
-#include "capi_core.hpp"
-#include "sfp_fft.cuh"
-#include "sfp_internal.hpp"
+#include "capi_sfp.hpp"
 
 using namespace arkhip;
 using namespace arkhip::capi;
 
-namespace {
+// shared with capi_fri.hip (capi_sfp.hpp)
+namespace arkhip {
+namespace capi {
 
-// nullptr for an id this build does not serve (the development build serves none)
 const SmallFieldOps* sfp_ops(int sfield) {
 #ifndef ARK_HIP_DEV
   switch (sfield) {
@@ -21,23 +20,7 @@ const SmallFieldOps* sfp_ops(int sfield) {
   (void)sfield;
   return nullptr;
 }
-#define ARK_SFP_SWITCH(sfield, CALL)                       \
-  switch (sfield) {                                        \
-    case ARK_HIP_SFP_GOLDILOCKS: return CALL(GOLDILOCKS);  \
-    case ARK_HIP_SFP_BABYBEAR: return CALL(BABYBEAR);      \
-    case ARK_HIP_SFP_KOALABEAR: return CALL(KOALABEAR);    \
-  }                                                        \
-  return ARK_HIP_ERR_ARG
-
-// what the host code needs of a field, by id
-struct SfpHost {
-  int bytes, two_adicity;
-  uint64_t p, one;
-  uint64_t (*mul)(uint64_t, uint64_t);
-  uint64_t (*pow)(uint64_t, uint64_t);
-  uint64_t (*from_canonical)(uint64_t);
-  uint64_t root;
-};
+namespace {
 template <class Cfg>
 int host_of(SfpHost* h) {
   using F = SFp<Cfg>;
@@ -52,11 +35,62 @@ int host_of(SfpHost* h) {
   h->root = Cfg::ROOT;
   return 0;
 }
+}  // namespace
 int sfp_host(int sfield, SfpHost* h) {
 #define CALL(NAME) host_of<NAME>(h)
   ARK_SFP_SWITCH(sfield, CALL);
 #undef CALL
 }
+
+int domain_check(const SfpHost& h, const ark_hip_sfp_radix2_domain* dom) {
+  if (!dom || dom->log_size_of_group > (uint32_t)h.two_adicity || dom->size != (uint64_t)1 << dom->log_size_of_group)
+    return ARK_HIP_ERR_ARG;
+  const uint64_t el[7] = {dom->size_as_field_element, dom->size_inv, dom->group_gen, dom->group_gen_inv, dom->offset, dom->offset_inv,
+                          dom->offset_pow_size};
+  for (uint64_t e : el)
+    if (e >= h.p) return ARK_HIP_ERR_ARG;
+  return 0;
+}
+
+namespace {
+SfpPow32 squares_of(const SfpHost& h, uint64_t x) {
+  SfpPow32 pw;
+  for (int i = 0; i < 32; i++, x = h.mul(x, x)) pw.v[i] = x;
+  return pw;
+}
+}  // namespace
+
+int powers_for(Context* c, int sfield, const SfpHost& h, const SmallFieldOps* ops, int k, uint64_t g, uint64_t scale, SfpScale* out) {
+  const int lo_bits = (k + 1) / 2;
+  const size_t nhi = (size_t)1 << (k - lo_bits), nlo = (size_t)1 << lo_bits;
+  const auto key = std::make_tuple(sfield, k, g, scale);
+  auto it = c->sfp.sfp_powers.find(key);
+  if (it == c->sfp.sfp_powers.end()) {
+    if (c->sfp.sfp_powers.size() >= 256) {   // a caller that walks through offsets: start over (stream order keeps users apart)
+      for (auto& kv : c->sfp.sfp_powers) kv.second.release();
+      c->sfp.sfp_powers.clear();
+    }
+    it = c->sfp.sfp_powers.emplace(key, DevBuf()).first;
+    int rc = it->second.ensure((nhi + nlo) * h.bytes) ? ARK_HIP_ERR_NOMEM : 0;
+    if (!rc) rc = ops->powers(it->second.p, (char*)it->second.p + nhi * h.bytes, nhi, lo_bits, squares_of(h, g), scale, c->stream);
+    if (rc) {
+      it->second.release();
+      c->sfp.sfp_powers.erase(it);
+      return rc;
+    }
+  }
+  out->mode = SFP_SCALE_TABLE;
+  out->k = 0;
+  out->hi = it->second.p;
+  out->lo = (const char*)it->second.p + nhi * h.bytes;
+  return 0;
+}
+
+}  // namespace capi
+}  // namespace arkhip
+
+namespace {
+
 template <class Cfg>
 int info_of(uint64_t out[8]) {
   out[0] = sizeof(typename Cfg::T);
@@ -68,22 +102,6 @@ int info_of(uint64_t out[8]) {
   out[6] = Cfg::TWO_ADICITY;
   out[7] = Cfg::ROOT;
   return 0;
-}
-
-// a domain the transforms accept: the size matches its log and the field can hold it
-int domain_check(const SfpHost& h, const ark_hip_sfp_radix2_domain* dom) {
-  if (!dom || dom->log_size_of_group > (uint32_t)h.two_adicity || dom->size != (uint64_t)1 << dom->log_size_of_group)
-    return ARK_HIP_ERR_ARG;
-  const uint64_t el[7] = {dom->size_as_field_element, dom->size_inv, dom->group_gen, dom->group_gen_inv, dom->offset, dom->offset_inv,
-                          dom->offset_pow_size};
-  for (uint64_t e : el)
-    if (e >= h.p) return ARK_HIP_ERR_ARG;
-  return 0;
-}
-SfpPow32 squares_of(const SfpHost& h, uint64_t x) {
-  SfpPow32 pw;
-  for (int i = 0; i < 32; i++, x = h.mul(x, x)) pw.v[i] = x;
-  return pw;
 }
 
 // the cached per-stage twiddle tables of (sfield, k, direction); built on the stream on first use
@@ -113,33 +131,6 @@ int twiddles_for(Context* c, int sfield, const SfpHost& h, const SmallFieldOps* 
   *out = it->second.p;
   return 0;
 }
-// the cached two-level power table of (sfield, k, g, scale): hi | lo in one buffer
-int powers_for(Context* c, int sfield, const SfpHost& h, const SmallFieldOps* ops, int k, uint64_t g, uint64_t scale, SfpScale* out) {
-  const int lo_bits = (k + 1) / 2;
-  const size_t nhi = (size_t)1 << (k - lo_bits), nlo = (size_t)1 << lo_bits;
-  const auto key = std::make_tuple(sfield, k, g, scale);
-  auto it = c->sfp.sfp_powers.find(key);
-  if (it == c->sfp.sfp_powers.end()) {
-    if (c->sfp.sfp_powers.size() >= 256) {   // a caller that walks through offsets: start over (stream order keeps users apart)
-      for (auto& kv : c->sfp.sfp_powers) kv.second.release();
-      c->sfp.sfp_powers.clear();
-    }
-    it = c->sfp.sfp_powers.emplace(key, DevBuf()).first;
-    int rc = it->second.ensure((nhi + nlo) * h.bytes) ? ARK_HIP_ERR_NOMEM : 0;
-    if (!rc) rc = ops->powers(it->second.p, (char*)it->second.p + nhi * h.bytes, nhi, lo_bits, squares_of(h, g), scale, c->stream);
-    if (rc) {
-      it->second.release();
-      c->sfp.sfp_powers.erase(it);
-      return rc;
-    }
-  }
-  out->mode = SFP_SCALE_TABLE;
-  out->k = 0;
-  out->hi = it->second.p;
-  out->lo = (const char*)it->second.p + nhi * h.bytes;
-  return 0;
-}
-
 // arguments checked by the caller; enqueues on the context stream
 int fft_enqueue(Context* c, int sfield, const SfpHost& h, const SmallFieldOps* ops, const ark_hip_sfp_radix2_domain* dom, void* d_data,
                 size_t count, size_t stride, size_t num_coeffs, int inverse) {

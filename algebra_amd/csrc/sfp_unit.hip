@@ -1,6 +1,7 @@
-// Instantiation of the small-field transform and pointwise kernels for one one-word field: compiled once per field with
+// Instantiation of the small-field transform, pointwise, extension-field and fold kernels for one one-word field: compiled once per field with
 // -DARK_UNIT_SFIELD=<name>.  SmallFieldOpsOf is the one implementation of SmallFieldOps (sfp_internal.hpp).
 #include "sfp_fft.cuh"
+#include "sfp_fri.cuh"
 #include "sfp_internal.hpp"
 #ifndef ARK_UNIT_SFIELD
 #error "compile with -DARK_UNIT_SFIELD=GOLDILOCKS (or BABYBEAR, KOALABEAR)"
@@ -21,6 +22,15 @@ struct SmallFieldOpsOf final : SmallFieldOps {
   int vec_op(int op, const void* a, const void* b, uint64_t k, void* r, size_t n, hipStream_t s) const override {
     return sfp_vec_launch<Cfg>(op, a, b, k, r, n, s);
   }
+  int xvec_op(int op, const void* a, size_t sa, const void* b, size_t sb, const SfpxConst& k, void* r, size_t sr, size_t n,
+              hipStream_t s) const override {
+    return sfpx_vec_launch<Cfg>(op, a, sa, b, sb, k, r, sr, n, s);
+  }
+  int xcombine(const void* cols, size_t count, size_t stride, size_t rows, const SfpCombineArgs& ar, void* out, size_t so,
+               int accumulate, hipStream_t s) const override {
+    return sfpx_combine_launch<Cfg>(cols, count, stride, rows, ar, out, so, accumulate, s);
+  }
+  int xfold(const SfpFoldArgs& f, int log_arity, hipStream_t s) const override { return sfpx_fold_launch<Cfg>(f, log_arity, s); }
 };
 }  // namespace
 const SmallFieldOps& ARK_CAT(sfp_ops_, ARK_UNIT_SFIELD)() {

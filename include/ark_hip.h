@@ -938,6 +938,87 @@ int ark_hip_merkle_verify_fr(int field, const uint8_t root[32], size_t n, uint64
  * launch, the permutation variant in force (0: the transcript's, 1: the one shaped for these kernels) }. */
 int ark_hip_merkle_plan(size_t n, size_t count, unsigned elem_bytes, uint64_t out[8]);
 
+/* ---- extension fields over the one-word fields, and FRI over them.  The extension fields are the reference's tower models over
+ * SmallFp<P> (ff/src/fields/models/fp2.rs, fp4.rs, quadratic_extension.rs), so every output is a function of the field alone
+ * and bit-exact:
+ *   Goldilocks             Fp2 = Fp[u] / (u^2 - 7),                                  degree d = 2
+ *   BabyBear / KoalaBear   Fp4 = Fp2[v] / (v^2 - u) over Fp2 = Fp[u] / (u^2 - W),    d = 4, W = 11 / 3
+ *   With X = v the quartic field is Fp[X] / (X^4 - W), and (c0 = (a0, a1), c1 = (b0, b1)) is a0 + b0 X + a1 X^2 + b1 X^3.
+ *   7, 11 and 3 are non-squares (Euler's criterion); all three primes are 1 mod 4, so X^4 - W is irreducible.
+ *   Components, in memory and in every hash, in the order CanonicalSerialize writes them (quadratic_extension.rs:685-695):
+ *   c0, c1 for Fp2 and c0.c0, c0.c1, c1.c0, c1.c1 for Fp4, each a stored Montgomery word of the base field.
+ *   A single element crosses this interface as uint64_t[4], the upper two words zero for d = 2.
+ * Extension vector: a d-column matrix in the layout of ark_hip_sfp_fft_batch_device and ark_hip_merkle_commit_sfp_device:
+ *   component k of element i at element offset k * stride + i, stride >= n.  So the base-field transform with count = d is the
+ *   extension's transform over a base-field domain; ark_hip_sfp_add / sub / neg / scale_device over the whole allocation are the
+ *   extension's; the Merkle commit with count = d hashes header | serialize_compressed(element).  None needs a kernel of its own.
+ * Fold: f holds n = 2^k evaluations in natural order over the coset D = { h w^i } (dom: group_gen w, offset h).  For
+ *   log_arity a in 1 .. 3 and beta in the extension write f(X) = sum_{r < 2^a} X^r f_r(X^(2^a)); the fold is
+ *   g = sum_r beta^r f_r as n / 2^a evaluations in natural order over D' = { h^(2^a) w^(2^a i) } (ark_hip_fri_folded_domain).
+ *   a = 1, i < n / 2:   g[i] = (f[i] + f[i + n/2]) / 2 + beta (f[i] - f[i + n/2]) / (2 h w^i)
+ *   arity 2^a equals a successive 2-folds with beta, beta^2, beta^4.
+ *   Row i of a layer of size n at arity 2^a is the tuple f[i + j n / 2^a], j < 2^a.  A compact layer (stride = n) is also a
+ *   matrix of d 2^a columns of n / 2^a rows with stride n / 2^a, column k 2^a + j holding component k of f[. + j n / 2^a];
+ *   committing that view puts a whole row in one leaf, so one opening per layer answers a query.
+ * EVERY vector argument of this family (d_*) is DEVICE memory and every call that takes one is ASYNCHRONOUS on the context
+ * stream, as ark_hip_memcpy_d2d is -- except ark_hip_fri_commit_phase, which returns host results.  Challenges and constants are
+ * read before the call returns.
+ * ARK_HIP_ERR_ARG before any device is touched: an unknown sfield; a null pointer; log_arity outside 1 .. 3 or beyond the
+ * domain's log size; a fold left without a level to take ((num_folds - 1) * log_arity >= log n: only the LAST fold may be
+ * shorter); stride < n; a domain domain_check refuses (size != 2^log, an element >= p); a component >= p (or a non-zero upper
+ * word at d = 2) in a constant; in and out of a fold or of combine_columns overlapping; the workspaces of the commit phase
+ * overlapping layer 0 or each other, or not 16-byte aligned; a device pointer that is no multiple of the field's word.
+ * ARK_HIP_ERR_NO_DEVICE from the device entries without a GPU. */
+/* out = { d, W, W as stored, e_0, e_1, e_2, e_3, 0 }: component k is the coefficient of X^(e_k) in Fp[X] / (X^d - W).  Host only. */
+int ark_hip_xfp_info(int sfield, uint64_t out[8]);
+/* a * b, a^-1 (by the norm down the tower: one base-field inversion; 0 -> 0), a^exp.  Host only. */
+int ark_hip_xfp_mul(int sfield, const uint64_t a[4], const uint64_t b[4], uint64_t out[4]);
+int ark_hip_xfp_inverse(int sfield, const uint64_t a[4], uint64_t out[4]);
+int ark_hip_xfp_pow(int sfield, const uint64_t a[4], uint64_t exp, uint64_t out[4]);
+/* Pointwise on extension vectors of n elements (any n, 0 included); d_r may be d_a or d_b itself (the same pointer and stride).
+ * inverse: a zero stays zero.  mul_const: by one extension element.  mul_base: by a base-field vector of n words. */
+int ark_hip_xfp_vec_mul(int sfield, const void* d_a, size_t stride_a, const void* d_b, size_t stride_b, void* d_r, size_t stride_r,
+                        size_t n);
+int ark_hip_xfp_vec_inverse(int sfield, const void* d_a, size_t stride_a, void* d_r, size_t stride_r, size_t n);
+int ark_hip_xfp_vec_mul_const(int sfield, const void* d_a, size_t stride_a, const uint64_t k[4], void* d_r, size_t stride_r, size_t n);
+int ark_hip_xfp_vec_mul_base(int sfield, const void* d_a, size_t stride_a, const void* d_b, void* d_r, size_t stride_r, size_t n);
+/* d_out[i] = alpha^first_power * sum_{j < count} alpha^j col_j[i], i < rows, over a base-field matrix (count >= 1 columns,
+ * `stride` apart); d_out an extension vector.  accumulate != 0: added to what d_out holds, so several matrices chain with
+ * first_power = the columns before them. */
+int ark_hip_xfp_combine_columns(int sfield, const void* d_cols, size_t count, size_t stride, size_t rows, const uint64_t alpha[4],
+                                uint64_t first_power, void* d_out, size_t stride_out, int accumulate);
+/* The fold of one row through the function the kernel runs, host only: row[k * 2^a + j] = component k of f[index + j n / 2^a]
+ * (the order of an opened row of the row view), index < n / 2^a. */
+int ark_hip_fri_fold_row(int sfield, const ark_hip_sfp_radix2_domain* dom, unsigned log_arity, uint64_t index, const uint64_t* row,
+                         const uint64_t beta[4], uint64_t out[4]);
+/* D' of the fold: Radix2EvaluationDomain::new(n / 2^a).get_coset(h^(2^a)).  Host only. */
+int ark_hip_fri_folded_domain(int sfield, const ark_hip_sfp_radix2_domain* dom, unsigned log_arity, ark_hip_sfp_radix2_domain* out);
+/* The commit phase of 2^log_n elements with num_folds folds of log_arity levels (the last takes min(log_arity, what is left)),
+ * host only.  out holds 8 + 5 (num_folds + 1) words:
+ *   { d, layers = num_folds + 1, words of d_layers, bytes of d_trees, launches per fold, size of the last layer,
+ *     word offset in d_layers of the last layer's interpolated copy, 0 },
+ *   then per layer l = 0 .. num_folds: { log size, log arity of its fold (0: the last layer), word offset in d_layers (layer 0 is
+ *   the caller's: 0), byte offset of its tree in d_trees, lo_bits of its fold's power table (i -> hi[i >> lo_bits] lo[i & mask]) }.
+ * ARK_HIP_ERR_SIZE beyond the two-adicity. */
+int ark_hip_fri_plan(int sfield, unsigned log_n, unsigned log_arity, unsigned num_folds, uint64_t* out);
+/* d_out = the fold of d_in (dom->size elements over dom) by beta: dom->size >> log_arity elements.  One launch; the twiddles
+ * (2 h w^i)^-1 come from the cached two-level power table of (size, group_gen_inv, (2 h)^-1), built by one more launch on first
+ * use.  d_in is not written. */
+int ark_hip_fri_fold(int sfield, const ark_hip_sfp_radix2_domain* dom, unsigned log_arity, const uint64_t beta[4], const void* d_in,
+                     size_t stride_in, void* d_out, size_t stride_out);
+/* The challenge of a layer from its root, on the calling thread: beta_out[4] as every element here; non-zero ends the phase. */
+typedef int (*ark_hip_fri_next_beta)(void* user, const uint8_t root[32], uint64_t beta_out[4]);
+/* The commit phase.  Layer 0 (d_layer0: compact, stride = dom->size, never written) is the caller's; layers 1 .. num_folds, the
+ * interpolated copy of the last one and trees 0 .. num_folds - 1 go into d_layers and d_trees at the plan's offsets.  For each
+ * l < num_folds: commit the row view of layer l (one wait, for the root), next_beta(user, root, beta), fold into layer l + 1.
+ * The last layer is interpolated (the inverse coset transform with count = d, on a copy) and its d * size coefficient words, in
+ * memory form, are written to out_final (HOST); the num_folds roots to out_roots (HOST).  A non-zero return of next_beta, or a
+ * challenge that is no element, ends the phase with that code after a stream wait.  d_trees, next_beta and out_roots may be NULL
+ * when num_folds = 0. */
+int ark_hip_fri_commit_phase(int sfield, const ark_hip_sfp_radix2_domain* dom, unsigned log_arity, unsigned num_folds,
+                             const void* d_layer0, void* d_layers, void* d_trees, ark_hip_fri_next_beta next_beta, void* user,
+                             uint8_t* out_roots, void* out_final);
+
 #ifdef ARK_HIP_TEST_HOOKS
 /* ---- device-arithmetic test hooks (used by tests/ to check the kernels' field and point
  * arithmetic against the oracle; host pointers) ----

@@ -1906,4 +1906,262 @@ class MerkleTree {
   bool have_root_ = false;
 };
 
+// ---- extension fields over the one-word fields, and FRI over them (ark_hip_xfp_*, ark_hip_fri_*) ----------------------------------
+// Fp2 = Fp[u] / (u^2 - 7) over Goldilocks; Fp4 = Fp2[v] / (v^2 - u) over Fp2 = Fp[u] / (u^2 - W) for BabyBear (W = 11) and KoalaBear
+// (W = 3): the reference's tower models over SmallFp<P>.  An element is its d components in the order CanonicalSerialize writes
+// them, each a stored word, zero-extended to four.
+using ExtElement = std::array<uint64_t, 4>;
+template <int SFIELD_ID>
+constexpr unsigned small_ext_degree() { return SFIELD_ID == ARK_HIP_SFP_GOLDILOCKS ? 2 : 4; }
+struct SmallExtInfo { unsigned degree; uint64_t w, w_stored; std::array<unsigned, 4> exponents; };
+template <int SFIELD_ID>
+inline SmallExtInfo small_ext_info() {
+  uint64_t o[8];
+  check(ark_hip_xfp_info(SFIELD_ID, o), "ark_hip_xfp_info");
+  return SmallExtInfo{(unsigned)o[0], o[1], o[2], {(unsigned)o[3], (unsigned)o[4], (unsigned)o[5], (unsigned)o[6]}};
+}
+template <int SFIELD_ID>
+inline ExtElement ext_mul(const ExtElement& a, const ExtElement& b) {
+  ExtElement r;
+  check(ark_hip_xfp_mul(SFIELD_ID, a.data(), b.data(), r.data()), "ark_hip_xfp_mul");
+  return r;
+}
+template <int SFIELD_ID>
+inline ExtElement ext_inverse(const ExtElement& a) {
+  ExtElement r;
+  check(ark_hip_xfp_inverse(SFIELD_ID, a.data(), r.data()), "ark_hip_xfp_inverse");
+  return r;
+}
+template <int SFIELD_ID>
+inline ExtElement ext_pow(const ExtElement& a, uint64_t e) {
+  ExtElement r;
+  check(ark_hip_xfp_pow(SFIELD_ID, a.data(), e, r.data()), "ark_hip_xfp_pow");
+  return r;
+}
+
+// n extension elements on the device: d columns of `stride` words in one SmallDeviceVec, component k at element offset k * stride.
+// The base-field transform with count = d, += / -= / negate / scale of data() and MerkleTree::commit_small with count = d are the
+// extension's.
+template <int SFIELD_ID>
+class SmallExtVec {
+ public:
+  using Word = typename SmallWord<SFIELD_ID>::type;
+  static constexpr unsigned D = small_ext_degree<SFIELD_ID>();
+  SmallExtVec() = default;
+  explicit SmallExtVec(size_t n, size_t stride = 0) : data_(D * (stride ? stride : n)), n_(n), stride_(stride ? stride : n) {
+    if (stride_ < n_) throw Error(ARK_HIP_ERR_ARG, "stride >= n");
+  }
+  // components: d vectors of n stored words
+  static SmallExtVec from_components(const std::vector<std::vector<Word>>& c) {
+    if (c.size() != D) throw Error(ARK_HIP_ERR_ARG, "d components");
+    std::vector<Word> flat;
+    for (const auto& col : c) {
+      if (col.size() != c[0].size()) throw Error(ARK_HIP_ERR_ARG, "components of one length");
+      flat.insert(flat.end(), col.begin(), col.end());
+    }
+    SmallExtVec v;
+    v.n_ = v.stride_ = c[0].size();
+    v.data_ = SmallDeviceVec<SFIELD_ID>::from_vec(flat);
+    return v;
+  }
+  size_t len() const { return n_; }
+  size_t stride() const { return stride_; }
+  SmallDeviceVec<SFIELD_ID>& data() { return data_; }
+  const SmallDeviceVec<SFIELD_ID>& data() const { return data_; }
+  void* device_ptr() { return data_.device_ptr(); }
+  const void* device_ptr() const { return data_.device_ptr(); }
+  SmallExtVec& operator*=(const SmallExtVec& o) {
+    if (o.n_ != n_) throw Error(ARK_HIP_ERR_ARG, "vectors of one length are combined");
+    check(ark_hip_xfp_vec_mul(SFIELD_ID, device_ptr(), stride_, o.device_ptr(), o.stride_, device_ptr(), stride_, n_), "ark_hip_xfp_vec_mul");
+    return *this;
+  }
+  SmallExtVec& batch_inverse() {
+    check(ark_hip_xfp_vec_inverse(SFIELD_ID, device_ptr(), stride_, device_ptr(), stride_, n_), "ark_hip_xfp_vec_inverse");
+    return *this;
+  }
+  SmallExtVec& mul_const(const ExtElement& k) {
+    check(ark_hip_xfp_vec_mul_const(SFIELD_ID, device_ptr(), stride_, k.data(), device_ptr(), stride_, n_), "ark_hip_xfp_vec_mul_const");
+    return *this;
+  }
+  SmallExtVec& mul_base(const SmallDeviceVec<SFIELD_ID>& b) {
+    if (b.len() != n_) throw Error(ARK_HIP_ERR_ARG, "one base-field word per element");
+    check(ark_hip_xfp_vec_mul_base(SFIELD_ID, device_ptr(), stride_, b.device_ptr(), device_ptr(), stride_, n_), "ark_hip_xfp_vec_mul_base");
+    return *this;
+  }
+
+ private:
+  SmallDeviceVec<SFIELD_ID> data_;
+  size_t n_ = 0, stride_ = 0;
+};
+
+// out[i] (+)= alpha^first_power * sum_j alpha^j col_j[i] over `count` columns of `rows` words, `stride` apart, inside `cols`
+template <int SFIELD_ID>
+inline void combine_columns(const SmallDeviceVec<SFIELD_ID>& cols, size_t count, size_t stride, size_t rows, const ExtElement& alpha,
+                            SmallExtVec<SFIELD_ID>& out, uint64_t first_power = 0, bool accumulate = false) {
+  if (count == 0 || stride < rows || (count - 1) * stride + rows > cols.len() || out.len() != rows)
+    throw Error(ARK_HIP_ERR_ARG, "the matrix lies inside the vector, one element per row");
+  check(ark_hip_xfp_combine_columns(SFIELD_ID, cols.device_ptr(), count, stride, rows, alpha.data(), first_power, out.device_ptr(), out.stride(),
+                                    accumulate ? 1 : 0), "ark_hip_xfp_combine_columns");
+}
+
+struct FriLayer { unsigned log_size, log_arity; uint64_t layer_offset, tree_offset; unsigned lo_bits; };
+struct FriPlan { unsigned degree; uint64_t layer_words, tree_bytes, launches_per_fold, final_size, final_copy_offset; std::vector<FriLayer> layers; };
+template <int SFIELD_ID>
+inline FriPlan fri_plan(unsigned log_n, unsigned log_arity, unsigned num_folds) {
+  std::vector<uint64_t> o(8 + 5 * ((size_t)num_folds + 1));
+  check(ark_hip_fri_plan(SFIELD_ID, log_n, log_arity, num_folds, o.data()), "ark_hip_fri_plan");
+  FriPlan p{(unsigned)o[0], o[2], o[3], o[4], o[5], o[6], {}};
+  for (size_t l = 0; l < o[1]; l++)
+    p.layers.push_back(FriLayer{(unsigned)o[8 + 5 * l], (unsigned)o[9 + 5 * l], o[10 + 5 * l], o[11 + 5 * l], (unsigned)o[12 + 5 * l]});
+  return p;
+}
+template <int SFIELD_ID>
+inline ark_hip_sfp_radix2_domain fri_folded_domain(const ark_hip_sfp_radix2_domain& dom, unsigned log_arity) {
+  ark_hip_sfp_radix2_domain out;
+  check(ark_hip_fri_folded_domain(SFIELD_ID, &dom, log_arity, &out), "ark_hip_fri_folded_domain");
+  return out;
+}
+// the fold of one opened row: row[k * 2^a + j] = component k of f[index + j n / 2^a]
+template <int SFIELD_ID>
+inline ExtElement fri_fold_row(const ark_hip_sfp_radix2_domain& dom, unsigned log_arity, uint64_t index, const std::vector<uint64_t>& row,
+                               const ExtElement& beta) {
+  if (row.size() != ((size_t)small_ext_degree<SFIELD_ID>() << log_arity)) throw Error(ARK_HIP_ERR_ARG, "a row holds d * 2^log_arity words");
+  ExtElement r;
+  check(ark_hip_fri_fold_row(SFIELD_ID, &dom, log_arity, index, row.data(), beta.data(), r.data()), "ark_hip_fri_fold_row");
+  return r;
+}
+template <int SFIELD_ID>
+inline SmallExtVec<SFIELD_ID> fri_fold(const SmallExtVec<SFIELD_ID>& f, const SmallRadix2EvaluationDomain<SFIELD_ID>& dom, unsigned log_arity,
+                                       const ExtElement& beta) {
+  if (f.len() != dom.size()) throw Error(ARK_HIP_ERR_ARG, "one evaluation per element of the domain");
+  SmallExtVec<SFIELD_ID> out(f.len() >> log_arity);
+  check(ark_hip_fri_fold(SFIELD_ID, &dom.raw(), log_arity, beta.data(), f.device_ptr(), f.stride(), out.device_ptr(), out.stride()),
+        "ark_hip_fri_fold");
+  return out;
+}
+
+// The commit phase over a compact SmallExtVec of dom.size() evaluations (layer 0, never written; it must outlive the prover).
+template <int SFIELD_ID>
+class FriProver {
+ public:
+  using Word = typename SmallWord<SFIELD_ID>::type;
+  static constexpr unsigned D = small_ext_degree<SFIELD_ID>();
+  // the challenge of a layer from its root
+  struct Challenger {
+    virtual ExtElement next_beta(const Digest& root) = 0;
+    virtual ~Challenger() = default;
+  };
+  FriProver(const SmallExtVec<SFIELD_ID>& layer0, const SmallRadix2EvaluationDomain<SFIELD_ID>& dom, unsigned log_arity, unsigned num_folds)
+      : layer0_(&layer0), dom_(dom.raw()), log_arity_(log_arity), num_folds_(num_folds),
+        plan_(fri_plan<SFIELD_ID>(dom.log_size_of_group(), log_arity, num_folds)) {
+    if (layer0.len() != dom.size() || layer0.stride() != layer0.len()) throw Error(ARK_HIP_ERR_ARG, "layer 0 is compact and fills the domain");
+    check(ark_hip_malloc(plan_.layer_words * sizeof(Word), &layers_), "ark_hip_malloc");
+    check(ark_hip_malloc(plan_.tree_bytes ? plan_.tree_bytes : 16, &trees_), "ark_hip_malloc");
+  }
+  FriProver(const FriProver&) = delete;
+  FriProver& operator=(const FriProver&) = delete;
+  ~FriProver() {
+    if (layers_) (void)ark_hip_free(layers_);
+    if (trees_) (void)ark_hip_free(trees_);
+  }
+  const FriPlan& plan() const { return plan_; }
+  // fills roots(), betas() and final_poly() (d * size stored coefficient words of the last layer, component by component)
+  void commit_phase(Challenger& ch) {
+    State st{&ch, &betas_};
+    betas_.clear();
+    roots_.assign(num_folds_, Digest{});
+    final_.assign((size_t)D * plan_.final_size, 0);
+    check(ark_hip_fri_commit_phase(SFIELD_ID, &dom_, log_arity_, num_folds_, layer0_->device_ptr(), layers_, trees_, &FriProver::trampoline, &st,
+                                   num_folds_ ? roots_[0].data() : nullptr, final_.data()), "ark_hip_fri_commit_phase");
+  }
+  const std::vector<Digest>& roots() const { return roots_; }
+  const std::vector<ExtElement>& betas() const { return betas_; }
+  const std::vector<Word>& final_poly() const { return final_; }
+  const void* layer_ptr(unsigned l) const {
+    return l == 0 ? layer0_->device_ptr() : (const void*)((const char*)layers_ + plan_.layers[l].layer_offset * sizeof(Word));
+  }
+  // per layer l < num_folds: the rows (d * 2^a words each) and paths of index mod rows, one opening per index
+  std::vector<MerkleTree::Opening> query(std::vector<uint64_t> indices) const {
+    std::vector<MerkleTree::Opening> out;
+    for (unsigned l = 0; l < num_folds_; l++) {
+      const FriLayer& lay = plan_.layers[l];
+      const size_t rows = (size_t)1 << (lay.log_size - lay.log_arity), count = (size_t)D << lay.log_arity;
+      for (auto& i : indices) i %= rows;
+      MerkleTree::Opening o;
+      o.paths.resize(indices.size() * (lay.log_size - lay.log_arity) * ARK_HIP_MERKLE_DIGEST_BYTES);
+      o.rows.resize(indices.size() * count * sizeof(Word));
+      check(ark_hip_merkle_open_device((const char*)trees_ + lay.tree_offset, rows, layer_ptr(l), sizeof(Word), count, rows, indices.data(),
+                                       indices.size(), o.rows.data(), o.paths.data()), "ark_hip_merkle_open_device");
+      out.push_back(std::move(o));
+    }
+    return out;
+  }
+
+ private:
+  struct State { Challenger* ch; std::vector<ExtElement>* betas; };
+  static int trampoline(void* user, const uint8_t root[32], uint64_t beta_out[4]) {
+    State* st = (State*)user;
+    Digest d;
+    std::memcpy(d.data(), root, d.size());
+    const ExtElement b = st->ch->next_beta(d);
+    st->betas->push_back(b);
+    std::memcpy(beta_out, b.data(), sizeof(uint64_t) * 4);
+    return 0;
+  }
+  const SmallExtVec<SFIELD_ID>* layer0_;
+  ark_hip_sfp_radix2_domain dom_;
+  unsigned log_arity_, num_folds_;
+  FriPlan plan_;
+  void* layers_ = nullptr;
+  void* trees_ = nullptr;
+  std::vector<Digest> roots_;
+  std::vector<ExtElement> betas_;
+  std::vector<Word> final_;
+};
+
+// One query of a commit phase, on the host: rows[l] / paths[l] open row (position mod rows) of layer l.  Every row must open
+// against its root and carry the value the previous fold produced; the last fold must equal the final polynomial at its point.
+template <int SFIELD_ID>
+inline bool fri_verify_query(const ark_hip_sfp_radix2_domain& dom, unsigned log_arity, const std::vector<Digest>& roots,
+                             const std::vector<ExtElement>& betas, const std::vector<typename SmallWord<SFIELD_ID>::type>& final_poly,
+                             uint64_t index, const std::vector<std::vector<typename SmallWord<SFIELD_ID>::type>>& rows,
+                             const std::vector<std::vector<uint8_t>>& paths) {
+  constexpr unsigned D = small_ext_degree<SFIELD_ID>();
+  const unsigned num_folds = (unsigned)roots.size();
+  const FriPlan plan = fri_plan<SFIELD_ID>(dom.log_size_of_group, log_arity, num_folds);
+  const uint64_t p = small_field_info<SFIELD_ID>().p;
+  if (betas.size() != num_folds || rows.size() != num_folds || paths.size() != num_folds || final_poly.size() != D * plan.final_size) return false;
+  ark_hip_sfp_radix2_domain cur = dom;
+  uint64_t pos = index % dom.size;
+  ExtElement value{};
+  bool have = false;
+  for (unsigned l = 0; l < num_folds; l++) {
+    const unsigned a = plan.layers[l].log_arity;
+    const uint64_t m = (uint64_t)1 << (plan.layers[l].log_size - a), r = pos % m, j = pos / m;
+    if (rows[l].size() != ((size_t)D << a) || paths[l].size() != (size_t)(plan.layers[l].log_size - a) * ARK_HIP_MERKLE_DIGEST_BYTES) return false;
+    if (!MerkleTree::verify_small<SFIELD_ID>(roots[l], m, r, rows[l].data(), rows[l].size(), paths[l].data())) return false;
+    std::vector<uint64_t> row(rows[l].begin(), rows[l].end());
+    for (uint64_t w : row)
+      if (w >= p) return false;
+    if (have)
+      for (unsigned k = 0; k < D; k++)
+        if (row[((size_t)k << a) + j] != value[k]) return false;
+    value = fri_fold_row<SFIELD_ID>(cur, a, r, row, betas[l]);
+    have = true;
+    cur = fri_folded_domain<SFIELD_ID>(cur, a);
+    pos = r;
+  }
+  if (!have) return true;
+  const ExtElement x = ext_mul<SFIELD_ID>(ExtElement{cur.offset, 0, 0, 0}, ExtElement{small_field_pow<SFIELD_ID>(cur.group_gen, pos), 0, 0, 0});
+  ExtElement acc{};
+  for (size_t i = plan.final_size; i-- > 0;) {   // Horner on every component: x lies in the base field
+    acc = ext_mul<SFIELD_ID>(acc, x);
+    for (unsigned k = 0; k < D; k++) {
+      const unsigned __int128 s = (unsigned __int128)acc[k] + final_poly[k * plan.final_size + i];
+      acc[k] = (uint64_t)(s % p);
+    }
+  }
+  return acc == value;
+}
+
 }  // namespace ark_hip
